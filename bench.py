@@ -2,6 +2,8 @@
 """bench.py — env-steps/s of the batched quadrotor step on MI355X (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 1000 --warmup 50
+    python bench.py --gpus 1 --steps 1000 --warmup 50 --full      (+ every secondary figure below)
+    python bench.py ... --dump-outputs DIR                         (+ the last timed step's outputs as DIR/<name>.npy)
     python bench.py --gpus N ...          (no launcher: starts the N ranks itself as child processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -13,32 +15,35 @@ Random actions terminate an episode within ~100 steps, so — like every loop of
 that steps an env (main.py:183-186 resets on done) — terminated envs are re-sampled, here
 inside the same launch (QR_FLAG_AUTO_RESET, ~1.2 % of the envs per step).  The free-running
 variant (--no-auto-reset: step() alone, the population tumbling far beyond termination, where
-the rate-adaptive substep count adds work) is timed too and reported under
-config.other_reset_mode.  Envs are sharded over ranks
+the rate-adaptive substep count adds work) is timed too (--full) and reported under
+config.free_run_us.  Envs are sharded over ranks
 with NO collective on the step path (weak scaling: 65 536 envs per GPU); `value` = all ranks'
 env-steps / the max-over-ranks time of the K timed steps, inputs resident in HBM.
 
-Timing.  The K steps are one hipGraph of K captured qr_step launches (default) or K eager calls
-(--mode eager).  One timed REPETITION = barrier + synchronize, an untimed lead-in replay of
-max(10, 300 - K) steps (so that the K timed launches are queued behind running work — no host
-submission latency inside the timed region — and run at busy clocks, not on the ramp that
-follows the barrier's idle gap), HIP event, the K steps, HIP event, synchronize + barrier.  For
-K < 300 the timed graph holds ceil(300 / K) back-to-back copies of the K steps and the event
-time is divided by that count: a graph launch costs a fixed ~9 us on the device, which would
-otherwise weigh 8 % at K = 20 and 0.2 % at K = 1000.  Repetitions
-are made until >= 20 of them AND >= 50 ms of timed work exist (at most 200); the MEDIAN
-repetition is reported, after a MAX over ranks.  ONE clock feeds every figure of the line: the
-HIP-event time of the K steps on the launch stream -> `ms_per_step`, `value` = envs x K / that
-time, `roofline.achieved` = SURVEY.md 8(d) algorithmic bytes per launch / (that time / K) (the
-same number again as `roofline.avg_launch_us`).  The host wall clock of the same repetitions
-(which adds the graph submission and the synchronize round trip, ~20 us per repetition whatever
-K is) is reported beside it as `wall_ms_per_step`; `--steps 20` and `--steps 1000` therefore
-agree.  The default 1-GPU run then replays the headline graph back to back for --sustain seconds
-(3) without synchronising in between: `config.sustained_us` / `sustained_steps`, the rate under sustained load.
+Timing of the headline.  W = --warmup eager env-steps, then the K = --steps timed env-steps are captured as hipGraphs of at most
+GRAPH_LAUNCHES launches each (replayed untimed for ~50 ms — upload, busy clocks — after which the envs are put back into the state
+they had before those replays) or issued as K eager calls (--mode eager).  The ONE
+timed pass = barrier + synchronize, an untimed lead-in replay of max(10, 300 - K) steps (so that the timed launches are queued
+behind running work — no host submission latency inside the timed region — and run at busy clocks, not on the ramp that follows
+the barrier's idle gap), HIP event, exactly K steps (back-to-back graph replays), HIP event, synchronize + barrier; a MAX over
+ranks.  A graph launch costs a fixed ~9 us on the device: it weighs 0.2 % per 1000-launch graph, but 8 % at K = 20.  ONE clock
+feeds every figure of the line: the HIP-event time of the K steps on the launch stream -> `ms_per_step`, `value` = envs x K / that
+time, `roofline.achieved` = SURVEY.md 8(d) algorithmic bytes per launch / (that time / K) (the same number again as
+`roofline.avg_launch_us`).  The host wall clock of the same pass (which adds the graph submission and the synchronize round trip,
+~20 us whatever K is) is reported beside it as `wall_ms_per_step`.  The inputs (states, parameters, action slabs) come from fixed
+seeds and every step count above is fixed, so the same arguments step the same envs through the same steps: --dump-outputs DIR
+then writes what the LAST timed step returned to its caller (observation rows when the env has them, reward, terminated,
+truncated; the rows of the last env-step of a fused launch) and the state after it (get_current_state()), as float32 / float64
+DIR/<name>.npy, at most 64 MB in all (beyond that the same seeded sample of env rows from every array).
 `roofline.traffic` = HBM bytes per launch from the rocprofv3 PMC passes committed under
 profiles/ (tools/profile.sh), when one exists for this configuration.
 
-Secondary figures (rank 0, --extras 1), all through the same harness as the headline and all FLAT scalars under `config` (the
+A plain run measures the headline and nothing else.  --full adds everything below; the 1-GPU --full run first replays the
+headline's graphs back to back for --sustain seconds (3) without synchronising in between: `config.sustained_us` /
+`sustained_steps`, the rate under sustained load.
+
+Secondary figures (--full, rank 0, --extras 1), each timed in repetitions of its fixed step count (an untimed lead-in, HIP events
+around the steps; >= 20 repetitions AND >= 50 ms of timed work, at most 200; the MEDIAN repetition) and all FLAT scalars under `config` (the
 driver's record keeps scalars and drops nested lists; the whole line stays under 6 KB): `free_run_us` (the other reset mode), and
 per BASELINE.json configuration `<tag>_us` (us per launch), `<tag>_frac` (SURVEY 8(d) algorithmic bytes / time / 8 TB/s) and
 `<tag>_noop_us` (qr_touch over the same buffers: the do-nothing kernel that moves the step's bytes) for
@@ -50,7 +55,7 @@ Other runs, one flag each: `--config 2|3|4` = BASELINE.json con
 65 536; DecoupledWrapper 32 768 per GPU; Quad-v0 131 072 per GPU x 10 substeps), `--scaling strong` = a fixed global batch (the
 preset's named total, or --global-envs) cut into 64-aligned shards over the ranks, reported as `"scaling": "strong"`.
 
-`cpu_baseline` (rank 0, N=1 only) times the oracle's reference-style single-env path (NumPy RHS
+`cpu_baseline` (--full, rank 0, N=1 only) times the oracle's reference-style single-env path (NumPy RHS
 + scipy DOP853 + ensure_SO3, reset-on-done; oracle/quad_oracle.py) on one host core for ~12 s.
 """
 from __future__ import annotations
@@ -113,13 +118,19 @@ def secondary_keys():
 MAX_LINE_BYTES = 6144  # the driver keeps 8 KB of stdout: the JSON line must fit with room to spare (asserted before printing)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 HBM_COPY_GBS = 6290.0  # that measured copy ceiling: SURVEY.md 8(d) asks for the fraction of both
+GRAPH_LAUNCHES = 1000  # launches per captured graph of the headline's timed pass (a longer pass replays it back to back)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this many bytes in all
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=1000)   # K steps per timed repetition (>= 20 repetitions, >= 50 ms of timed work)
+    p.add_argument("--steps", type=int, default=1000)   # K: the headline times exactly K env-steps (whole launches of --horizon)
     p.add_argument("--warmup", type=int, default=50)
+    p.add_argument("--full", action="store_true", help="also measure every secondary figure: sustained rate, no-op kernel, the other reset "
+                                                       "mode, the other BASELINE.json configs, the float64 layout, the CPU baseline")
+    p.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step returned (and the state after it) as "
+                                                                     "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     p.add_argument("--envs", type=int, default=65536, help="envs PER GPU")
     p.add_argument("--kind", default="quad", choices=["quad", "coupled", "decoupled"])
     p.add_argument("--substeps", type=int, default=1)
@@ -128,12 +139,12 @@ def parse():
     p.add_argument("--auto-reset", action=argparse.BooleanOptionalAction, default=True,
                    help="re-sample terminated envs inside the launch (what a loop that steps the reference's env does on done); "
                         "--no-auto-reset = T free-running random-action steps from one reset")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU baseline leg (0 = skip)")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU baseline leg of --full (0 = skip)")
     p.add_argument("--action-batches", type=int, default=64, help="distinct pre-generated [N,A] action slabs cycled through (64 x 1 MiB > L2: every step streams its actions)")
-    p.add_argument("--extras", type=int, default=1, help="0: only the headline measurement (used under rocprofv3); 1: + config.other_reset_mode and "
+    p.add_argument("--extras", type=int, default=1, help="with --full, 0: only the headline measurement; 1: + config.other_reset_mode and "
                                                          "config.baseline_configs within --extras-budget; 2: all of them whatever they take")
-    p.add_argument("--sustain", type=float, default=3.0, help="seconds of back-to-back replays of the headline graph after the timed repetitions (config.sustained_us; 0 = skip; 1-GPU default run only)")
-    p.add_argument("--extras-budget", type=float, default=60.0, help="seconds after which the remaining secondary rows are skipped (--extras 1)")
+    p.add_argument("--sustain", type=float, default=3.0, help="seconds of back-to-back replays of the headline graphs after the timed pass (config.sustained_us; 0 = skip; 1-GPU --full run only)")
+    p.add_argument("--extras-budget", type=float, default=60.0, help="seconds after which the remaining secondary rows are skipped (--full --extras 1)")
     p.add_argument("--actor", default="ppo", choices=["ppo", "sac"], help="--workload rollout_actor: the actor form (ppo: parameter log_std, "
                                                                             "tanh-of-mean rule; sac: state-dependent log_std head, tanh-of-sample rule = the POLICY=2 kernel)")
     p.add_argument("--workload", default="step", choices=["step", "rollout", "rollout_actor", "touch"],
@@ -152,6 +163,8 @@ def parse():
                         "--global-envs, default the preset's named total or --envs — cut into 64-aligned shards over the ranks (shard_range)")
     p.add_argument("--global-envs", type=int, default=0, help="global batch of --scaling strong")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     if a.config:
         preset = PRESETS[a.config]
         a.kind, a.envs, a.substeps = preset["kind"], preset["envs"], preset["substeps"]
@@ -332,6 +345,36 @@ def algo_bytes_per_env_step(kind: str, workload: str = "step", H: int = 1) -> fl
     return per_step_io + once / H
 
 
+def step_outputs(ret, env, H: int) -> dict:
+    """What the last timed launch returned to its caller — its last env-step's rows for the fused launches — and the state after
+    it, as host float32 / float64 arrays with the env axis first: {name: array}."""
+    rows = {}
+    if isinstance(ret, dict):   # rollout() / rollout_actor(): [H, N, ...] rows ("obs" repeats obs0 / obs1)
+        rows = {k: v[H - 1] for k, v in ret.items() if k != "obs" and isinstance(v, torch.Tensor)}
+    elif ret is not None:       # step(): (obs, reward, terminated, truncated, info); obs is None for Quad-v0 without observation rows
+        obs, rows["reward"], rows["terminated"], rows["truncated"], _ = ret
+        obs = [] if obs is None else [obs] if isinstance(obs, torch.Tensor) else list(obs)
+        rows.update({f"obs{j}": o for j, o in enumerate(obs)})
+    rows["state"] = env.get_current_state()   # float64 [N, 18]
+    out = {}
+    for k, v in rows.items():
+        v = v.cpu().numpy()
+        out[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float32 if v.dtype == np.bool_ else np.float64)
+    return out
+
+
+def dump_outputs(arrays: dict, d: str, suffix: str, budget: int):
+    """DIR/<name><suffix>.npy for every array; above `budget` bytes in all, the same seeded sample of env rows from each."""
+    os.makedirs(d, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, int(budget // (total / n)), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}{suffix}.npy"), np.ascontiguousarray(v))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -359,12 +402,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def run(w, ar: bool, timed: bool, sustain_s: float = 0.0):
+    def run(w, ar: bool, timed: bool, sustain_s: float = 0.0, one_pass: bool = False, outputs: bool = False):
         """`w` = the workload (kind, envs, env_offset, substeps, workload, horizon, steps, slabs, helper, actor).  W warm-up
-        steps, then repetitions of exactly K = w.steps timed env-steps; returns the per-repetition (HIP-event ms, wall ms) lists
-        and a few facts about the final state.  timed=False: no cross-rank barrier (rank-0-only secondary measurements).
-        sustain_s > 0 (graph mode, in-launch resets): afterwards the timed graph is replayed back to back for about that many seconds
-        with NO synchronisation in between — the rate the chip holds under sustained load (its clocks under power, not a 4 ms burst)."""
+        steps, then repetitions of exactly K = w.steps timed env-steps (one_pass: ONE of them, replaying graphs of at most
+        GRAPH_LAUNCHES launches); returns the per-repetition (HIP-event ms, wall ms) lists and a few facts about the final state.
+        timed=False: no cross-rank barrier (rank-0-only secondary measurements).  outputs: also the last timed step's outputs
+        (host arrays).  sustain_s > 0 (graph mode, in-launch resets): afterwards the timed graphs are replayed back to back for about
+        that many seconds with NO synchronisation in between — the rate the chip holds under sustained load (its clocks under power,
+        not a 4 ms burst)."""
         H, K, n = w.horizon, w.steps, w.envs
         env = QuadVecEnv(w.kind, n, device=dev, seed=0, substeps=w.substeps, layout=getattr(w, "layout", a.layout), use_UDM=True,
                          auto_reset=ar, env_offset=w.env_offset, **{"helper" if w.workload in ("step", "touch") else "helper_rollout": TRI[w.helper]},
@@ -397,37 +442,53 @@ def main():
             pout = {k: v for k, v in po.items() if k != "obs"}
             launch = lambda i: env.rollout_actor(actors, H, out=pout)              # noqa: E731
             last_done = lambda: pout["terminated"][H - 1]                          # noqa: E731
-        n_launch = K // H
+        n_launch, ret = K // H, None   # ret: what the last timed launch returns to its caller
         for i in range(-(-a.warmup // H)):
             launch(i)
         # untimed lead-in of every repetition: long enough (~1.5 ms) to bring the chip back to its busy clocks after the
         # barrier's idle gap — the first ~50 launches after an idle period run 5-20 % slow — and to keep the queue ahead
         n_lead = max(10, 300 - K) if H == 1 else max(1, 300 // H)     # (in launches)
         # a graph launch costs a fixed ~9 us on the device whatever it holds (measured: the 20-step graph ran 8 % slower per step
-        # than the 1000-step one): for small K the timed graph holds `copies` back-to-back copies of the K steps
-        copies = max(1, -(-300 // K)) if a.mode == "graph" else 1
-        graph = lead = None
+        # than the 1000-step one): for small K the timed graph of the repetitions holds `copies` back-to-back copies of the K steps
+        copies = max(1, -(-300 // K)) if a.mode == "graph" and not one_pass else 1
+        # the timed steps as [(graph, replays)]: one pass replays graphs of at most GRAPH_LAUNCHES launches (capture stays short
+        # whatever K is), the repetitions one graph of all their launches
+        per_graph = min(n_launch, GRAPH_LAUNCHES) if one_pass else n_launch * copies
+        counts = [(per_graph, n_launch // per_graph)] + ([(n_launch % per_graph, 1)] if one_pass and n_launch % per_graph else [])
+        graphs, lead = [], None
         side = torch.cuda.Stream(dev)
         if a.mode == "graph":
             torch.cuda.synchronize(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
-            graph, lead = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            lead = torch.cuda.CUDAGraph()
             with torch.cuda.stream(side):
-                with torch.cuda.graph(graph, stream=side):
-                    for i in range(n_launch * copies):
-                        launch(i)
+                for n_in, reps in counts:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=side):
+                        for i in range(n_in):
+                            ret = launch(i)
+                    graphs.append((g, reps))
                 with torch.cuda.graph(lead, stream=side):
                     for i in range(n_lead):
                         launch(n_launch + i)
             torch.cuda.current_stream(dev).wait_stream(side)
-            # untimed: the first replay uploads the graph; keep replaying for ~50 ms so the timed
-            # repetitions run at the clocks a training loop sees, not at the idle-to-busy ramp
+            # untimed: the first replay uploads a graph; keep replaying for ~50 ms so that the timed steps run at the clocks a
+            # training loop sees, not at the idle-to-busy ramp.  One pass: then the envs are put back where they were, so that the
+            # timed steps start from the same state however many replays that took (--dump-outputs: the same bits run to run)
+            keep, obs_rows = (env.state_dict(), env._last_obs) if one_pass else (None, None)
             t_w = time.perf_counter()
             while True:
-                graph.replay()
+                for g, _ in graphs:
+                    g.replay()
                 torch.cuda.synchronize(dev)
                 if time.perf_counter() - t_w > 0.05:
                     break
+            if keep is not None:
+                env.load_state_dict(keep)
+                if obs_rows is not None:   # the rows the captured rollout_actor launches read their first observation from
+                    for o, k in zip([obs_rows] if isinstance(obs_rows, torch.Tensor) else obs_rows, keep["last_obs"]):
+                        o.copy_(k)
+                    env._last_obs = obs_rows
 
         def issue_lead():
             if lead is not None:
@@ -437,11 +498,14 @@ def main():
                     launch(n_launch + i)
 
         def issue_steps():
-            if graph is not None:
-                graph.replay()
+            nonlocal ret
+            if graphs:
+                for g, reps in graphs:
+                    for _ in range(reps):
+                        g.replay()
             else:
                 for i in range(n_launch):
-                    launch(i)
+                    ret = launch(i)
 
         dev_ms, wall_ms = [], []
         reps_min, reps_max, budget_ms = 20, 200, 50.0
@@ -458,6 +522,8 @@ def main():
             barrier() if timed else torch.cuda.synchronize(dev)
             wall_ms.append((time.perf_counter() - t0) * 1e3)
             dev_ms.append(ev0.elapsed_time(ev1) / copies)
+            if one_pass:
+                break
             done_reps = len(dev_ms)
             stop = done_reps >= reps_max or (done_reps >= reps_min and sum(dev_ms) * copies >= budget_ms)
             if dist is not None and timed:  # all ranks stop together (the barrier count must match)
@@ -466,8 +532,9 @@ def main():
                 stop = bool(flag.item())
             if stop:
                 break
+        outs = step_outputs(ret, env, H) if outputs else None   # before anything else steps the envs
         sustained = None
-        if sustain_s > 0 and graph is not None and ar:
+        if sustain_s > 0 and graphs and ar:
             per_replay_ms = float(np.median(dev_ms)) * copies
             n_rep = max(1, int(sustain_s * 1e3 / per_replay_ms))
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -475,7 +542,7 @@ def main():
             issue_lead()
             ev0.record()
             for _ in range(n_rep):
-                graph.replay()
+                issue_steps()
             ev1.record()
             torch.cuda.synchronize(dev)
             sustained = (ev0.elapsed_time(ev1) / (n_rep * copies), n_rep * copies * K)   # (ms per K steps, env-steps per env in the window)
@@ -486,13 +553,16 @@ def main():
         plan = env.launch_plan(H, actor=(w.actor if w.workload == "rollout_actor" else None))   # the launcher's own decision, this env's substeps
         if w.workload == "touch":
             plan = dict(plan, name=f"qr::touch_kernel<{_lib.KIND_ID[w.kind]},...>", block=64, launches=1)
-        return dev_ms, wall_ms, finite, done_rate, (plan, launch_rule), n_lead * H, copies, sustained
+        return dev_ms, wall_ms, finite, done_rate, (plan, launch_rule), n_lead * H, copies, sustained, outs
 
     from types import SimpleNamespace as NS
     head = NS(kind=a.kind, envs=N, env_offset=env_offset, substeps=a.substeps, workload=a.workload, horizon=a.horizon, steps=a.steps,
               slabs=a.action_batches, helper=a.helper, actor=a.actor, layout=a.layout)
-    sustain_s = a.sustain if (world == 1 and a.extras and a.workload == "step") else 0.0
-    dev_ms, wall_ms, finite, done_rate, kinfo, n_lead, copies, sustained = run(head, auto_reset, True, sustain_s)
+    sustain_s = a.sustain if (a.full and world == 1 and a.extras and a.workload == "step") else 0.0
+    dev_ms, wall_ms, finite, done_rate, kinfo, n_lead, copies, sustained, outs = run(head, auto_reset, True, sustain_s, one_pass=True,
+                                                                                     outputs=bool(a.dump_outputs))
+    if outs is not None:
+        dump_outputs(outs, a.dump_outputs, f"_rank{rank}" if world > 1 else "", DUMP_BYTES // world)
     reps = len(dev_ms)
     med_dev, med_wall = float(np.median(dev_ms)), float(np.median(wall_ms))
     tmax = torch.tensor([med_dev, med_wall], dtype=torch.float64, device=dev if on_dev else "cpu")
@@ -550,7 +620,7 @@ def main():
                          "profile_period_us": prof_us,
                          "frac_profile_clock": (round(algo * N * H / (prof_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if prof_us else None)},
         }
-        if n_gpus == 1 and a.extras and a.workload == "step":
+        if a.full and n_gpus == 1 and a.extras and a.workload == "step":
             t_extra = time.perf_counter()
 
             def us_per_launch(w, ar=True):
@@ -591,7 +661,7 @@ def main():
             if skipped:
                 cfg["rows_skipped"] = ",".join(skipped)[:118]
             cfg["extras_s"] = round(time.perf_counter() - t_extra, 2)
-        if n_gpus == 1 and a.cpu_seconds > 0:
+        if a.full and n_gpus == 1 and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(a.kind, a.cpu_seconds)
         line = json.dumps(out)
         assert len(line) <= MAX_LINE_BYTES, f"bench line is {len(line)} bytes (> {MAX_LINE_BYTES}): the driver's record would lose its tail"

@@ -548,6 +548,45 @@ def test_bench_presets_and_scaling_flags_without_gpu(monkeypatch):
     assert a.extras == 1 and a.extras_budget > 0 and a.actor == "ppo" and parse("--actor", "sac").actor == "sac" and 0 < a.sustain <= 10
 
 
+def test_bench_dump_outputs_without_gpu(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: what the last timed launch returned (a fused launch: its last env-step's rows) and the state after it,
+    as float32 / float64 .npy files; above the byte budget the same seeded env rows of every array; plain runs leave --full off."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    n = 1000
+
+    class Env:
+        def get_current_state(self):
+            return torch.arange(n * 18, dtype=torch.float64).reshape(n, 18)
+
+    rew = torch.arange(n, dtype=torch.float32)[:, None]
+    done = (torch.arange(n) % 7 == 0)[:, None]
+    o = bench.step_outputs((None, rew, done, torch.zeros(n, dtype=torch.bool), {}), Env(), 1)
+    assert sorted(o) == ["reward", "state", "terminated", "truncated"]
+    assert o["terminated"].dtype == np.float32 and o["terminated"].sum() == 143 and o["state"].dtype == np.float64
+    obs0, obs1 = torch.ones(n, 15), torch.zeros(n, 3)
+    assert sorted(bench.step_outputs(((obs0, obs1), rew, done, done[:, 0], {}), Env(), 1)) == ["obs0", "obs1", "reward", "state",
+                                                                                               "terminated", "truncated"]
+    ro = {"obs0": torch.arange(3 * n * 2, dtype=torch.float32).reshape(3, n, 2), "obs": None, "reward": torch.zeros(3, n, 1),
+          "action": torch.zeros(3, n, 4), "terminated": torch.zeros(3, n, 1, dtype=torch.bool)}
+    o = bench.step_outputs(ro, Env(), 3)
+    assert sorted(o) == ["action", "obs0", "reward", "state", "terminated"] and np.array_equal(o["obs0"], ro["obs0"][2].numpy())
+    bench.dump_outputs(o, str(tmp_path / "all"), "", 1 << 20)
+    assert np.array_equal(np.load(tmp_path / "all" / "state.npy"), o["state"])
+    budget = 100 * sum(v.nbytes // n for v in o.values())          # room for 100 of the 1000 env rows
+    for d in ("a", "b"):
+        bench.dump_outputs(o, str(tmp_path / d), "", budget)
+    s = np.load(tmp_path / "a" / "state.npy")
+    assert s.shape == (100, 18) and np.array_equal(s, np.load(tmp_path / "b" / "state.npy"))
+    rows = (s[:, 0] / 18).astype(int)                               # the same env rows in every file
+    assert np.all(np.diff(rows) > 0) and np.array_equal(np.load(tmp_path / "a" / "obs0.npy"), o["obs0"][rows])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= budget + 128 * len(o)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "")
+
+
 def test_bench_gpus_n_spawns_its_own_ranks_without_gpu(monkeypatch):
     """`bench.py --gpus 4` with no WORLD_SIZE: the ranks are started as child processes through torch.distributed.run
     (same arguments, 127.0.0.1 rendezvous) and the children's exit code is the caller's; under a launcher nothing is spawned."""
@@ -637,6 +676,32 @@ def test_bench_rollout_workloads(workload, kind, horizon, per_step_bytes):
     assert abs(d["roofline"]["avg_launch_us"] - d["ms_per_step"] * 1e3 * horizon) < 1e-9
     assert abs(d["value"] - 8192 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
     assert abs(d["roofline"]["achieved"] - per_step_bytes * 8192 / (d["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * d["roofline"]["achieved"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags,names", [
+    (["--steps", "2300"], ["reward", "state", "terminated", "truncated"]),
+    (["--steps", "96", "--workload", "rollout_actor", "--kind", "decoupled", "--horizon", "32", "--envs", "8192"],
+     ["action", "logprob", "obs0", "obs1", "reward", "state", "terminated", "truncated"])])
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs(tmp_path, flags, names):
+    """A plain bench.py run: ONE timed pass of exactly --steps env-steps (2300 = two 1000-launch graphs and a 300-launch one), the
+    headline and nothing else (no --full figures); --dump-outputs writes the last timed step's outputs, bit-identical from run to run."""
+    import json
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "5", "--dump-outputs", str(tmp_path / d)]
+                           + flags, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    for d in lines:
+        assert d["steps"] == int(flags[1]) and d["config"]["reps"] == 1 and d["ms_per_step"] > 0 and d["config"]["state_finite"]
+        assert "cpu_baseline" not in d and "sustained_us" not in d["config"] and d["roofline"]["noop_kernel_us"] is None
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "a")) == names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype in (np.float32, np.float64) and len(x) == lines[0]["config"]["envs_per_gpu"] and np.isfinite(x).all()
+        assert np.array_equal(x, y), n
+    assert np.load(tmp_path / "a" / "state.npy").shape[1] == 18
 
 
 @pytest.mark.gpu

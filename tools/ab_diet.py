@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of library builds on the VALU-bound launches (GPU box): for every build (QR_LIB) the configurations below are timed through
-bench.py's own harness (hipGraph, lead-in, >= 20 repetitions, HIP events, median), builds alternating A B A B so that clock drift
+bench.py's own headline harness (hipGraphs, lead-in, HIP events around exactly --steps env-steps), builds alternating A B A B so that clock drift
 shows up as spread, not as a difference.  Prints us per env-step of the whole batch.
 
     python tools/ab_diet.py build/ab/base.so build/ab/new.so [--reps 2] [--only rollout_quad,quad1Mx10,...] [--json out.json]

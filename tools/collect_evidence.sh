@@ -58,8 +58,8 @@ b rollout_actor_decoupled65536_T32 --workload rollout_actor --kind decoupled --h
 b rollout_coupled65536_T100 --workload rollout --kind coupled --horizon 100 --steps 1000
 b rollout_actor_coupled262144_T32 --workload rollout_actor --kind coupled --envs 262144 --horizon 32 --steps 320
 b config2 --config 2 ; b config3 --config 3 ; b config4 --config 4
-python3 bench.py > "$OUT/bench_full_line.json" 2>> "$OUT/bench.err"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_full_line_steps20.json" 2>> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench_full_line.json" 2>> "$OUT/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_full_line_steps20.json" 2>> "$OUT/bench.err"
 python3 tools/eager_cost.py > "$OUT/eager_cost.json" 2>> "$OUT/bench.err"
 b f64_quad65536 --layout f64 ; b f64_coupled65536 --layout f64 --kind coupled ; b f64_quad1M --layout f64 --envs 1048576 --action-batches 16 --steps 300
 python3 tools/noop_yardstick.py > "$OUT/noop_yardstick.json" 2> "$OUT/noop_yardstick.err"

@@ -10,7 +10,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# QR_LIB overrides the path for measurement builds (tools/microbench.py ablations) only.
+# QR_LIB overrides the path for measurement builds (the span build, tools/build_ab.sh A/B builds) only.
 LIB_PATH = os.environ.get("QR_LIB", os.path.join(_HERE, "libquadrotor_hip.so"))
 
 KIND_QUAD, KIND_COUPLED, KIND_DECOUPLED = 0, 1, 2

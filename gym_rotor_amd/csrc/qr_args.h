@@ -108,17 +108,13 @@ struct Args {
 // grids are bound by bytes and gain nothing (1 M envs: equal; Coupled 131 072 envs 9.2 -> 9.6-9.9 us), and a rollout has one
 // boundary per horizon and pays for the write-through instead (Quad-v0 65 536 envs, T = 100: 1.73 -> 1.91 us per env-step,
 // profiles/r03/ab_rollout_store_policy.txt): both keep plain stores.
-#ifndef QR_HELP_AUX
-#define QR_HELP_AUX 16   // one-step helper-wave instantiations (grids in the launch-latency regime)
-#endif
-#ifndef QR_PLAIN_AUX
-#define QR_PLAIN_AUX 0   // everything else
-#endif
+constexpr int kHelpAux = 16;   // one-step helper-wave instantiations (grids in the launch-latency regime)
+constexpr int kPlainAux = 0;   // everything else
 
 // A store of a caller-facing output (any address, per lane) with the cache policy AUX: 0 = a plain store; otherwise the SAME aux
 // bits the SoA buffer stores of the launch carry (SoA::store<AUX>), expressed the way the compiler offers them for flat global
 // stores — as the scope of a relaxed atomic store (gfx950 memory model: workgroup = sc0, agent = sc1, system = sc0 sc1):
-//   AUX 16 (sc1)      -> agent scope      (the product's write-through policy, QR_HELP_AUX)
+//   AUX 16 (sc1)      -> agent scope      (the product's write-through policy, kHelpAux)
 //   AUX 17 (sc0 sc1)  -> system scope
 //   AUX  1 (sc0)      -> workgroup scope
 // 16-byte stores have no atomic form: inline asm with the same bits.  The aux encoding and the sc0 / sc1 modifiers are gfx940+.
@@ -126,13 +122,9 @@ struct Args {
 #error "qr_args.h: the store cache policies (sc0 / sc1 aux bits) are written for gfx950 (Makefile: ARCH)"
 #endif
 typedef float f4_t __attribute__((ext_vector_type(4)));
-#ifndef QR_GSTORE_EXTRA_BITS
-#define QR_GSTORE_EXTRA_BITS 0  // measurement builds only: 1 = sc0 on top of the launch's bits for these stores (round 3 wrote them at system
-#endif                          // scope, sc0 sc1, whatever AUX said; profiles/r04/ab_gstore_scope.txt)
-template <int AUX_IN = 0, typename V>
+template <int AUX = 0, typename V>
 __device__ __forceinline__ void gstore(V* p, V v) {
-  static_assert(AUX_IN == 0 || AUX_IN == 16 || AUX_IN == 17 || AUX_IN == 1, "store policy: 0 (plain), 16 (sc1), 17 (sc0 sc1) or 1 (sc0)");
-  constexpr int AUX = AUX_IN == 0 ? 0 : (AUX_IN | QR_GSTORE_EXTRA_BITS);
+  static_assert(AUX == 0 || AUX == 16 || AUX == 17 || AUX == 1, "store policy: 0 (plain), 16 (sc1), 17 (sc0 sc1) or 1 (sc0)");
   constexpr int kScope = AUX == 16 ? __HIP_MEMORY_SCOPE_AGENT : AUX == 17 ? __HIP_MEMORY_SCOPE_SYSTEM : __HIP_MEMORY_SCOPE_WORKGROUP;
   if constexpr (AUX == 0) {
     *p = v;

@@ -163,7 +163,7 @@ __device__ __forceinline__ void sample_reset(Work<T, X>& w, const Draws& d, bool
 //
 // Only ~1 % of the envs reset in a given step, but more than half of the waves contain one and a
 // launch ends with its slowest wave, so the reset's instructions sit on the critical path of the
-// whole launch (measured with in-kernel clock stamps, tools/stamp_timeline.py).  Nothing about WHICH
+// whole launch (measured with in-kernel clock stamps, profiles/r02/stamps_quad65536_ar1.txt).  Nothing about WHICH
 // lane resets is known before the step has been integrated — but what a resetting lane needs
 // (Philox draws + the sampling arithmetic) does not depend on the lane at all if the stream is
 // keyed by the wave instead of by the env:

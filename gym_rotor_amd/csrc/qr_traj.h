@@ -250,7 +250,7 @@ struct SoA {
       return __builtin_bit_cast(E, __builtin_amdgcn_raw_buffer_load_b64(rsrc, lane * 8u, soff(f, first), 0));
     }
   }
-  template <int AUX = 0>  // cache policy (qr_args.h: QR_HELP_AUX)
+  template <int AUX = 0>  // cache policy (qr_args.h: kHelpAux)
   __device__ __forceinline__ void store(int f, unsigned first, unsigned lane, E v) const {
     if constexpr (sizeof(E) == 4) {
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), rsrc, lane * 4u, soff(f, first), AUX);

@@ -40,6 +40,8 @@
 //   qr_traj.h      goal generator (trajectory_generator.py modes 0/1/6), SoA buffer accessor
 //   qr_actor.h     PPO actor (MFMA / LDS forms), action sampling
 //   this file      step / rollout kernel, auxiliary kernels, host launchers and the C-ABI
+// Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
+// QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr below.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -50,10 +52,6 @@
 #include <type_traits>
 
 #include "quadrotor_hip.h"
-
-#ifndef QR_ABLATE
-#define QR_ABLATE 0  // 0 = product build; measurement-only builds (Makefile: evidence-libs): 1 = the kernel returns at once
-#endif               // (launch floor), 2 = loads and stores only (no integration)
 
 #include "qr_args.h"
 #include "qr_rng.h"
@@ -70,52 +68,11 @@ static_assert(alignof(Args) == 8, "Args follows the leading scalar arguments wit
 static_assert(sizeof(Coeffs) <= 5 * 64 && offsetof(Args, c) + sizeof(Coeffs) == sizeof(Args), "the step kernel touches the five kernarg lines of the coefficient block (the last field of Args)");
 #endif
 
-// QR_STAMPS: diagnostic build (tools/stamp_timeline.py).  Every wave records the 100 MHz real-time clock at
-// seven points of the step; the values go to a buffer of their own that nothing else reads.
-#ifdef QR_STAMPS
-__device__ unsigned long long* g_stamps = nullptr;
-#define QR_STAMP(k, dep)                                                                          \
-  do {                                                                                            \
-    unsigned long long t_;                                                                        \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep) : "memory");    \
-    if (g_stamps != nullptr && lane == 0) g_stamps[(size_t)blockIdx.x * 8 + (k)] = t_;            \
-  } while (0)
-// the helper wave's stamps: rows gridDim.x .. 2 gridDim.x - 1 of the same buffer
-#define QR_HSTAMP(k, dep)                                                                         \
-  do {                                                                                            \
-    unsigned long long t_;                                                                        \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep) : "memory");    \
-    if (g_stamps != nullptr && threadIdx.x == 64) g_stamps[((size_t)gridDim.x + blockIdx.x) * 8 + (k)] = t_; \
-  } while (0)
-// the multi-step launches (tools/phase_timeline.py): row (tile * n_steps + t) of the buffer, stamp k of step t
-#define QR_PSTAMP(k, dep)                                                                         \
-  do {                                                                                            \
-    unsigned long long t_;                                                                        \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep) : "memory");    \
-    if (g_stamps != nullptr && lane == 0) g_stamps[((size_t)blockIdx.x * n_steps + t) * 8 + (k)] = t_; \
-  } while (0)
-// where the hardware put each wave (tools/wave_placement.py): HW_ID | XCC_ID << 32, row blockIdx.x, column = wave of the workgroup
-__device__ unsigned long long* g_hwid = nullptr;
-#define QR_HWID()                                                                                 \
-  do {                                                                                            \
-    unsigned h_, x_;                                                                              \
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(h_));                              \
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x_));                             \
-    if (g_hwid != nullptr && (threadIdx.x & 63u) == 0)                                            \
-      g_hwid[(size_t)blockIdx.x * 2 + (threadIdx.x >> 6)] = (unsigned long long)h_ | ((unsigned long long)x_ << 32); \
-  } while (0)
-#else
-#define QR_STAMP(k, dep) do { } while (0)
-#define QR_HSTAMP(k, dep) do { } while (0)
-#define QR_PSTAMP(k, dep) do { } while (0)
-#define QR_HWID() do { } while (0)
-#endif
-
 // QR_SPAN: the light diagnostic build (tools/span_timeline.py).  Every wave records the 100 MHz real-time clock twice — with its first
 // instruction and behind its last — into row `span_slot` of a buffer of its own; a chain of launches with slots 0, 1, 2, ... then
 // shows, on the device's own clock, each launch's SPAN (first wave in to last wave out) and the GAP to the next launch.  Two scalar
 // memory-time reads per wave and one 16-byte store at the very end: the build runs within a few per cent of the product's period
-// (the seven-stamp QR_STAMPS build: +50 %), which is what makes span + gap a usable clock for kernels rocprofv3 inflates.
+// (the retired seven-stamp build: +50 %), which is what makes span + gap a usable clock for kernels rocprofv3 inflates.
 #ifdef QR_SPAN
 static unsigned long long* g_span_buf = nullptr;  // (host) the stamp buffer and the row the next launches write: qr_debug_set_span[_slot]
 static int g_span_slot = -1;
@@ -149,70 +106,41 @@ static int g_span_slot = -1;
 #define QR_SPAN_END() do { } while (0)
 #endif
 
-#ifndef QR_STEP_PRIO
-#define QR_STEP_PRIO 3  // s_setprio of the stepping wave in the helper-wave launches (0: the A/B arm without it)
-#endif
-#ifndef QR_HELP_REWARD_TILES
-#define QR_HELP_REWARD_TILES 1408  // one-step Quad-v0 helper launches beyond this many tiles form the reward on the stepping wave
-#endif
-#ifndef QR_HELP_ROWS_TILES
-#define QR_HELP_ROWS_TILES 1600  // one-step wrapper helper launches beyond this many tiles store their rows from the stepping wave
-#endif
-#ifndef QR_PRIO_SUBSTEPS
-#define QR_PRIO_SUBSTEPS 2
-#endif
-#ifndef QR_HELPER_GRID_WRAP_SUBSTEPS
-#define QR_HELPER_GRID_WRAP_SUBSTEPS 1664  // the wrappers' one-step helper-wave launches with two or more substeps: up to this many tiles (wants_helper)
-#endif
-#ifndef QR_PRIO_SINGLE_TILES
-#define QR_PRIO_SINGLE_TILES 768
-#endif
-#ifndef QR_DELTA_STAGES
-#define QR_DELTA_STAGES 1  // 0: the rate-adaptive instantiations use the plain stage arithmetic (numerics: tools/numerics_delta.py and the free-run rows of
-                           // profiles/r03/parity_summary.txt, 6.8e-6 -> 2.4e-6; cost: the "free run in regime" rows of profiles/r03/runtime_ab.json, 4.39 against 4.03 us)
-#endif
-#ifndef QR_EARLY_STORE_GRID
-#define QR_EARLY_STORE_GRID 4096  // grids up to this many waves store a resetting wave's settled lanes before it samples (65 536 envs 5.43 / 5.49 us, 1 M 39.4 / 37.4)
-#endif
-#ifndef QR_HELP_POLICY
-#define QR_HELP_POLICY 1  // 0: no helper wave in qr_rollout_actor (Coupled 65 536 envs, T = 32: 5.37 -> 4.51 us per env-step)
-#endif
-#ifndef QR_HELP_REWARD
-#define QR_HELP_REWARD 1        // the helper wave forms Quad-v0's reward (§3.3 item 2; evidence build q_norew: profiles/r03/ab_quad_builds.txt)
-#endif
+constexpr int kStepPrio = 3;                  // s_setprio of the stepping wave in the helper-wave launches
+constexpr unsigned kHelpRewardTiles = 1408;   // one-step Quad-v0 helper launches beyond this many tiles form the reward on the stepping wave
+constexpr unsigned kHelpRowsTiles = 1600;     // one-step wrapper helper launches beyond this many tiles store their rows from the stepping wave
+constexpr int kPrioSubsteps = 2;
+constexpr unsigned kHelperGridWrapSubsteps = 1664;  // the wrappers' one-step helper-wave launches with two or more substeps: up to this many tiles (wants_helper)
+constexpr unsigned kPrioSingleTiles = 768;
+constexpr int kEarlyStoreGrid = 4096;  // grids up to this many waves store a resetting wave's settled lanes before it samples (65 536 envs 5.43 / 5.49 us, 1 M 39.4 / 37.4)
 // (Settled A/Bs whose losing arms are gone from the tree — the winning arm is the code, the measurement is cited where it applies:
 //  kernarg lines requested with the wave's first instructions (Decoupled 5.16 -> 5.02 us), output pointers read with the first scalar
 //  batch in the plain launches (1 M envs 34.7 -> 33.9 us), rows to the LDS tile before the reset block + late goal / integrator loads
 //  in the plain wrapper launches (262 144 envs 19.1 -> 16.5 us), role constants formed in the reset block of one-step launches
 //  (142 -> 128 VGPRs), observation rows carried out by the helper wave, per-episode action-map constants in the rollouts
-//  (profiles/r04/ab_hoist_act.txt).  DESIGN.md / docs/EXPERIMENTS.md name the files.)
-#ifndef QR_XCD_GRID
-#define QR_XCD_GRID 1536   // one-step helper-wave launches up to this many tiles give every XCD a contiguous range of tiles (see tile_id); 0 = never
-#endif
-#ifndef QR_HELPER_GRID
+//  (profiles/r04/ab_hoist_act.txt), Quad-v0's reward formed by the helper wave (§3.3 item 2; profiles/r03/ab_quad_builds.txt, q_norew),
+//  a helper wave in qr_rollout_actor (§3.3 item 5: Coupled 65 536 envs, T = 32: 5.37 -> 4.51 us per env-step), the delta-form stages
+//  of the rate-adaptive launches (numerics: tools/numerics_delta.py and the free-run rows of profiles/r03/parity_summary.txt, 6.8e-6
+//  -> 2.4e-6; cost: the "free run in regime" rows of profiles/r03/runtime_ab.json, 4.39 against 4.03 us).  DESIGN.md /
+//  docs/EXPERIMENTS.md name the files.)
+constexpr unsigned kXcdGrid = 1536;  // one-step helper-wave launches up to this many tiles give every XCD a contiguous range of tiles (see tile_id)
 // Grids up to this many tiles run the one-step kernel with a helper wave per tile (HELP).  The limit is an EMPIRICAL crossover,
 // not a residency rule: 2560 tiles are 5120 waves, more than the 4096 wave slots the 120-VGPR kernel has at four waves per SIMD —
 // the helper waves are short-lived and the launch still wins there (profiles/r03/ab_helper_thresholds.txt, with the write-through
 // stores of DESIGN.md 3.5: Quad-v0 163 840 envs 7.3 against 8.3 us plain, 196 608 equal, 262 144 10.3 against 9.9).  Round 5, with
-// the reward on the stepping wave beyond QR_HELP_REWARD_TILES (one substep): 196 608 envs 8.0-8.2 against 8.8-8.9 plain, 229 376
+// the reward on the stepping wave beyond kHelpRewardTiles (one substep): 196 608 envs 8.0-8.2 against 8.8-8.9 plain, 229 376
 // 8.6-9.2 against 9.7-9.8, 245 760 9.1-9.9 against 9.9-10.1, 262 144 9.8-10.6 against 10.1-10.3 (profiles/r05/ab_step_prio.txt):
 // 3328 tiles for one substep; launches with more substeps keep 2560.  The environment variable QR_HELPER_GRID and the
 // QR_FLAG_*_HELPER bits override it (see `tuning`).
-#define QR_HELPER_GRID 3328
-#endif
-#ifndef QR_HELPER_GRID_SUBSTEPS
-#define QR_HELPER_GRID_SUBSTEPS 2560  // Quad-v0 with >= 2 substeps or the fused goal generator (its own guard: a build may set QR_HELPER_GRID alone)
-#endif
-#ifndef QR_HELPER_GRID_ROLLOUT
-#define QR_HELPER_GRID_ROLLOUT (QR_HELPER_GRID < 1024 ? QR_HELPER_GRID : 1024)  // qr_rollout / qr_rollout_actor (two waves per SIMD)
-#endif
-#ifndef QR_HELPER_GRID_WRAP
-#define QR_HELPER_GRID_WRAP (QR_HELPER_GRID < 2560 ? QR_HELPER_GRID : 2560)  // the wrappers: ahead of the plain launch up to 262 144 envs while the action rows come
+constexpr unsigned kHelperGrid = 3328;
+constexpr unsigned kHelperGridSubsteps = 2560;  // Quad-v0 with >= 2 substeps or the fused goal generator
+constexpr unsigned kHelperGridRollout = 1024;   // qr_rollout / qr_rollout_actor (two waves per SIMD)
+// The wrappers: ahead of the plain launch up to 262 144 envs while the action rows come
 // from cache (r03/ab_helper_thresholds.txt, 8 slabs: 14.9 against 15.7 us), behind it beyond 131 072 envs when they stream from HBM (r03/ab_helper_wave.txt, 64 slabs:
 // 131 072 envs 9.4 against 9.1 us, 262 144 envs 18.4 against 16.5 — three stepping waves per SIMD hide less latency than four).  Round 5, with the rows on
-// the stepping wave beyond QR_HELP_ROWS_TILES: ahead up to 163 840 envs with either action source (10.2-10.4 against 10.5-10.7), mixed at 196 608: 2560 tiles
-// (one substep; 1664 with more: QR_HELPER_GRID_WRAP_SUBSTEPS; 2048 with the fused goal generator)
-#endif
+// the stepping wave beyond kHelpRowsTiles: ahead up to 163 840 envs with either action source (10.2-10.4 against 10.5-10.7), mixed at 196 608: 2560 tiles
+// (one substep; 1664 with more: kHelperGridWrapSubsteps; 2048 with the fused goal generator)
+constexpr unsigned kHelperGridWrap = 2560;
 // ------------------------------------------------------------------------------------
 // Quad-v0 reward and termination (quad.py:274-318) from the post-step state
 // ------------------------------------------------------------------------------------
@@ -322,13 +250,13 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   using X = XV;  // and so are x, v
   using KT = KindTraits<KIND>;
   constexpr int A = KT::A, D0 = KT::D0, D1 = KT::D1 ? KT::D1 : 1, NAG = KT::NAG;
-  constexpr int AUX = (HELP && SINGLE) ? QR_HELP_AUX : QR_PLAIN_AUX;  // cache policy of every store of this launch (qr_args.h)
+  constexpr int AUX = (HELP && SINGLE) ? kHelpAux : kPlainAux;  // cache policy of every store of this launch (qr_args.h)
   __shared__ __attribute__((aligned(16))) float smem[B * (D0 > A ? D0 : A)];
   const int tid = threadIdx.x;
   const unsigned lane = threadIdx.x;
   // XCD-aware tile map.  Workgroups are dealt round-robin over the 8 XCDs (workgroup b runs on XCD b % 8).  With tile = blockIdx.x
   // an XCD therefore touches every EIGHTH 256- / 512-byte segment of each SoA field — its requests alias onto a few of its L2's
-  // channels.  For the grids whose working set is cache-resident (the one-step helper-wave launches up to QR_XCD_GRID tiles) every XCD
+  // channels.  For the grids whose working set is cache-resident (the one-step helper-wave launches up to kXcdGrid tiles) every XCD
   // gets a CONTIGUOUS range of tiles instead (a bijection for any tile count: XCD x owns q + (x < r) tiles, q = tiles / 8, r = tiles % 8):
   // 16 384 ... 81 920 envs 0.5-4 % faster for all three kinds (Quad-v0 65 536: 4.15 -> 4.07 us, Coupled 5.34 -> 5.18, Decoupled 5.17 ->
   // 4.98; profiles/r05/ab_xcd_map.txt), nothing at <= 8192 envs.  Larger grids stream from HBM, where the default deal keeps the eight
@@ -337,7 +265,7 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   unsigned tile_id = blockIdx.x;
   if constexpr (HELP && SINGLE) {
     const unsigned n_tiles = ((unsigned)n_envs + 63u) >> 6;
-    if (n_tiles <= (unsigned)QR_XCD_GRID) {
+    if (n_tiles <= kXcdGrid) {
       const unsigned xcd = blockIdx.x & 7u, q8 = n_tiles >> 3, r8 = n_tiles & 7u;
       tile_id = xcd * q8 + (xcd < r8 ? xcd : r8) + (blockIdx.x >> 3);
     }
@@ -346,7 +274,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   const unsigned ufirst = tile_id * (unsigned)B;
   const int64_t first = (int64_t)ufirst;
   const int64_t i = first + tid;
-  QR_HWID();
   const int64_t N = a.n, L = a.ld;
   const int rows = min(n_envs - (int)ufirst, B);   // (n_envs < 2^31: checked on the host)
   const bool active = tid < rows;
@@ -355,9 +282,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   // (Measured and NOT adopted, profiles/r03/ab_dev_coeffs.txt: the coefficient block in a device-resident global instead of
   // the kernarg segment — 4.63 against 4.16 us per launch at 65 536 envs.)
   const Coeffs& c = ka.c;
-#if QR_ABLATE == 1  // measurement build: launch floor only
-  return;
-#endif
   static_assert(!HELP || B == 64, "the helper wave belongs to the one-wave-per-tile kernels");
   // (a rollout alternates between two pools: the helper samples step t+1's while the stepping wave takes from step t's)
   __shared__ typename std::conditional<HELP, PoolLds<T>, char>::type pool_lds[(SINGLE || POLICY) ? 1 : 2];  // (unused without HELP: dropped)
@@ -365,10 +289,10 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   __shared__ __attribute__((aligned(16))) float eps_lds[HELP && POLICY ? 2 * 64 * 8 : 4];
   // Quad-v0's reward (an atan2, a sqrt: ~90 instructions) is formed by the helper wave as well
   // (HREW = false: the one-step Quad-v0 launch on grids where some SIMDs hold a second stepping wave — launch_kind)
-  constexpr bool kHelpReward = HELP && !POLICY && !TRAJ && KIND == QR_KIND_QUAD && QR_HELP_REWARD && HREW;  // (TRAJ: the goal lives in the stepping wave's registers)
+  constexpr bool kHelpReward = HELP && !POLICY && !TRAJ && KIND == QR_KIND_QUAD && HREW;  // (TRAJ: the goal lives in the stepping wave's registers)
   __shared__ typename std::conditional<kHelpReward, PostLds<T, X>, char>::type post_lds[SINGLE ? 1 : 2];  // (a rollout alternates)
   __shared__ PoolLds<T> own_pool;  // pools this wave samples itself (no helper; or a tile's 13th.. resetting lane)
-  // (HREW = false for a wrapper: the rows stay with the stepping wave — one-step grids beyond QR_HELP_ROWS_TILES tiles, launch_kind)
+  // (HREW = false for a wrapper: the rows stay with the stepping wave — one-step grids beyond kHelpRowsTiles tiles, launch_kind)
   constexpr bool kHelpRows = HELP && SINGLE && (KIND == QR_KIND_QUAD || HREW);
   // (plain one-step wrapper kernels: large grids) the observation rows go to their LDS tile as soon as they are formed,
   // BEFORE the reset block, and a re-sampled env overwrites its row there: the 18-23 row registers need not survive the
@@ -387,7 +311,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     // (the wave's first lane decides: a wave-uniform branch in the compiler's eyes too — on threadIdx.x itself everything
     // after it counts as divergent control flow, and scalar offsets of the loads below were re-derived per lane)
     if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= B) {  // ---- the helper wavefront: pass 0 of the tile's reset pool -> LDS ----  //@sec helper-wave
-      QR_HSTAMP(0, threadIdx.x);
       float hgoal[12];
 #pragma unroll
       for (int f = 0; f < 12; ++f) hgoal[f] = f == 6 ? 1.0f : 0.0f;  // hover default (quad.py:98-101)
@@ -410,8 +333,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       const uint32_t hflags = ka.flags;
       const uint64_t hseed = ka.seed;
       const uint64_t hgfirst = (uint64_t)(ka.env_offset + first);
-      QR_HSTAMP(5, (float)hflags + (float)hseed + (float)hgfirst);   // (diagnostic builds) kernarg scalars back
-      QR_HSTAMP(6, (float)rc);                                       // the tile counter (global memory) back
       // (Measured and NOT adopted, profiles/r03/ab_helper_touch.txt: requesting this wave's kernarg lines with dummy loads in its
       // first instructions, like the stepping wave does — 4.148 against 4.151 us per launch; the pool is in LDS ~0.7 us before
       // the stepping wave asks for it either way.)
@@ -504,14 +425,10 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
         QR_SPAN_END();
         return;
       }
-      QR_HSTAMP(1, hrole.off[0] + (float)rc);
       make_pool<T>(hp, hrole, hseed, hgfirst, rc, 0);
       pool_to_lds(pool_lds[0], hp);
-      QR_HSTAMP(2, hp.v[0] + (float)hp.q[0]);
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      QR_HSTAMP(3, threadIdx.x);
-      if constexpr (kHelpReward) help_reward(0);
-      QR_HSTAMP(4, threadIdx.x);  // ---- then the reward of the step, from the post-step state the stepping wave left in LDS ----
+      if constexpr (kHelpReward) help_reward(0);  // ---- then the reward of the step, from the post-step state the stepping wave left in LDS ----
       if constexpr (kHelpRows) {  // ---- and the observation rows: the stepping wave leaves the tile in LDS, this wave carries it out ----
         if (KIND != QR_KIND_QUAD || hob0 != nullptr) {
           asm volatile("s_barrier" ::: "memory");
@@ -531,11 +448,11 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   // One-step launches: the helper's pool is wanted within the same microsecond and its reward / rows trail the launch, so only
   // up to the pool barrier and only on grids of at most 768 tiles (32 768 envs: wrappers -3.7 %, Quad-v0 -1.5 %; 65 536 envs
   // +0.3...3 %, 98 304 +9 % with it).  Changes no result.  profiles/r05/ab_step_prio.txt
-  if constexpr (HELP && !SINGLE) __builtin_amdgcn_s_setprio(QR_STEP_PRIO);
+  if constexpr (HELP && !SINGLE) __builtin_amdgcn_s_setprio(kStepPrio);
   if constexpr (HELP && SINGLE) {
-    if ((((unsigned)n_envs + 63u) >> 6) <= (unsigned)QR_PRIO_SINGLE_TILES) __builtin_amdgcn_s_setprio(QR_STEP_PRIO);
+    if ((((unsigned)n_envs + 63u) >> 6) <= kPrioSingleTiles) __builtin_amdgcn_s_setprio(kStepPrio);
   }
-  QR_STAMP(0, tid);  //@sec prologue-loads
+  //@sec prologue-loads
 #if defined(__HIP_DEVICE_COMPILE__)
   // The coefficient block spans five 64-byte lines of the kernarg segment (host-visible memory: ~0.5 us per miss).  The
   // compiler reads coefficients where they are used, i.e. it requests those lines only AFTER the first batch of scalar
@@ -626,7 +543,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   // same wave right after issuing its loads — 5.86-5.92 against 5.28 us per launch at 65 536 envs: the pool's inputs arrive only
   // ~0.5 us after the wave's first instruction, so most of its ~0.6 us does not hide under the loads and EVERY wave pays it.)
   ResetPool<T> pool;
-  QR_STAMP(1, 0.0f);
 
   Traj tr;
   const int goal_mode = TRAJ ? ka.goal_mode : QR_GOAL_EXTERNAL;  // wave-uniform
@@ -651,7 +567,7 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   bool stored_early = false;  // (SINGLE) this lane's state went out before its wave sampled a reset pool
   // (n_envs: a preloaded SGPR — gridDim.x would be a scalar load.  With a helper wave the reset block is six LDS reads:
   // nothing to overlap.)
-  const bool early_store = SINGLE && !HELP && n_envs <= QR_EARLY_STORE_GRID * 64;
+  const bool early_store = SINGLE && !HELP && n_envs <= kEarlyStoreGrid * 64;
   QuatPack<T> qp;             // attitude in its storage form, formed once per env-step
   qp.k[0] = qp.k[1] = qp.k[2] = T(0);
 
@@ -690,7 +606,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
 
   for (int t = 0; t < n_steps; ++t) {  //@sec action-source
     float act[A];
-    if constexpr (!SINGLE) QR_PSTAMP(0, tid);
     if constexpr (POLICY) {
       float pre[A], ls[A], eps[A], logp[A];
       // the wave's observation rows -> LDS tile [lane][D0] (B operands of the first layer)
@@ -718,8 +633,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       }
 #pragma unroll
       for (int j = 0; j < A; ++j) eps[j] = 0.0f;
-      if constexpr (!SINGLE) QR_PSTAMP(1, pre[0] + pre[A - 1]);   // actor heads done
-      if constexpr (!SINGLE) QR_PSTAMP(2, tid);                   // past the noise barrier
       if (!ka.deterministic) {
         if (ka.noise != nullptr) {  // injected draws [T][N][A]
           if (active) {
@@ -767,19 +680,11 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       if (t + 1 < n_steps) load_action(t + 1, act_next);
     }
 
-#if QR_ABLATE == 2  // measurement build: memory traffic only (no integration)
-    w.x[0] += X(act[0]);
-    pack_quat(w.q, qp);
-    uint8_t* const done_ptr = ka.done;
-    uint8_t* const trunc_ptr = ka.truncated;
-#else
     // ---- goal for this step from the pre-step state (main.py:145-147) ----  //@sec traj-goal
     if constexpr (TRAJ) {
       float b1d_dot[3];
       traj_goal<kStateful>(w, tr, goal_mode, c, b1d_dot);
     }
-    QR_STAMP(2, (float)w.q[0] + (float)w.x[0] + act[0] + w.prm[0] + (float)w.W[2]);
-    if constexpr (!SINGLE) QR_PSTAMP(3, act[0] + act[A - 1]);     // action sampled (policy) / loaded
     // ---- action_wrapper ----  //@sec action-map
     Dyn<T> dyn;
     if constexpr (!kHoistAct) act_consts(w, c, ac);
@@ -808,7 +713,7 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       // (kDelta) The launches that step envs on without in-launch resets — the only ones in which an env can leave the
       // regime — form the quaternion stages in delta form (qr_dynamics.h: integrate_delta): their free run lands on RK4's
       // truncation floor instead of 7x above it.  qr_rollout_actor keeps the plain stages (its kernel is at its register limit).
-      constexpr bool kDelta = QR_DELTA_STAGES && !POLICY;
+      constexpr bool kDelta = !POLICY;
       const T wmax = fmax(fmax(fabs(w.W[0]), fabs(w.W[1])), fabs(w.W[2]));
       const T need = wmax * T(c.inv_w_adapt);
       if constexpr (kDelta) {
@@ -834,7 +739,7 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       //  Quad-v0 131 072 envs x 10 substeps 9.66 -> 9.21 us, x 4: 7.04 -> 6.67, x 2: 5.97 -> 5.78; with ONE substep it loses
       //  at 65 536 envs (+1.2 %) and is left out: profiles/r05/ab_step_prio.txt)
       if constexpr (HELP && SINGLE) {
-        if (nsub >= QR_PRIO_SUBSTEPS) __builtin_amdgcn_s_setprio(QR_STEP_PRIO);
+        if (nsub >= kPrioSubsteps) __builtin_amdgcn_s_setprio(kStepPrio);
       }
       integrate_sel<MAG>(w.x, w.v, w.q, w.W, dyn, nsub, T(c.dt) * recip(T(nsub)));
     }
@@ -852,9 +757,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     // The attitude as it is stored (qr_traj.h: QuatPack) is formed once per env-step: here when this wave may store
     // its settled lanes early (below), otherwise after the reset block, when every lane holds what it will store.
     if (early_store) pack_quat(w.q, qp);
-    QR_STAMP(3, (float)w.q[0] + (float)w.x[0] + (float)w.v[2] + (float)w.W[0]);
-    if constexpr (!SINGLE) QR_PSTAMP(4, (float)w.q[0] + (float)w.x[0] + (float)w.v[2] + (float)w.W[0]);   // integrated
-#endif
 
     // ---- obs / reward / done ----  //@sec obs-reward-done
     T R[9];
@@ -908,8 +810,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     for (int g = 0; g < NAG; ++g)
       if (dn[g]) rwd[g] = -1.0f;
 
-    QR_STAMP(4, rwd[0] + (dn[0] ? 1.0f : 0.0f));
-    if constexpr (!SINGLE) QR_PSTAMP(5, rwd[0] + (dn[0] ? 1.0f : 0.0f));   // observation, reward, done formed
     // ---- time limit + auto-reset ----  //@sec reward-done-stores
     steps += 1;
     const bool trunc = ka.max_episode_steps > 0 && steps >= ka.max_episode_steps;
@@ -939,7 +839,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     else if constexpr (HELP && !kHelpReward) asm volatile("s_barrier" ::: "memory");
     if constexpr (HELP && !kHelpReward && SINGLE) __builtin_amdgcn_s_setprio(0);
     const unsigned long long rmask = __ballot(need_reset);
-    if constexpr (!SINGLE) QR_PSTAMP(6, tid);                     // stores issued, past the pool barrier
     if (rmask) {  // wave-uniform: skipped unless some lane of this wave starts a new episode  //@sec reset-block
       if (early_store) {
         // This wave is about to spend ~0.5 us sampling episode starts.  The state of its lanes that do NOT
@@ -1045,10 +944,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       if constexpr (kHoistAct) act_consts(w, c, ac);  // (some lane of the wave holds new parameters: every lane re-forms — the same values for the others)
     }
     if (!early_store) pack_quat(w.q, qp);  //@sec pack-quat
-    QR_STAMP(5, (float)w.q[0] + (float)w.x[0] + w.prm[0]);
-#ifdef QR_STAMPS
-    if (g_stamps != nullptr && lane == 0) g_stamps[(size_t)blockIdx.x * 8 + 7] = rmask;
-#endif
 
     // ---- outputs of step t ----  //@sec obs-rows-out
     if constexpr (kHelpRows) {  // rows -> LDS tile(s); the helper wave stores them
@@ -1099,7 +994,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       for (int j = 0; j < D1; ++j) po1[j] = o1[j];
     }
     if constexpr (!SINGLE) unpack_quat(qp, w.q);  //@sec unpack-quat  // the next env-step starts from what a single-step launch would have re-loaded
-    if constexpr (!SINGLE) QR_PSTAMP(7, (float)w.q[0] + (rmask ? 1.0f : 0.0f));   // reset block, pack, rows handed over, unpack
   }
 
   if constexpr ((HELP && POLICY != 0) || kRollRows) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the last step's tile: see the helper wave
@@ -1138,7 +1032,6 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   } else if (auto_reset && lane == 0) {
     a.reset_count[tile_id] = (int32_t)(rcount_s + (uint32_t)n_steps);  // never reuse a (tile, counter)
   }
-  QR_STAMP(6, tid);
   QR_SPAN_END();
 }
 
@@ -1555,7 +1448,7 @@ static int fill_env(Args& a, const QrEnv* e) {
 static inline int pick_block(int64_t) { return 64; }
 
 // The launch rule's thresholds.  The compiled-in defaults are crossovers measured on the pool's MI355X boxes (the comments at
-// QR_HELPER_GRID*); boxes differ by 7-10 % in what they stream, and the wrappers' crossover moves with where the action rows come
+// kHelperGrid*); boxes differ by 7-10 % in what they stream, and the wrappers' crossover moves with where the action rows come
 // from, so every threshold can be overridden per process — environment variables of the same names, read once — and per env
 // through QrEnv.flags (QR_FLAG_FORCE_HELPER / QR_FLAG_NO_HELPER: what QuadVecEnv(autotune=True) sets after timing both
 // instantiations for ITS kind, size, box and action source).  No choice changes a result bit
@@ -1573,9 +1466,9 @@ static unsigned env_uint(const char* name, unsigned dflt) {
 static const Tuning& tuning() {
   static const Tuning t = [] {
     Tuning x;
-    x.helper_grid = env_uint("QR_HELPER_GRID", QR_HELPER_GRID);
-    x.helper_grid_wrap = env_uint("QR_HELPER_GRID_WRAP", x.helper_grid < (unsigned)QR_HELPER_GRID_WRAP ? x.helper_grid : (unsigned)QR_HELPER_GRID_WRAP);
-    x.helper_grid_rollout = env_uint("QR_HELPER_GRID_ROLLOUT", x.helper_grid < (unsigned)QR_HELPER_GRID_ROLLOUT ? x.helper_grid : (unsigned)QR_HELPER_GRID_ROLLOUT);
+    x.helper_grid = env_uint("QR_HELPER_GRID", kHelperGrid);
+    x.helper_grid_wrap = env_uint("QR_HELPER_GRID_WRAP", x.helper_grid < kHelperGridWrap ? x.helper_grid : kHelperGridWrap);
+    x.helper_grid_rollout = env_uint("QR_HELPER_GRID_ROLLOUT", x.helper_grid < kHelperGridRollout ? x.helper_grid : kHelperGridRollout);
     return x;
   }();
   return t;
@@ -1600,11 +1493,11 @@ static inline bool wants_helper(const Args& a, int kind, int layout, unsigned ti
   // and a helper wave per tile are all resident only up to 1024 tiles; beyond, measured: Quad-v0 98 304 envs 3.52 against
   // 2.97 us per env-step plain, Coupled 5.06 against 3.74)
   const Tuning& tn = tuning();
-  const unsigned quad_limit = a.substeps <= 1 || tn.helper_grid < (unsigned)QR_HELPER_GRID_SUBSTEPS ? tn.helper_grid : (unsigned)QR_HELPER_GRID_SUBSTEPS;
+  const unsigned quad_limit = a.substeps <= 1 || tn.helper_grid < kHelperGridSubsteps ? tn.helper_grid : kHelperGridSubsteps;
   // (2560 measured with one substep only.  Several substeps — since round 6 the Magnus substep — re-measured, profiles/r06/
   //  ab_magnus_helper_sweep.txt: the wrappers' helper launch is ahead up to 1664 tiles (x 2 / x 4: -6...7 %), level at 1792, behind
-  //  from 1920 on (2048 tiles: +5...15 %); Quad-v0 keeps QR_HELPER_GRID_SUBSTEPS = 2560.)
-  const unsigned wrap_limit = a.substeps <= 1 || tn.helper_grid_wrap < (unsigned)QR_HELPER_GRID_WRAP_SUBSTEPS ? tn.helper_grid_wrap : (unsigned)QR_HELPER_GRID_WRAP_SUBSTEPS;
+  //  from 1920 on (2048 tiles: +5...15 %); Quad-v0 keeps kHelperGridSubsteps = 2560.)
+  const unsigned wrap_limit = a.substeps <= 1 || tn.helper_grid_wrap < kHelperGridWrapSubsteps ? tn.helper_grid_wrap : kHelperGridWrapSubsteps;
   const unsigned limit = a.n_steps > 1 ? tn.helper_grid_rollout : (kind == QR_KIND_QUAD ? quad_limit : wrap_limit);
   return layout == QR_LAYOUT_MIXED && a.act_out == nullptr && a.goal_mode == QR_GOAL_EXTERNAL && !wants_adapt(a) &&
          (a.flags & QR_FLAG_AUTO_RESET) && helper_choice(a, tiles, limit);
@@ -1613,9 +1506,9 @@ static inline bool wants_helper(const Args& a, int kind, int layout, unsigned ti
 static inline bool wants_helper_traj(const Args& a, int kind) {  // the same with the fused goal generator (one-step launches)
   const unsigned tiles = (unsigned)((a.n + 63) / 64);
   const Tuning& tn = tuning();
-  const unsigned wrap_traj = a.substeps <= 1 ? 2048u : (unsigned)QR_HELPER_GRID_WRAP_SUBSTEPS;
+  const unsigned wrap_traj = a.substeps <= 1 ? 2048u : kHelperGridWrapSubsteps;
   return a.act_out == nullptr && a.goal_mode != QR_GOAL_EXTERNAL && a.goal_mode < QR_GOAL_MODE2 && !wants_adapt(a) && (a.flags & QR_FLAG_AUTO_RESET) &&
-         helper_choice(a, tiles, kind == QR_KIND_QUAD ? (tn.helper_grid < (unsigned)QR_HELPER_GRID_SUBSTEPS ? tn.helper_grid : (unsigned)QR_HELPER_GRID_SUBSTEPS)
+         helper_choice(a, tiles, kind == QR_KIND_QUAD ? (tn.helper_grid < kHelperGridSubsteps ? tn.helper_grid : kHelperGridSubsteps)
                                                       : (tn.helper_grid_wrap < wrap_traj ? tn.helper_grid_wrap : wrap_traj));
 }
 
@@ -1627,7 +1520,7 @@ static inline bool wants_helper_traj(const Args& a, int kind) {  // the same wit
 // against 7.60 us chunked).
 static inline unsigned rollout_chunk(const Args& a, int kind, int layout) {
   const unsigned tiles = (unsigned)((a.n + 63) / 64), limit = tuning().helper_grid_rollout;
-  if (a.act_out == nullptr || !QR_HELP_POLICY || kind == QR_KIND_QUAD || layout != QR_LAYOUT_MIXED || tiles <= limit || limit == 0) return 0;
+  if (a.act_out == nullptr || kind == QR_KIND_QUAD || layout != QR_LAYOUT_MIXED || tiles <= limit || limit == 0) return 0;
   if ((a.flags & QR_FLAG_NO_HELPER_ROLLOUT) || !(a.flags & QR_FLAG_AUTO_RESET) || a.goal_mode != QR_GOAL_EXTERNAL) return 0;
   return limit;
 }
@@ -1670,7 +1563,7 @@ static inline Pick pick_shape(const Args& a, int kind, int layout, unsigned tile
       // profiles/r05/ab_actor_plain.txt).  External goals only: with the fused generator the actor launches stay rate-adaptive.
       // (the general form — SAC's log_std head and rule — with the same split; measured, profiles/r05/ab_sac_helper.txt,
       //  65 536 envs, T = 32: Coupled 4.95 -> 4.38 us per env-step, Decoupled 5.54 -> 4.87, bit-identical)
-      if (QR_HELP_POLICY && !traj && (a.flags & QR_FLAG_AUTO_RESET) && helper_choice(a, tiles, tuning().helper_grid_rollout))
+      if (!traj && (a.flags & QR_FLAG_AUTO_RESET) && helper_choice(a, tiles, tuning().helper_grid_rollout))
         return {0, adapt, general ? 2 : 1, false, true, true};
       if (!traj && !adapt) return {0, false, general ? 2 : 1, false, false, true};
     }
@@ -1686,12 +1579,12 @@ static inline Pick pick_shape(const Args& a, int kind, int layout, unsigned tile
     }
     if (adapt) return {0, true, 0, true, false, true};
     if (help) {
-      // (Quad-v0, one substep, more than QR_HELP_REWARD_TILES tiles: the reward stays on the stepping wave — measured with the
+      // (Quad-v0, one substep, more than kHelpRewardTiles tiles: the reward stays on the stepping wave — measured with the
       //  product's other choices in place, profiles/r05/ab_step_prio.txt: 98 304 envs 5.12 -> 4.92 us, 163 840 envs 7.31 -> 6.57;
-      //  identical bits.  The wrappers, one substep, more than QR_HELP_ROWS_TILES tiles: the helper only samples the pool, the
+      //  identical bits.  The wrappers, one substep, more than kHelpRowsTiles tiles: the helper only samples the pool, the
       //  rows go out with the stepping wave — 114 688 envs Coupled 8.14 -> 6.98 us, Decoupled 8.21 -> 6.97; 131 072: 9.07 -> 8.61 /
       //  9.11 -> 8.69; 98 304 envs and below are better with the helper's rows; profiles/r05/ab_step_prio.txt)
-      const unsigned lim = kind == QR_KIND_QUAD ? (unsigned)QR_HELP_REWARD_TILES : (unsigned)QR_HELP_ROWS_TILES;
+      const unsigned lim = kind == QR_KIND_QUAD ? kHelpRewardTiles : kHelpRowsTiles;
       return {0, false, 0, true, true, !(a.substeps == 1 && tiles > lim)};
     }
     return {0, false, 0, true, false, true};
@@ -1707,7 +1600,7 @@ static inline Pick pick_shape(const Args& a, int kind, int layout, unsigned tile
 // two or more substeps in the default layout take the Magnus substep (MAG; qr_dynamics.h: 74 instead of 149 instructions per
 // substep), one substep keeps RK4 in kernels that hold nothing else (byte-identical to the build without MAG).  The rate-adaptive
 // delta-form instantiations (ADAPT without an actor: the launches whose envs may leave the regime) have their own arithmetic.
-static constexpr bool uses_plain_integrate(int adapt, int policy) { return !(adapt && QR_DELTA_STAGES && !policy); }
+static constexpr bool uses_plain_integrate(int adapt, int policy) { return !adapt || policy; }
 static inline Pick pick_instance(const Args& a, int kind, int layout, unsigned tiles_of_launch = 0) {
   Pick p = pick_shape(a, kind, layout, tiles_of_launch);
   p.mag = layout == QR_LAYOUT_MIXED && a.substeps >= 2 && uses_plain_integrate(p.adapt, p.policy);
@@ -1904,17 +1797,6 @@ int qr_debug_set_span(void* buf) {  // diagnostic build only: device buffer [slo
   return 0;
 }
 void qr_debug_set_span_slot(int slot) { qr::g_span_slot = slot; }  // the row the NEXT launches write (baked into a captured launch)
-#endif
-
-#ifdef QR_STAMPS
-int qr_debug_set_stamps(void* buf) {  // diagnostic builds only: device buffer of 8 x uint64 per wave (NULL = off)
-  unsigned long long* p = reinterpret_cast<unsigned long long*>(buf);
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(qr::g_stamps), &p, sizeof(p));
-}
-int qr_debug_set_hwid(void* buf) {  // 2 x uint64 per workgroup: HW_ID | XCC_ID << 32 of its stepping and helper wave (NULL = off)
-  unsigned long long* p = reinterpret_cast<unsigned long long*>(buf);
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(qr::g_hwid), &p, sizeof(p));
-}
 #endif
 
 int qr_abi_version(void) { return QR_ABI_VERSION; }

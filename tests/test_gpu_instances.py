@@ -11,7 +11,7 @@ import torch
 from conftest import grouped_rel_err
 
 KINDS = ("quad", "coupled", "decoupled")
-BIG = 64 * 1700 + 5      # 1701 tiles: beyond QR_HELP_REWARD_TILES / QR_HELP_ROWS_TILES, inside the helper-wave thresholds
+BIG = 64 * 1700 + 5      # 1701 tiles: beyond kHelpRewardTiles / kHelpRowsTiles (1408 / 1600), inside the helper-wave thresholds
 
 
 def _make(kind, n, layout, goal_mode, auto_reset, w_adapt, helper=None, substeps=1):

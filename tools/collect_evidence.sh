@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box (via gpurun): everything DESIGN.md §5 cites, into gpurun_out/<round>/ (copy to profiles/<round>/).
 #   tools/collect_evidence.sh r05 [profiles|bench|ab|tests|all]
-# The measurement-only builds are NOT pushed with the repo (.gpurunignore: build/evidence/): they are built here first.
+# The stand-alone microbenchmarks (build/evidence/) are not shipped with the sources: they are built here first.
 set -u
 RND=${1:-r05}; WHAT=${2:-all}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -65,11 +65,12 @@ b f64_quad65536 --layout f64 ; b f64_coupled65536 --layout f64 --kind coupled ; 
 python3 tools/noop_yardstick.py > "$OUT/noop_yardstick.json" 2> "$OUT/noop_yardstick.err"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = ab ]; then
-# (3) build-time ablations (A/B of libraries), run-time A/B, timelines, microbenchmarks
-QR_AB_JSON=$OUT/ab_quad_builds.json QR_AB_KINDS=quad QR_AB_SIZES=65536,1048576 python3 tools/ab_libs.py $EV/libquadrotor_hip_q.so $EV/libquadrotor_hip_q_aux0.so $EV/libquadrotor_hip_q_norew.so $EV/libquadrotor_hip_q_nohelp.so $EV/libquadrotor_hip_q_floor.so $EV/libquadrotor_hip_q_copy.so > "$OUT/ab_quad_builds.txt" 2>&1
-tools/sweep_kinds.sh "$EV/libquadrotor_hip_nohelp.so $EV/libquadrotor_hip_aux0.so gym_rotor_amd/libquadrotor_hip.so" "quad:65536 quad:98304 quad:131072 quad:163840 quad:196608 coupled:65536 coupled:131072 coupled:262144 decoupled:32768 decoupled:65536 decoupled:131072 decoupled:262144" > "$OUT/ab_helper_wave.txt" 2>&1
+# (3) run-time A/B, microbenchmarks
+# (the build-time ablations of rounds 2-5 — ab_quad_builds.txt, stamps_*.txt — are retired: profiles/r05/ holds their last record)
+HW_CASES="quad:65536 quad:98304 quad:131072 quad:163840 quad:196608 coupled:65536 coupled:131072 coupled:262144 decoupled:32768 decoupled:65536 decoupled:131072 decoupled:262144"
+{ echo "# no helper-wave launches (QR_HELPER_GRID=0)"; QR_HELPER_GRID=0 tools/sweep_kinds.sh gym_rotor_amd/libquadrotor_hip.so "$HW_CASES"
+  echo "# the launch rule"; tools/sweep_kinds.sh gym_rotor_amd/libquadrotor_hip.so "$HW_CASES"; } > "$OUT/ab_helper_wave.txt" 2>&1
 python3 tools/evidence.py > "$OUT/runtime_ab.json" 2> "$OUT/runtime_ab.err"
-for ar in 1 0; do QR_LIB=$PWD/$EV/libquadrotor_hip_q_stamps.so python3 tools/stamp_timeline.py --auto-reset $ar --json "$OUT/stamps_quad65536_ar$ar.json" > "$OUT/stamps_quad65536_ar$ar.txt" 2>&1; done
 bash tools/rocprof_floor.sh > "$OUT/rocprof_dispatch_floor.txt" 2>&1
 $EV/valu_mb > "$OUT/valu_microbench.json" 2> "$OUT/valu_microbench.err"
 $EV/vmem_mb > "$OUT/vmem_width_microbench.json" 2> "$OUT/vmem_width_microbench.err"

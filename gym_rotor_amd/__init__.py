@@ -11,6 +11,7 @@ from .vec_env import CapturedStep, QuadVecEnv, as_gymnasium_vector_env  # noqa: 
 from .compat import QuadEnv, CoupledWrapper, DecoupledWrapper  # noqa: F401
 from .rollout import RolloutStorage  # noqa: F401
 from .policy import ActorParams, random_actors  # noqa: F401
+from .evaluate import EvalResult, evaluate_policy  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)
 
 __all__ = ["QuadVecEnv", "QuadEnv", "CoupledWrapper", "DecoupledWrapper", "QuadConstants", "Box",

@@ -19,19 +19,19 @@ FLAG_AUTO_RESET, FLAG_EVAL_RESET, FLAG_NO_UDM = 1, 2, 4
 FLAG_FORCE_HELPER, FLAG_NO_HELPER = 8, 16   # launch-rule overrides of the one-step launch (speed only)
 FLAG_CALLER_RESETS = 32                     # the caller resets every done env before stepping it again (one-step launches)
 FLAG_FORCE_HELPER_ROLLOUT, FLAG_NO_HELPER_ROLLOUT = 64, 128   # the same overrides for qr_rollout / qr_rollout_actor
-ABI_VERSION = 15
+ABI_VERSION = 16
 GOAL_EXTERNAL, GOAL_MODE0, GOAL_MODE1, GOAL_MODE6, GOAL_MODE2, GOAL_MODE3, GOAL_MODE4, GOAL_MODE5 = 0, 1, 2, 3, 4, 5, 6, 7
 GOAL_ID = {None: 0, 0: 1, 1: 2, 6: 3, 2: 4, 3: 5, 4: 6, 5: 7}  # TrajectoryGenerator mode -> QR_GOAL_*
 LAYOUT_ID = {"mixed": 0, "f64": 1, "f32": 2}
 
 ERRORS = {-1: "QR_E_NULL: a required pointer is NULL", -2: "QR_E_KIND: bad env kind",
-          -3: "QR_E_SIZE: bad num_envs / substeps / n_steps / coefficients", -4: "QR_E_ALIGN: buffer not 16-byte aligned"}
+          -3: "QR_E_SIZE: bad num_envs / substeps / n_steps / max_steps / actor sizes / coefficients", -4: "QR_E_ALIGN: buffer not 16-byte aligned"}
 
 # every symbol include/quadrotor_hip.h declares
 SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_error_obs_format", "qr_reset", "qr_get_state", "qr_set_state", "qr_check_state",
            "qr_traj_start", "qr_get_desired", "qr_gae",
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
-           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch")
+           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor")
 
 
 class QrCoeffs(C.Structure):
@@ -74,6 +74,11 @@ class QrPolicyRollout(C.Structure):
                 ("action_out", C.c_void_p), ("logprob_out", C.c_void_p)]
 
 
+class QrEvalOut(C.Structure):
+    _fields_ = [("episode_return", C.c_void_p), ("benchmark", C.c_void_p), ("length", C.c_void_p), ("terminated", C.c_void_p),
+                ("success", C.c_void_p), ("final_error", C.c_void_p), ("obs0", C.c_void_p), ("obs1", C.c_void_p)]
+
+
 class QrLaunchPlan(C.Structure):
     _fields_ = [("grid", C.c_int32), ("block", C.c_int32), ("launches", C.c_int32),
                 ("traj", C.c_int32), ("adapt", C.c_int32), ("policy", C.c_int32), ("single", C.c_int32), ("help", C.c_int32), ("hrew", C.c_int32),
@@ -111,6 +116,8 @@ def load():
     lib.qr_rollout.argtypes = [P(QrEnv), C.c_void_p, C.c_int32, C.c_int32, P(QrStepOut), C.c_void_p]
     lib.qr_rollout_actor.restype = C.c_int
     lib.qr_rollout_actor.argtypes = [P(QrEnv), P(QrPolicyRollout), C.c_int32, C.c_int32, P(QrStepOut), C.c_void_p]
+    lib.qr_evaluate_actor.restype = C.c_int
+    lib.qr_evaluate_actor.argtypes = [P(QrEnv), P(QrPolicyRollout), C.c_int32, C.c_int32, P(QrEvalOut), C.c_void_p]
     lib.qr_error_obs.restype = C.c_int
     lib.qr_error_obs.argtypes = [P(QrEnv), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.qr_error_obs_format.restype = C.c_int

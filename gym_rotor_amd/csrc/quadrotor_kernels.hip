@@ -39,6 +39,7 @@
 //   qr_dynamics.h  attitude helpers, quaternion-form RHS + RK4, row transposes, action maps, error obs
 //   qr_traj.h      goal generator (trajectory_generator.py modes 0/1/6), SoA buffer accessor
 //   qr_actor.h     PPO actor (MFMA / LDS forms), action sampling
+//   qr_eval.h      batched policy evaluation (qr_evaluate_actor): eval_kernel
 //   this file      step / rollout kernel, auxiliary kernels, host launchers and the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr below.
@@ -58,6 +59,7 @@
 #include "qr_dynamics.h"
 #include "qr_traj.h"
 #include "qr_actor.h"
+#include "qr_eval.h"
 
 namespace qr {
 
@@ -1787,6 +1789,75 @@ static int do_rollout(const QrEnv* env, const float* action, const QrPolicyRollo
   return rc;
 }
 
+// qr_evaluate_actor: eval_kernel over the whole grid, one 64-env tile per workgroup.  Instantiations: both wrappers x TRAJ 0 / 1 / 2 x
+// (default layout: RK4 and Magnus; uniform layouts: RK4) = 24, none of them a step_kernel (not in QR_INSTANCES, not counted by
+// qr_launch_stats).  The integrator follows pick_instance's rule for a plain actor rollout: Magnus for two or more substeps in the
+// default layout.
+template <int KIND, typename XV, typename QW>
+static void launch_eval_kind(const EvalLaunch& k, hipStream_t s) {
+  constexpr bool kMixed = std::is_same<XV, float>::value && std::is_same<QW, double>::value;
+  const dim3 grid((unsigned)((k.a.n + 63) / 64));
+  const int traj = k.a.goal_mode == QR_GOAL_EXTERNAL ? 0 : (k.a.goal_mode >= QR_GOAL_MODE2 ? 2 : 1);
+  const bool mag = kMixed && k.a.substeps >= 2 && uses_plain_integrate(0, 1);
+#define QR_EVAL(TR, MG) hipLaunchKernelGGL((eval_kernel<KIND, XV, QW, TR, MG>), grid, dim3(64), 0, s, k)
+  if constexpr (kMixed) {
+    if (mag) {
+      if (traj == 0) QR_EVAL(0, true); else if (traj == 1) QR_EVAL(1, true); else QR_EVAL(2, true);
+      return;
+    }
+  }
+  if (traj == 0) QR_EVAL(0, false); else if (traj == 1) QR_EVAL(1, false); else QR_EVAL(2, false);
+#undef QR_EVAL
+}
+
+template <typename XV, typename QW>
+static int launch_eval(const EvalLaunch& k, int kind, hipStream_t s) {
+  if (k.a.n == 0) return 0;
+#ifdef QR_ONLY_KIND
+  if constexpr (QR_ONLY_KIND == QR_KIND_QUAD) {
+    return QR_E_KIND;
+  } else {
+    if (kind != QR_ONLY_KIND) return QR_E_KIND;
+    launch_eval_kind<QR_ONLY_KIND, XV, QW>(k, s);
+  }
+#else
+  if (kind == QR_KIND_COUPLED) launch_eval_kind<QR_KIND_COUPLED, XV, QW>(k, s);
+  else launch_eval_kind<QR_KIND_DECOUPLED, XV, QW>(k, s);
+#endif
+  return (int)hipGetLastError();
+}
+
+static int do_evaluate(const QrEnv* env, const QrPolicyRollout* pol, int32_t max_steps, int32_t substeps, const QrEvalOut* out,
+                       void* stream) {
+  EvalLaunch k{};
+  Args& a = k.a;
+  if (int rc = fill_env(a, env)) return rc;
+  if (!pol || !out) return QR_E_NULL;
+  if (env->kind == QR_KIND_QUAD) return QR_E_KIND;
+  if (substeps < 1 || max_steps < 1) return QR_E_SIZE;
+  if (!env->integ || !pol->actors || !pol->obs0_in || !out->obs0 || !out->episode_return || !out->benchmark || !out->length ||
+      !out->terminated || !out->success) return QR_E_NULL;
+  if (env->kind == QR_KIND_COUPLED) {
+    if (int rc = fill_actor(a.actor[0], pol->actors[0], 23, 16, 4)) return rc;
+  } else {
+    if (!pol->obs1_in || !out->obs1) return QR_E_NULL;
+    if (int rc = fill_actor(a.actor[0], pol->actors[0], 15, 16, 4)) return rc;
+    if (int rc = fill_actor(a.actor[1], pol->actors[1], 3, 4, 1)) return rc;
+  }
+  if (!(pol->max_action > 0.0f)) return QR_E_SIZE;
+  for (ActorW& w : a.actor) w.log_std = w.ls_w = w.ls_b = nullptr;  // the deterministic rule reads no log_std
+  a.obs0_in = pol->obs0_in; a.obs1_in = pol->obs1_in; a.act_out = pol->action_out; a.max_action = pol->max_action;
+  a.obs0 = out->obs0; a.obs1 = out->obs1;
+  a.n_steps = max_steps; a.substeps = substeps;
+  EvalArgs& e = k.e;
+  e.ret = out->episode_return; e.bench = out->benchmark; e.length = out->length; e.terminated = out->terminated;
+  e.success = out->success; e.final_error = out->final_error; e.max_steps = max_steps;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int rc = 0;
+  QR_DISPATCH_LAYOUT(env->layout, (rc = launch_eval<XV, QW>(k, env->kind, s)));
+  return rc;
+}
+
 }  // namespace qr
 
 extern "C" {
@@ -1827,6 +1898,11 @@ int qr_rollout_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t n_
                      void* stream) {
   if (!policy) return QR_E_NULL;
   return qr::do_rollout(env, nullptr, policy, n_steps, substeps, out, stream);
+}
+
+int qr_evaluate_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t max_steps, int32_t substeps, const QrEvalOut* out,
+                      void* stream) {
+  return qr::do_evaluate(env, policy, max_steps, substeps, out, stream);
 }
 
 int qr_error_obs_format(const QrEnv* env, int32_t format, float* obs0, float* obs1, void* stream) {

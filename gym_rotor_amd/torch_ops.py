@@ -133,8 +133,22 @@ def qr_rollout_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Optio
     """The collection loop with the reference's MLP actor(s) inside the step kernel (qr_rollout_actor).  actorK = the agent's
     tensors in the order fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, then EITHER log_std OR log_std_w, log_std_b (7 or 8
     tensors; actor1 = [] for COUPLED); squash = QR_ACTOR_* per agent."""
-    from .policy import ActorParams, c_actor_array
+    from .policy import c_actor_array
     e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
+    arr = c_actor_array(_actor_params(actor0, actor1, squash))
+    pol = _lib.QrPolicyRollout()
+    pol.actors = arr
+    pol.obs0_in, pol.obs1_in, pol.noise = obs0_in.data_ptr(), _p(obs1_in), _p(noise)
+    pol.noise_seed, pol.step_base = int(noise_seed) & (2 ** 64 - 1), int(step_base)
+    pol.max_action, pol.deterministic = float(max_action), int(bool(deterministic))
+    pol.action_out, pol.logprob_out = action_out.data_ptr(), _p(logprob_out)
+    o = _out_struct(obs0, obs1, reward, reward_raw, done, truncated, final_obs0, final_obs1)
+    with torch.cuda.device(pos_vel.device):
+        _lib.check(_lib.load().qr_rollout_actor(C.byref(e), C.byref(pol), n_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_rollout_actor")
+
+
+def _actor_params(actor0, actor1, squash):
+    from .policy import ActorParams
     actors = []
     for k, ts in enumerate((actor0, actor1)):
         if not ts:
@@ -145,16 +159,34 @@ def qr_rollout_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Optio
             actors.append(ActorParams(*ts[:6], None, ts[6], ts[7], int(squash[k])))
         else:
             raise ValueError("an actor is 7 tensors (.., log_std) or 8 (.., log_std_w, log_std_b)")
-    arr = c_actor_array(actors)
+    return actors
+
+
+@torch.library.custom_op(f"{_NS}::qr_evaluate_actor",
+                         mutates_args=("pos_vel", "att_rate", "integ", "goal", "traj", "steps", "action_out", "episode_return", "benchmark",
+                                       "length", "terminated", "success", "final_error", "obs0", "obs1"))
+def qr_evaluate_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Optional[torch.Tensor], params: Optional[torch.Tensor],
+                      goal: Optional[torch.Tensor], traj: Optional[torch.Tensor], episode: Optional[torch.Tensor], steps: Optional[torch.Tensor],
+                      reset_count: Optional[torch.Tensor],
+                      actor0: List[torch.Tensor], actor1: List[torch.Tensor], squash: List[int],
+                      obs0_in: torch.Tensor, obs1_in: Optional[torch.Tensor], action_out: Optional[torch.Tensor],
+                      episode_return: torch.Tensor, benchmark: torch.Tensor, length: torch.Tensor, terminated: torch.Tensor,
+                      success: torch.Tensor, final_error: Optional[torch.Tensor], obs0: torch.Tensor, obs1: Optional[torch.Tensor],
+                      max_steps: int, substeps: int, max_action: float, cfg: List[int], coeffs: List[float]) -> None:
+    """Learner.eval_policy for every env in one launch (qr_evaluate_actor): the deterministic actor(s) from each env's current state
+    until its first done or max_steps; per-env results as in QrEvalOut.  Actors as in qr_rollout_actor."""
+    from .policy import c_actor_array
+    e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
+    arr = c_actor_array(_actor_params(actor0, actor1, squash))
     pol = _lib.QrPolicyRollout()
     pol.actors = arr
-    pol.obs0_in, pol.obs1_in, pol.noise = obs0_in.data_ptr(), _p(obs1_in), _p(noise)
-    pol.noise_seed, pol.step_base = int(noise_seed) & (2 ** 64 - 1), int(step_base)
-    pol.max_action, pol.deterministic = float(max_action), int(bool(deterministic))
-    pol.action_out, pol.logprob_out = action_out.data_ptr(), _p(logprob_out)
-    o = _out_struct(obs0, obs1, reward, reward_raw, done, truncated, final_obs0, final_obs1)
+    pol.obs0_in, pol.obs1_in = obs0_in.data_ptr(), _p(obs1_in)
+    pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _p(action_out)
+    o = _lib.QrEvalOut()
+    o.episode_return, o.benchmark, o.length, o.terminated = _p(episode_return), _p(benchmark), _p(length), _p(terminated)
+    o.success, o.final_error, o.obs0, o.obs1 = _p(success), _p(final_error), _p(obs0), _p(obs1)
     with torch.cuda.device(pos_vel.device):
-        _lib.check(_lib.load().qr_rollout_actor(C.byref(e), C.byref(pol), n_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_rollout_actor")
+        _lib.check(_lib.load().qr_evaluate_actor(C.byref(e), C.byref(pol), max_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_evaluate_actor")
 
 
 @torch.library.custom_op(f"{_NS}::qr_error_obs", mutates_args=("integ", "obs0", "obs1"))
@@ -253,6 +285,14 @@ def rollout_actor(env, actors, n_steps: int, obs, out: dict, noise: Optional[tor
                   step_base: int = 0, max_action: float = 1.0, deterministic: bool = False) -> None:
     t, cfg, co = env_args(env)
     obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    lists, squash = _actor_lists(actors)
+    torch.ops.gym_rotor_amd.qr_rollout_actor(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None, noise,
+                                             out["action"], out.get("logprob"), *_outs(env, out), n_steps, env.substeps,
+                                             (env.seed if noise_seed is None else noise_seed) & (2 ** 63 - 1), step_base, max_action,
+                                             deterministic, cfg, co)
+
+
+def _actor_lists(actors):
     lists, squash = [], []
     for a in actors:
         ts = [a.fc1_w, a.fc1_b, a.fc2_w, a.fc2_b, a.mean_w, a.mean_b]
@@ -260,10 +300,19 @@ def rollout_actor(env, actors, n_steps: int, obs, out: dict, noise: Optional[tor
         lists.append(ts); squash.append(int(a.squash))
     while len(lists) < 2:
         lists.append([]); squash.append(0)
-    torch.ops.gym_rotor_amd.qr_rollout_actor(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None, noise,
-                                             out["action"], out.get("logprob"), *_outs(env, out), n_steps, env.substeps,
-                                             (env.seed if noise_seed is None else noise_seed) & (2 ** 63 - 1), step_base, max_action,
-                                             deterministic, cfg, co)
+    return lists, squash
+
+
+def evaluate(env, actors, max_steps: int, obs, out: dict, max_action: float = 1.0) -> None:
+    """`env.evaluate(actors, max_steps, obs)` as ONE torch op on the env's buffers: results land in `out` (the keys of the dict
+    QuadVecEnv.evaluate returns; "action" and "final_error" optional)."""
+    t, cfg, co = env_args(env)
+    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    lists, squash = _actor_lists(actors)
+    torch.ops.gym_rotor_amd.qr_evaluate_actor(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None, out.get("action"),
+                                              out["episode_return"], out["benchmark"], out["length"], out["terminated"], out["success"],
+                                              out.get("final_error"), out["obs0"], out.get("obs1"), int(max_steps), env.substeps,
+                                              float(max_action), cfg, co)
 
 
 def error_obs(env, framework: Optional[str] = None, out=None) -> None:

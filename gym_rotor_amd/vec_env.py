@@ -446,27 +446,11 @@ class QuadVecEnv:
         obs0[t] is the observation after step t.  out: the same dict with preallocated tensors
         (e.g. views of a RolloutStorage)."""
         from . import policy as _policy
-        if self.kind == "quad":
-            raise ValueError("rollout_actor needs kind 'coupled' or 'decoupled' (the reference trains on the wrappers)")
-        if not self.obs_rows:
-            raise ValueError("rollout_actor needs obs_rows=True")
-        actors = list(actors)
-        dims = _policy.ACTOR_DIMS[self.kind]
-        if len(actors) != len(dims):
-            raise ValueError(f"kind {self.kind!r} needs {len(dims)} actor(s)")
-        for a_, d in zip(actors, dims):
-            a_.check(d, self.device)
+        actors = self._check_actors(actors, "rollout_actor")
         T, N, A, dev = int(n_steps), self.num_envs, self.action_dim, self.device
         if T < 1:
             raise ValueError("n_steps must be >= 1")
-        if obs is None:
-            obs = self._last_obs
-            if obs is None:
-                raise ValueError("no current observation: call get_norm_error_state() / step() first or pass obs=")
-        obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
-        for o_, d in zip(obs, self.obs_dims):
-            if tuple(o_.shape) != (N, d) or o_.dtype != torch.float32 or o_.device != dev or not o_.is_contiguous():
-                raise ValueError(f"obs must be contiguous float32 [{N}, {d}] on {dev}")
+        obs = self._policy_obs(obs)
         if noise is not None:
             if tuple(noise.shape) != (T, N, A) or noise.dtype != torch.float32 or noise.device != dev or not noise.is_contiguous():
                 raise ValueError(f"noise must be contiguous float32 [{T}, {N}, {A}] on {dev}")
@@ -501,6 +485,90 @@ class QuadVecEnv:
         self._policy_steps += T
         self._last_obs = out["obs0"][T - 1] if len(self.obs_dims) == 1 else (out["obs0"][T - 1], out["obs1"][T - 1])
         out["obs"] = out["obs0"] if len(self.obs_dims) == 1 else (out["obs0"], out["obs1"])
+        return out
+
+    def _check_actors(self, actors, what: str) -> list:
+        """The policy launches' argument checks on the host: a wrapper kind with observation rows, one actor per agent of the
+        reference's sizes (qr_rollout_actor / qr_evaluate_actor return QR_E_SIZE otherwise)."""
+        from . import policy as _policy
+        if self.kind == "quad":
+            raise ValueError(f"{what} needs kind 'coupled' or 'decoupled' (the reference trains on the wrappers)")
+        if not self.obs_rows:
+            raise ValueError(f"{what} needs obs_rows=True")
+        actors = list(actors)
+        dims = _policy.ACTOR_DIMS[self.kind]
+        if len(actors) != len(dims):
+            raise ValueError(f"kind {self.kind!r} needs {len(dims)} actor(s)")
+        for a_, d in zip(actors, dims):
+            a_.check(d, self.device)
+        return actors
+
+    def _policy_obs(self, obs) -> list:
+        """The observation rows the first action is computed from: `obs`, or what the last step / reset returned."""
+        N, dev = self.num_envs, self.device
+        if obs is None:
+            obs = self._last_obs
+            if obs is None:
+                raise ValueError("no current observation: call get_norm_error_state() / step() first or pass obs=")
+        obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+        for o_, d in zip(obs, self.obs_dims):
+            if tuple(o_.shape) != (N, d) or o_.dtype != torch.float32 or o_.device != dev or not o_.is_contiguous():
+                raise ValueError(f"obs must be contiguous float32 [{N}, {d}] on {dev}")
+        return obs
+
+    def evaluate(self, actors, max_steps: Optional[int] = None, obs=None, max_action: float = 1.0, out: Optional[dict] = None) -> dict:
+        """Learner.eval_policy (main.py:270-404) for every env in ONE launch (qr_evaluate_actor): from each env's current state and
+        observation, the deterministic action of the actor(s) (rollout_actor(deterministic=True)'s rule) until the first step that
+        sets any agent's done flag, that step included, or `max_steps` (default round(5 s / dt) = 1000, eval_max_steps).  Then the
+        env is frozen: its state, integrators and generator state stay as they were after its last step (read them with
+        get_current_state()), episode_steps advances by `length`.  Nothing is re-sampled, whatever auto_reset says, and no per-step
+        row is written.  Returns a dict of per-env tensors:
+            episode_return [N, n_agents] float64   sum of the rewards through the terminal step (main.py:356)
+            benchmark      [N] float64             sum of benchmark_reward_func(ex, eb1) (utils/utils.py:42-47)
+            length         [N] int32               steps taken
+            terminated     [N] bool                ended by done (any agent) rather than by max_steps
+            success        [N, n_agents] bool      length == max_steps and |ex| <= 0.01 on every axis (agent 0), |eb1| <= 0.01
+                                                   (MODUL agent 1), at the last step (main.py:366-373; an early end is 0 here, where
+                                                   the reference would re-append the previous episode's flags)
+            final_error    [N, 4] float32          ex (3), eb1 of the last step (get_error_state)
+            obs0[, obs1]                           the last observation rows;  action [N, A]: the last action
+        `out`: the same dict with preallocated tensors ("final_error" and "action" may be left out).  The rows become the env's
+        current observation; the exploration-noise stream of rollout_actor does not advance."""
+        actors = self._check_actors(actors, "evaluate")
+        T = int(round(5.0 / self.dt)) if max_steps is None else int(max_steps)
+        if T < 1:
+            raise ValueError("max_steps must be >= 1")
+        if not float(max_action) > 0.0:
+            raise ValueError("max_action must be > 0")
+        obs = self._policy_obs(obs)
+        N, A, G, dev = self.num_envs, self.action_dim, self.n_agents, self.device
+        want = {"episode_return": ((N, G), torch.float64), "benchmark": ((N,), torch.float64), "length": ((N,), torch.int32),
+                "terminated": ((N,), torch.bool), "success": ((N, G), torch.bool), "final_error": ((N, 4), torch.float32),
+                "obs0": ((N, self.obs_dims[0]), torch.float32), "action": ((N, A), torch.float32)}
+        if len(self.obs_dims) > 1:
+            want["obs1"] = ((N, self.obs_dims[1]), torch.float32)
+        if out is None:
+            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
+        for k, (shape, dt) in want.items():
+            t = out.get(k)
+            if t is None and k in ("final_error", "action"):
+                continue
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
+        from .policy import c_actor_array
+        arr = c_actor_array(actors)
+        pol = _lib.QrPolicyRollout()
+        pol.actors = arr
+        pol.obs0_in, pol.obs1_in = obs[0].data_ptr(), (obs[1].data_ptr() if len(obs) > 1 else None)
+        pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _ptr(out.get("action"))
+        o = _lib.QrEvalOut()
+        o.episode_return, o.benchmark, o.length = _ptr(out["episode_return"]), _ptr(out["benchmark"]), _ptr(out["length"])
+        o.terminated, o.success, o.final_error = _ptr(out["terminated"]), _ptr(out["success"]), _ptr(out.get("final_error"))
+        o.obs0, o.obs1 = _ptr(out["obs0"]), _ptr(out.get("obs1"))
+        with self._on_device():
+            rc = self._lib.qr_evaluate_actor(C.byref(self._cenv), C.byref(pol), T, self.substeps, C.byref(o), self._stream())
+        _lib.check(rc, "qr_evaluate_actor")
+        self._last_obs = out["obs0"] if len(self.obs_dims) == 1 else (out["obs0"], out["obs1"])
         return out
 
     def capture(self, actions: Optional[torch.Tensor] = None, n_steps: int = 1, body=None, warmup: int = 1) -> "CapturedStep":

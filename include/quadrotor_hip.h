@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define QR_ABI_VERSION 15
+#define QR_ABI_VERSION 16
 
 /* env kinds */
 #define QR_KIND_QUAD      0 /* QuadEnv            gym_rotor/envs/quad.py:19            */
@@ -279,6 +279,34 @@ typedef struct QrPolicyRollout {
  * DECOUPLED only (the reference trains on the wrappers). */
 int qr_rollout_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t n_steps, int32_t substeps,
                      const QrStepOut* out, void* stream);
+
+/* Per-env results of qr_evaluate_actor (NAG = 2 for DECOUPLED, else 1). */
+typedef struct QrEvalOut {
+  double*  episode_return; /* [N][NAG] sum of rewards up to and including the terminal step (main.py:356; summed in float64, where
+                              the reference rounds the running sum to 4 decimals every step) */
+  double*  benchmark;      /* [N]      sum of benchmark_reward_func(ex, eb1) (utils/utils.py:42-47) */
+  int32_t* length;         /* [N]      steps taken (1..max_steps) */
+  uint8_t* terminated;     /* [N]      1 = ended by done (any agent), 0 = ran max_steps without */
+  uint8_t* success;        /* [N][NAG] length == max_steps and |ex|_inf <= 0.01 (agent 0), |eb1| <= 0.01 (MODUL agent 1), judged at the
+                              last step (main.py:366-373).  Deliberate deviation: the reference never clears its `success` list between
+                              episodes, so an episode that ends early re-appends the flags of the episode before it; here such an
+                              episode has success = 0. */
+  float*   final_error;    /* [N][4]   ex (3), eb1 of the last step, as get_error_state forms them; may be NULL */
+  float*   obs0; float* obs1; /* final observation rows [N][D0] / [N][D1] (DECOUPLED: obs1 required) */
+} QrEvalOut;
+
+/* Replaces Learner.eval_policy (main.py:270-404) for N envs in ONE launch: from each env's CURRENT state, its observation
+ * policy->obs0_in / obs1_in and its goal (buffer or fused generator), up to max_steps env-steps of the deterministic action
+ * (QrPolicyRollout.deterministic != 0's rule; noise, deterministic and logprob_out are ignored) until the first step that sets
+ * any agent's done flag — that step included.  Then the env freezes: its state, integrators, generator state and goal stop
+ * changing and are written back, `steps` (when present) advances by `length`, and its final observation rows, last action
+ * (policy->action_out, optional: [N][A]) and results go to `out`.  No per-step row is written, nothing is re-sampled
+ * (QR_FLAG_AUTO_RESET and max_episode_steps are ignored), and a 64-env tile stops as soon as all of its envs are frozen.
+ * Every evaluated step starts in regime, so the plain integrator runs (RK4; Magnus for substeps >= 2 in the default layout,
+ * the same rule as every other launch).  COUPLED and DECOUPLED only (QR_E_KIND for Quad-v0); QR_E_SIZE for max_steps < 1 or
+ * actor sizes other than qr_rollout_actor's. */
+int qr_evaluate_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t max_steps, int32_t substeps,
+                      const QrEvalOut* out, void* stream);
 
 /* Replaces QuadEnv.get_norm_error_state(framework) (quad.py:421-466): normalised error
  * observation of the CURRENT state; advances both trapezoid integrators (same side

@@ -133,6 +133,140 @@ def test_accounting_edge_cases():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# eval_policy in closed loop on the float64 oracle (the reference for tests/test_gpu_evaluate_oracle.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def oracle_action(actors, obs, max_action=1.0):
+    """The deterministic action of one actor per agent on the oracle: clip(mean, +-max_action) (PPO / TD3 form, ppo.py:100-101),
+    tanh(mean) for an actor with a log_std head (SAC form, sac.py:104-105), rounded to float32 as the kernel's action is."""
+    from oracle import actor_oracle as ao
+    cols = [ao.sac_sample(p, o)[0] if "log_std_w" in p else ao.choose_action(p, o, None, max_action)[0] for p, o in zip(actors, obs)]
+    return np.concatenate(cols, 1).astype(np.float32)
+
+
+def eval_oracle(kind, state, params, max_steps, actors=None, actions=None, max_action=1.0, goal_mode=None, draws=(None, None, None),
+                n_sub=1, perturb=None, fly_on=5, warm_calls=0):
+    """eval_policy (main.py:270-404) for N envs from existing pieces only: traj_oracle forms the goal before every step, actor_oracle
+    the deterministic action (`actors`: one dict of weights per agent; or `actions` [T, A]: recorded ones), quad_oracle.step_batch
+    advances the env, eval_accounting reduces the rows.  Every env is flown `fly_on` steps past its own end (a decision tie with
+    the GPU is judged on those rows) and then parked at rest, so the rows stay finite.  perturb=seed: the knife-edge probe —
+    actions jittered by +-2e-7 relative after the float32 rounding, x and v rounded to float32 after every step.
+    Returns eval_accounting's dict plus, per env AT ITS OWN TERMINAL STEP, state [N,18], integ [N,8], goal [N,12] and the
+    generator dict `traj`; and `rows`: obs0[, obs1], action, reward, done of every step flown [T', N, .]."""
+    from oracle import quad_oracle as orc
+    from oracle import traj_oracle as trj
+    fw = "MODUL" if kind == "decoupled" else "MONO"
+    state = np.array(state, dtype=np.float64)
+    n = len(state)
+    rng = None if perturb is None else np.random.default_rng(perturb)
+    tr, goal12 = None, np.tile(orc.DEFAULT_GOAL, (n, 1))
+
+    def desired():
+        xd, vd, b1d, _, Wd = trj.get_desired_batch(tr, state)
+        return np.concatenate([xd, vd, b1d, Wd], 1)
+
+    if goal_mode is not None:  # main.py:305-309: mark_traj_start, the first goal, the first observation
+        tr = trj.traj_start_batch(state, goal_mode, theta_b1d=draws[0], t_traj=draws[1], w_b1d=draws[2])
+        for _ in range(warm_calls):   # (the generator's clock run ahead with the env held at its start, to reach a late phase sooner)
+            desired()
+        goal12 = desired()
+    first = orc.error_obs_batch(kind, state, goal12, np.zeros((n, 8)))
+    obs, integ = first["obs"], first["integ"]
+    rest = np.zeros(18)
+    rest[6] = rest[10] = rest[14] = 1.0
+    live, ended_at = np.ones(n, bool), np.full(n, max_steps)
+    rows = {k: [] for k in ("obs0", "obs1", "action", "reward", "done")}
+    end = {"state": np.zeros((n, 18)), "integ": np.zeros((n, 8)), "goal": np.zeros((n, 12)),
+           "traj": None if tr is None else {k: np.array(v) for k, v in tr.items()}}
+    for t in range(max_steps):
+        if tr is not None:
+            goal12 = desired()
+        act = np.broadcast_to(actions[t], (n, len(actions[t]))) if actions is not None else oracle_action(actors, obs, max_action)
+        act = np.asarray(act, np.float32).astype(np.float64)
+        if rng is not None:
+            act = act * (1.0 + rng.uniform(-2e-7, 2e-7, act.shape))
+        out = orc.step_batch(kind, state, act, params, goal12, integ, n_sub=n_sub)
+        state, integ, obs = out["state"], out["integ"], out["obs"]
+        if rng is not None:
+            state[:, 0:6] = state[:, 0:6].astype(np.float32)
+        for k, v in (("obs0", obs[0]), ("obs1", obs[1] if len(obs) > 1 else None), ("action", act.astype(np.float32)),
+                     ("reward", out["reward"]), ("done", out["done"])):
+            if v is not None:
+                rows[k].append(v)
+        ending = live & (out["done"].any(1) | (t + 1 == max_steps))
+        if ending.any():
+            end["state"][ending], end["integ"][ending], end["goal"][ending] = state[ending], integ[ending], goal12[ending]
+            if tr is not None:
+                for k, v in tr.items():
+                    if isinstance(v, np.ndarray) and v.shape[:1] == (n,):
+                        end["traj"][k][ending] = v[ending]
+            ended_at[ending] = t + 1
+        live &= ~ending
+        gone = t + 1 >= ended_at + fly_on
+        state[gone], integ[gone] = rest, 0.0
+        if not live.any() and t + 1 >= min(max_steps, ended_at.max() + fly_on):
+            break
+    rows = {k: np.stack(v) for k, v in rows.items() if v}
+    res = eval_accounting(rows["reward"], rows["done"], rows["obs0"], rows.get("obs1"), fw, max_steps, x_lim=orc.X_LIM)
+    assert (res["length"] == ended_at).all()
+    res.update(end, rows=rows)
+    return res
+
+
+@pytest.mark.parametrize("fw,kind,mode", [("mono", "coupled", 1), ("modul", "decoupled", 6)])
+def test_eval_oracle_on_the_reference_eval_flights(golden, fw, kind, mode):
+    """The closed-loop helper with the RECORDED actions of the shipped TD3 actor in place of the actor, on one reference flight
+    per wrapper: what it accounts equals eval_accounting of the reference's recorded rows — lengths and flags identical, returns
+    within the 1e-6 per step and rows within the 2e-7 that test_oracle_replays_the_shipped_policy_flights allows, the frozen
+    state within its 1e-9.  (The benchmark's step is 0.5 (2 - |ex| - |eb1|): at most 0.5 (sqrt 3 + pi) times the row bar.)
+    Both flights last all T steps without a done (the shipped policy keeps flying), so the helper's bookkeeping of an EARLY end
+    — the capture at the terminal step, the parking after fly_on — is not pinned to the reference here: it is checked by the
+    helper's own assertion that eval_accounting finds the lengths it froze at."""
+    g = golden(f"closedloop_td3_{fw}")
+    p = f"m{mode}_"
+    framework = fw.upper()
+    T = min(1000, len(g[p + "actions"]))
+    obs1 = g[p + "obs1"][:, None] if p + "obs1" in g else None
+    want = eval_accounting(g[p + "rewards"][:, None], g[p + "dones"][:, None], g[p + "obs0"][:, None], obs1, framework, T)
+    got = eval_oracle(kind, g[p + "init_state"][None], np.atleast_2d(g["params"]), T, actions=g[p + "actions"], goal_mode=mode,
+                      draws=tuple(g[p + "draws"]))
+    assert got["length"][0] == want["length"][0] == T and not got["terminated"][0] and not want["terminated"][0]
+    assert (got["success"] == want["success"]).all()
+    assert np.abs(got["episode_return"] - want["episode_return"]).max() <= 1e-6 * T
+    assert abs(got["benchmark"][0] - want["benchmark"][0]) <= 0.5 * (np.sqrt(3) + np.pi) * 2e-7 * T
+    assert np.abs(got["final_error"] - want["final_error"]).max() <= 2e-7 * np.pi
+    assert np.abs(got["rows"]["obs0"][T - 1, 0].astype(np.float64) - g[p + "obs0"][T - 1]).max() <= 2e-7
+    from conftest import grouped_rel_err
+    assert grouped_rel_err(got["state"], g[p + "states"][T][None]) <= 1e-9
+    assert got["traj"]["calls"][0] == T + 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# which eval kernels the build holds
+# ---------------------------------------------------------------------------------------------------------------------
+def test_the_build_holds_exactly_the_24_eval_kernels(tmp_path):
+    """The eval_kernel<...> symbols of the built library's gfx950 code object (llvm-objdump --offloading, demangled names, as
+    tools/codeobj_diff.py lists kernels): exactly the 24 instantiations that the table of tests/test_gpu_evaluate_oracle.py flies."""
+    import re
+    import shutil
+    from test_gpu_evaluate_oracle import INSTANCES, TABLE, instance_of
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    objdump = shutil.which("llvm-objdump", path=os.pathsep.join([f"{rocm}/lib/llvm/bin", f"{rocm}/llvm/bin", os.environ.get("PATH", "")]))
+    assert objdump, f"llvm-objdump not found under {rocm} or on PATH: the build's kernels cannot be listed"
+    lib = os.environ.get("QR_LIB") or os.path.join(ROOT, "gym_rotor_amd", "libquadrotor_hip.so")
+    shutil.copy(lib, tmp_path / "lib.so")
+    subprocess.run([objdump, "--offloading", "lib.so"], check=True, capture_output=True, cwd=tmp_path)
+    co = [f for f in os.listdir(tmp_path) if "gfx950" in f]
+    assert co, "no gfx950 code object in the library"
+    syms = subprocess.run([objdump, "--syms", "-C", str(tmp_path / co[0])], check=True, capture_output=True, text=True).stdout
+    found = set(re.findall(r" F \.text\s+[0-9a-f]+\s+(?:\.protected )?(?:void )?qr::eval_kernel<([^>]*)>\(qr::EvalLaunch\)$", syms, re.M))
+    types = {"mixed": "float, double", "f64": "double, double", "f32": "float, float"}
+    name = lambda kind, layout, traj, mag: f"{ {'coupled': 1, 'decoupled': 2}[kind]}, {types[layout]}, {traj}, {'true' if mag else 'false'}"
+    assert len(found) == 24, sorted(found)
+    assert found == {name(*i) for i in INSTANCES}
+    assert found == {name(*instance_of(*row[:4])) for row in TABLE}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the C-ABI
 # ---------------------------------------------------------------------------------------------------------------------
 def test_qr_eval_out_mirrors_the_header(tmp_path):

@@ -66,6 +66,8 @@ def _np(t):
 
 
 CASES = [(k, g, lay, s) for k in ("coupled", "decoupled") for g in (None, 0, 6) for lay in ("mixed", "f64", "f32") for s in (1, 4)]
+# the generator's stateful modes (TRAJ == 2: the one path with evaluate-only code, the write-back at each lane's freeze)
+CASES += [(k, g, lay, s) for k in ("coupled", "decoupled") for g, lay, s in ((2, "mixed", 1), (3, "mixed", 4), (4, "f64", 1), (5, "f64", 4))]
 
 
 @pytest.mark.parametrize("kind,goal_mode,layout,substeps", CASES)
@@ -113,7 +115,9 @@ def test_evaluate_matches_the_actor_rollout(kind, goal_mode, layout, substeps):
 
 
 @pytest.mark.parametrize("kind,layout,substeps,goal_mode", [("coupled", "mixed", 1, None), ("decoupled", "mixed", 4, 1),
-                                                             ("decoupled", "f64", 1, 0), ("coupled", "f32", 4, 6)])
+                                                             ("decoupled", "f64", 1, 0), ("coupled", "f32", 4, 6),
+                                                             ("coupled", "mixed", 1, 3), ("decoupled", "f64", 4, 5),
+                                                             ("coupled", "mixed", 4, 2), ("decoupled", "mixed", 1, 4)])
 def test_evaluate_freezes_each_env_at_its_terminal_step(kind, layout, substeps, goal_mode):
     """After evaluate, each env's state is the state after `length` step() calls from the same start with the same actions (the
     rollout's action rows), and episode_steps has advanced by `length`."""

@@ -712,8 +712,8 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     // and in regime — |W| < 2 pi < w_adapt — this costs one ballot): every lane takes at least
     // the count its own rate asks for.
     if constexpr (ADAPT) {
-      // (kDelta) The launches that step envs on without in-launch resets — the only ones in which an env can leave the
-      // regime — form the quaternion stages in delta form (qr_dynamics.h: integrate_delta): their free run lands on RK4's
+      // (kDelta) The launches that step envs on without in-launch resets — in which an env can leave the regime — and those
+      // with resets whose W_lim puts the re-sampling bound within reach of w_adapt (wants_adapt: 2.5 W_lim > w_adapt) form the quaternion stages in delta form (qr_dynamics.h: integrate_delta): their free run lands on RK4's
       // truncation floor instead of 7x above it.  qr_rollout_actor keeps the plain stages (its kernel is at its register limit).
       constexpr bool kDelta = !POLICY;
       const T wmax = fmax(fmax(fabs(w.W[0]), fabs(w.W[1])), fabs(w.W[2]));

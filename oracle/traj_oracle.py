@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .quad_oracle import DT
+from . import quad_oracle as _orc
 
 
 def _R(state):
@@ -138,11 +138,13 @@ def _stateful_modes(tr, state, dt):
     return skip_wd
 
 
-EIGHT = dict(T=9.0, A1=1.5, A2=1.0, w_b1d=0.349066, alt_d=-0.6, eps=0.01, count=3)  # :98-110
+EIGHT = _orc.EIGHT  # :98-110 (one table, changed in place by quad_oracle.constants)
 
 
-def get_desired_batch(tr, state, dt=DT, eight=None):
-    """get_desired(state, mode) (:113-173): advances t by dt, returns xd, vd, b1d, b1d_dot, Wd [N,3]."""
+def get_desired_batch(tr, state, dt=None, eight=None):
+    """get_desired(state, mode) (:113-173): advances t by dt, returns xd, vd, b1d, b1d_dot, Wd [N,3].
+    dt=None: quad_oracle.DT when called; `eight` entries replace those of the EIGHT table as it stands when called."""
+    dt = _orc.DT if dt is None else dt
     state = np.atleast_2d(np.asarray(state, dtype=np.float64))
     n = state.shape[0]
     tr["calls"] = tr["calls"] + 1.0  # update_current_time (:224-229)

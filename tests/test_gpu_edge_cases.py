@@ -144,15 +144,29 @@ def _same_env_state(a, b):
                                      ("coupled", dict(auto_reset=True, goal_mode=0, final_obs=True)),
                                      ("decoupled", dict(auto_reset=True, goal_mode=5, final_obs=True)),   # a stateful goal mode: the op mutates `goal` too
                                      ("decoupled", dict(auto_reset=True, max_episode_steps=25, final_obs=True, w_adapt=12.0)),
-                                     ("coupled", dict(auto_reset=False, layout="f64", substeps=2))])
-def test_torch_custom_ops_match_the_env_bit_for_bit(kind, kw):
+                                     ("coupled", dict(auto_reset=False, layout="f64", substeps=2)),
+                                     # every coefficient off its default, no two neighbours of QrCoeffs alike (tests/golden/onestep_coeffs_A.npz):
+                                     # the eight-curve generator and the in-launch reset read theirs too
+                                     ("decoupled", dict(auto_reset=True, goal_mode=6, final_obs=True, coeff_set="A")),
+                                     ("quad", dict(auto_reset=True, obs_rows=True, coeff_set="A"))])
+def test_torch_custom_ops_match_the_env_bit_for_bit(kind, kw, golden):
     """torch.ops.gym_rotor_amd.* carry the FULL QrEnv (coefficients, fused goals, time limit, truncated, raw reward, terminal
     observations, reset counters): stepping through the ops equals QuadVecEnv.step / rollout / get_norm_error_state /
     reset / get / set state bit for bit — eagerly, under torch.compile(fullgraph=True) and replayed from a captured graph."""
     from gym_rotor_amd import QuadConstants, torch_ops as ops
     n = 1000
     consts = QuadConstants(Cx=5.0, Cv=0.3, x_lim=0.9, alpha=0.02)          # non-default coefficients must reach the kernel
+    kw = dict(kw)
+    if kw.pop("coeff_set", None):
+        import coeff_cases
+        consts, udm, cw, _ = coeff_cases.coeff_set(golden("onestep_coeffs_A"))
+        kw["UDM_percentage"] = udm
     env, ref = _twin(kind, n, seed=6, constants=consts, **kw)
+    if "UDM_percentage" in kw:                                             # CW apart from Cw12 (QuadConstants ties them), on both paths
+        for e in (env, ref):
+            e._cenv.coeffs.CW = cw
+            e._sync_structs()
+        assert env._op_coeffs[5] == cw != env._op_coeffs[6]
     g = torch.Generator(device="cuda"); g.manual_seed(0)
     acts = torch.rand(12, n, env.action_dim, device="cuda", generator=g) * 2 - 1
 

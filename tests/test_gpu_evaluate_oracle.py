@@ -245,11 +245,13 @@ def _compare(tag, env, got, want, layout, steps0, calls0=1, x_lim=1.0, numbers=T
 
 
 def _run(tag, kind, n, T, actors, layout="mixed", substeps=1, goal_mode=None, x_lim=1.0, rest_x=None, max_action=1.0, out=None,
-         numbers_steps=None, **kw):
+         numbers_steps=None, setup=None, **kw):
     """One case: env, starts, the oracle's evaluation (knife-edge inputs refused on it alone), the launch, the comparison.
     numbers_steps = K (float32 layout): the numbers are compared on a flight of K steps from these starts, the T-step flight —
     from the same starts again — for the decisions, the counters and the generator's write-back only."""
     env = _env(kind, n, layout=layout, substeps=substeps, goal_mode=goal_mode, **kw)
+    if setup is not None:   # (what the constructor cannot express, e.g. QrCoeffs.CW apart from Cw12)
+        setup(env)
     warm = WARM_CALLS.get(goal_mode, 0)
     obs, state, params, draws = _starts(env, x_lim, rest_x, warm)
     env.start = (env.state_dict(), [o.clone() for o in obs])
@@ -391,18 +393,17 @@ def test_tile_geometry_and_no_write_past_the_batch(kind):
 
 
 @pytest.mark.parametrize("kind", KINDS)
-def test_non_default_limits_and_reward_coefficients(kind, monkeypatch):
+def test_non_default_limits_and_reward_coefficients(kind):
     """x_lim = 2 and other reward coefficients (QuadConstants), the same values in the oracle.  Envs hover at 8, 12, 15 and 25 mm from
     the goal — both sides of |ex| = 0.01 in METRES and of 0.01 in normalised units: without the x_lim factor in ex the 12 and 15 mm
     envs would succeed; the doomed third starts 0.2 m inside the 2 m bound."""
     from gym_rotor_amd.constants import QuadConstants
     c = QuadConstants(x_lim=2.0, Cx=8.0, Cv=0.7, Cb1=4.5, Cw12=0.9, CW3=0.3)
-    for k, v in (("X_LIM", c.x_lim), ("CX", c.Cx), ("CV", c.Cv), ("CB1", c.Cb1), ("CW12", c.Cw12), ("CW", c.CW), ("CW3", c.CW3),
-                 ("REWARD_MIN", c.reward_min), ("REWARD_MIN_1", c.reward_min_1), ("REWARD_MIN_2", c.reward_min_2)):
-        monkeypatch.setattr(orc, k, v)
     n, T = 130, 100
     rest_x = [(0.008, 0, 0), (0, -0.012, 0), (0, 0, 0.015), (0.025, 0, 0)]
-    env, got, want, ok = _run(f"{kind} x_lim 2", kind, n, T, _actors(kind, 2, zero=True), x_lim=2.0, rest_x=rest_x, use_UDM=False, constants=c)
+    with orc.constants(c):
+        assert (orc.X_LIM, orc.CW, orc.REWARD_MIN, orc.REWARD_MIN_1, orc.REWARD_MIN_2) == (2.0, 0.9, c.reward_min, c.reward_min_1, c.reward_min_2)
+        env, got, want, ok = _run(f"{kind} x_lim 2", kind, n, T, _actors(kind, 2, zero=True), x_lim=2.0, rest_x=rest_x, use_UDM=False, constants=c)
     i = np.flatnonzero(np.arange(n) % 3 == 1)
     succ = _np(got["success"])[i, 0]
     assert (succ == (i % 4 == 0)).all() and (want["success"][i, 0] == succ).all(), succ

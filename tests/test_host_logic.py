@@ -1,6 +1,7 @@
 """CPU: host-side logic, the C-ABI surface (loads, exports, struct layout, argument errors)
 and the multi-process sharding path over gloo.  No compute kernel is launched here."""
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -281,6 +282,32 @@ def test_launch_geometry_rule_without_gpu():
     assert thr == {"step_quad": 3328, "step_wrappers": 2560, "rollout": 1024} or any(k in os.environ for k in ("QR_HELPER_GRID", "QR_HELPER_GRID_WRAP", "QR_HELPER_GRID_ROLLOUT"))
     assert info(0, 65536, AR | flag["FORCE_HELPER"], layout=1)[2] == 64 and info(0, 65536, AR | flag["FORCE_HELPER"], w_adapt=3.0)[2] == 64
     assert info(0, 65536, flag["FORCE_HELPER"])[2] == 64                   # no such instantiation without in-launch resets: ignored
+
+
+def test_launch_plan_reads_w_lim():
+    """wants_adapt: with in-launch resets (or the caller's reset promise, one-step launches) the rate-adaptive kernel is taken only
+    where an in-regime env could reach w_adapt: adapt = 0 while 2.5 W_lim < w_adapt, 1 otherwise; w_adapt = 0 switches it off."""
+    L = _lib()
+    lib = L.load()
+
+    def adapt(W_lim, w_adapt=16.0, flags=L.FLAG_AUTO_RESET, n_steps=1, kind=1, actor=0):
+        e = L.QrEnv()
+        lib.qr_default_coeffs(C.byref(e.coeffs))
+        e.coeffs.W_lim, e.coeffs.w_adapt = W_lim, w_adapt
+        e.kind, e.num_envs, e.pos_vel, e.att_rate, e.flags = kind, 65536, 0x1000, 0x2000, flags
+        p = L.QrLaunchPlan()
+        assert lib.qr_launch_plan(C.byref(e), n_steps, 1, actor, C.byref(p)) == 0
+        return p.adapt
+
+    for kind in (0, 1, 2):
+        assert adapt(5.1, kind=kind) == 0 and adapt(2 * math.pi, kind=kind) == 0 and adapt(4 * math.pi, kind=kind) == 1
+        assert adapt(6.39, kind=kind) == 0 and adapt(6.41, kind=kind) == 1               # 2.5 W_lim against w_adapt = 16
+        assert adapt(5.1, w_adapt=12.0, kind=kind) == 1 and adapt(4 * math.pi, w_adapt=0.0, kind=kind) == 0
+        assert adapt(5.1, n_steps=32, kind=kind) == 0 and adapt(4 * math.pi, n_steps=32, kind=kind) == 1
+        assert adapt(5.1, flags=0, kind=kind) == 1                                          # free run: always
+        assert adapt(5.1, flags=L.FLAG_CALLER_RESETS, kind=kind) == 0 and adapt(4 * math.pi, flags=L.FLAG_CALLER_RESETS, kind=kind) == 1
+        assert adapt(5.1, flags=L.FLAG_CALLER_RESETS, n_steps=8, kind=kind) == 1            # (the promise holds for one-step launches only)
+    assert adapt(5.1, n_steps=32, actor=1) == 0 and adapt(4 * math.pi, n_steps=32, actor=1) == 1
 
 
 def test_launch_plan_names_the_instantiation_without_gpu():

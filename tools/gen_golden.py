@@ -18,6 +18,8 @@ Files written (see tests/golden/README.md for the field lists):
   traj_reset_{kind}.npz    1000-step trajectories with reset-on-done to injected states
   errobs_formats.npz       (`python tools/gen_golden.py errobs`) get_norm_error_state("MONO" | "MODUL") on BOTH wrapper classes: the argument selects the format
   flightlog_modul.npz      all 3600 rows of results/MODUL_log_20250303_120200.dat
+  onestep_coeffs_{A,B}.npz (`python tools/gen_golden.py coeffs`) the reference with EVERY runtime coefficient moved off its default (two sets):
+                           128 single-step transitions per env kind and 128 get_norm_error_state rows per format; the values travel in the file
   gae.npz                  the reference's own GAE + normalisation lines (ppo.py:134-147) on synthetic data
   trajgoal_m{0,1,6}_{kind}.npz  closed loop env + TrajectoryGenerator (modes 0/1/6) as main.py drives them
   actor_ppo.npz            the reference's MLP_Actor_PPO (torch): weights, obs -> mean, injected-noise action, log_prob
@@ -858,6 +860,171 @@ def gen_flightlog(rows=3600):
     print("flightlog rows", rows, "of", log.shape)
 
 
+# ------------------------------------------------------------------------------------
+# every runtime coefficient off its default (QuadConstants names; CW apart from Cw12: the ABI allows it, quad.py:80 ties them)
+# ------------------------------------------------------------------------------------
+# Set A: every field moved DOWN by 10-35 %; set B: every field moved UP.  No two fields that are neighbours in QrCoeffs
+# (include/quadrotor_hip.h) hold the same value in a set, so that a swap shows.
+COEFF_SETS = {
+    "A": dict(Cx=5.1, CIx=0.08, Cv=0.31, Cb1=4.7, CIb1=0.07, CW=0.47, Cw12=0.52, CW3=0.085, alpha=0.0085, beta=0.041, freq=250,
+              x_lim=0.8, v_lim=3.3, W_lim=5.1, eIx_lim=2.3, eIb1_lim=2.1, euler_lim=62.0, UDM_percentage=17.0,
+              eight_T=7.0, eight_A1=1.2, eight_A2=0.8, eight_w_b1d=0.29, eight_alt_d=-0.5, eight_eps=0.008, eight_count=2.0,
+              m_nominal=1.83, d_nominal=0.19, J1_nominal=0.017, J3_nominal=0.029, c_tf_nominal=0.0112, c_tw_nominal=1.9,
+              g=8.1, min_force=0.4),
+    "B": dict(Cx=7.3, CIx=0.13, Cv=0.52, Cb1=6.9, CIb1=0.12, CW=0.75, Cw12=0.69, CW3=0.125, alpha=0.013, beta=0.062, freq=400,
+              x_lim=1.3, v_lim=4.7, W_lim=7.4, eIx_lim=3.7, eIb1_lim=3.4, euler_lim=88.0, UDM_percentage=4.0,
+              eight_T=11.0, eight_A1=1.8, eight_A2=1.2, eight_w_b1d=0.41, eight_alt_d=-0.75, eight_eps=0.013, eight_count=4.0,
+              m_nominal=2.5, d_nominal=0.27, J1_nominal=0.026, J3_nominal=0.043, c_tf_nominal=0.0162, c_tw_nominal=2.6,
+              g=11.3, min_force=0.65),
+}
+
+
+def oracle_overrides(cs):
+    """A coefficient set as keyword arguments of oracle.quad_oracle.constants (the names of orc.FROM_QUAD_CONSTANTS)."""
+    kw = {orc.FROM_QUAD_CONSTANTS[k]: float(v) for k, v in cs.items() if k in orc.FROM_QUAD_CONSTANTS}
+    kw.update(DT=1.0 / cs["freq"], CW=float(cs["CW"]), EIGHT={k: float(cs["eight_" + k]) for k in orc.EIGHT})
+    return kw
+
+
+def apply_coeffs(env, kind, cs):
+    """Overwrite the instance attributes QuadEnv.__init__ and the wrappers set (quad.py:28-107, coupled:20-24) and redo what
+    __init__ derives from them: reward_min* (quad.py:81-88), and through set_random_parameters('eval') the force limits and
+    forces_to_fM (quad.py:359-404)."""
+    env.m_nominal, env.d_nominal, env.c_tf_nominal, env.c_tw_nominal = cs["m_nominal"], cs["d_nominal"], cs["c_tf_nominal"], cs["c_tw_nominal"]
+    env.J_nominal = np.diag([cs["J1_nominal"], cs["J1_nominal"], cs["J3_nominal"]])
+    env.g, env.freq, env.dt, env.UDM_percentage = cs["g"], cs["freq"], 1.0 / cs["freq"], cs["UDM_percentage"]
+    env.Cx, env.CIx, env.Cv, env.Cb1, env.CIb1, env.CW = cs["Cx"], cs["CIx"], cs["Cv"], cs["Cb1"], cs["CIb1"], cs["CW"]
+    env.reward_min = -np.ceil(env.Cx + env.CIx + env.Cv + env.Cb1 + env.CIb1 + env.CW)
+    if kind == "decoupled":
+        env.Cw12, env.CW3 = cs["Cw12"], cs["CW3"]
+        env.reward_min_1 = -np.ceil(env.Cx + env.CIx + env.Cv + env.Cw12)
+        env.reward_min_2 = -np.ceil(env.Cb1 + env.CW3 + env.CIb1)
+    env.alpha, env.beta, env.eIx_lim, env.eIb1_lim = cs["alpha"], cs["beta"], cs["eIx_lim"], cs["eIb1_lim"]
+    env.x_lim, env.v_lim, env.W_lim, env.euler_lim = cs["x_lim"], cs["v_lim"], cs["W_lim"], cs["euler_lim"]
+    env.set_random_parameters("eval")
+    restore_min_force(env, cs)
+
+
+def restore_min_force(env, cs):
+    """set_random_parameters puts min_force back to 0.5 (quad.py:393) before it forms avrg_act / scale_act (:402-403): set it
+    again and redo those two lines with it, as __init__ forms them (quad.py:40-42)."""
+    env.min_force = cs["min_force"]
+    env.avrg_act = (env.min_force + env.max_force) / 2.0
+    env.scale_act = env.max_force - env.avrg_act
+
+
+def scaled_boundary_states(rng, n, cs):
+    """boundary_states at the set's own thresholds: |x| ~ x_lim, |v| ~ v_lim, |W| ~ W_lim, roll / pitch ~ euler_lim, each within
+    +-2 % of its limit (call inside orc.constants so that the other components are drawn at the set's ranges)."""
+    s = orc.sample_reset_state(rng, n, "train")
+    for i in range(n):
+        which = i % 5
+        eps = rng.uniform(-0.02, 0.02)
+        j = rng.integers(0, 3)
+        sgn = rng.choice([-1.0, 1.0])
+        if which == 0:
+            s[i, 0 + j] = sgn * cs["x_lim"] * (1.0 + eps)
+        elif which == 1:
+            s[i, 3 + j] = sgn * cs["v_lim"] * (1.0 + eps)
+        elif which == 2:
+            s[i, 15 + j] = sgn * cs["W_lim"] * (1.0 + eps)
+        else:
+            ang = np.deg2rad(cs["euler_lim"] * (1.0 + eps))
+            roll, pitch = (sgn * ang, rng.uniform(-0.3, 0.3)) if which == 3 else (rng.uniform(-0.3, 0.3), sgn * ang)
+            s[i, 6:15] = orc.euler_xyz_to_R(roll, pitch, rng.uniform(-np.pi, np.pi)).reshape(9, order="F")
+            s[i, 15:18] *= 0.05
+    return s
+
+
+def done_margin(kind, cs, next_state, obs):
+    """Distance of the nearest deciding quantity of the done rule from its threshold, relative to the limit."""
+    s = next_state
+    if kind == "quad":
+        from scipy.spatial.transform import Rotation
+        eul = Rotation.from_matrix(s[6:15].reshape(3, 3, order="F")).as_euler("xyz", degrees=True)
+        q = np.concatenate([s[0:3] / cs["x_lim"], s[3:6] / cs["v_lim"], s[15:18] / cs["W_lim"], eul[0:2] / cs["euler_lim"]])
+    elif kind == "coupled":
+        o = obs[0].astype(np.float64)
+        q = np.concatenate([o[0:3], o[6:9], o[20:23]])
+    else:
+        o1, o2 = (o.astype(np.float64) for o in obs)
+        q = np.concatenate([o1[0:3], o1[6:9], o1[12:15], o2[2:3]])
+    return np.abs(np.abs(q) - 1.0).min()
+
+
+def gen_onestep_coeffs(name, n=128, seed=0):
+    cs = COEFF_SETS[name]
+    out = {"coeff_names": np.array(sorted(cs)), "coeff_values": np.array([float(cs[k]) for k in sorted(cs)])}
+    with orc.constants(**oracle_overrides(cs)):
+        for kind in orc.KINDS:
+            rng = np.random.default_rng(5000 + seed + 17 * orc.KINDS.index(kind) + 101 * sorted(COEFF_SETS).index(name))
+            A, nag, nb = orc.ACTION_DIM[kind], orc.N_AGENTS[kind], n // 4
+            obs_dims = {"quad": [18], "coupled": [23], "decoupled": [15, 3]}[kind]
+            env = make_env(kind)
+            apply_coeffs(env, kind, cs)
+            d = dict(state=np.zeros((n, 18)), action=np.zeros((n, A)), params=np.zeros((n, 6)), goal=np.zeros((n, 12)), integ=np.zeros((n, 8)),
+                     next_state=np.zeros((n, 18)), f=np.zeros(n), M=np.zeros((n, 3)), reward_raw=np.zeros((n, nag)),
+                     reward=np.zeros((n, nag)), done=np.zeros((n, nag), bool), next_integ=np.zeros((n, 8)))
+            obs_out = [np.zeros((n, k), np.float64 if kind == "quad" else np.float32) for k in obs_dims]
+            redrawn = 0
+            for i in range(n):
+                while True:   # rows nearer than 1e-4 (relative) to a termination threshold are drawn again
+                    st = scaled_boundary_states(rng, 5, cs)[i % 5] if i >= n - nb else orc.sample_reset_state(rng, 1, "train")[0]
+                    st = state_in(st)
+                    a = f32r(rng.uniform(-1, 1, A))
+                    if i % 7 == 0:
+                        a = f32r(np.sign(a))  # saturated commands
+                    prm = f32r(orc.sample_params(rng, 1, "train")[0] if i % 2 else orc.NOMINAL_PARAMS)
+                    goal = random_goal(rng, 1)[0] if i >= n // 2 and i % 4 < 2 or i < n // 2 and i % 4 == 3 else orc.DEFAULT_GOAL.copy()
+                    integ = np.concatenate([rng.uniform(-4.0, 4.0, 3) if i % 5 == 0 else rng.uniform(-1.0, 1.0, 3), rng.uniform(-1.0, 1.0, 3),
+                                            [rng.uniform(-4.0, 4.0) if i % 9 == 0 else rng.uniform(-2.0, 2.0), rng.uniform(-3.0, 3.0)]])
+                    integ = np.zeros(8) if kind == "quad" else f32r(integ)
+                    inject_params(env, prm)
+                    restore_min_force(env, cs)
+                    inject(env, st, goal, integ)
+                    ns, f, M, obs, raw, rwd, done = ref_step(env, kind, a)
+                    if done_margin(kind, cs, ns, obs) >= 1e-4:
+                        break
+                    redrawn += 1
+                d["state"][i], d["action"][i], d["params"][i], d["goal"][i], d["integ"][i] = st, a, prm, goal, integ
+                d["next_state"][i], d["f"][i], d["M"][i] = ns, f, M
+                d["reward_raw"][i], d["reward"][i], d["done"][i] = raw, rwd, done
+                d["next_integ"][i] = read_integ(env)
+                for k, o in enumerate(obs):
+                    obs_out[k][i] = o
+            for k, o in enumerate(obs_out):
+                d[f"obs{k}"] = o
+            for k in ("action", "params", "goal", "integ"):   # float32-representable by construction: stored as float32
+                assert np.array_equal(f32r(d[k]), d[k])
+                d[k] = d[k].astype(np.float32)
+            out.update({f"{kind}_{k}": v for k, v in d.items()})
+            print(f"onestep_coeffs_{name} {kind}: n={n} done-rate={d['done'].mean():.3f} random goals={int((d['goal'] != orc.DEFAULT_GOAL).any(1).sum())} "
+                  f"random params={int((d['params'] != f32r(orc.NOMINAL_PARAMS)).any(1).sum())} redrawn={redrawn}")
+        # get_norm_error_state in both formats (as errobs_formats.npz), from the coupled wrapper: the class does not matter
+        rng = np.random.default_rng(5900 + seed + sorted(COEFF_SETS).index(name))
+        state = state_in(np.concatenate([orc.sample_reset_state(rng, n - n // 4, "train"), scaled_boundary_states(rng, n // 4, cs)]))
+        goal = np.tile(orc.DEFAULT_GOAL, (n, 1)); goal[n // 3:] = random_goal(rng, n)[n // 3:]
+        integ = np.concatenate([rng.uniform(-1.0, 1.0, (n, 6)), rng.uniform(-2.0, 2.0, (n, 1)), rng.uniform(-3.0, 3.0, (n, 1))], 1)
+        integ[::5, 0:3] = rng.uniform(-4.0, 4.0, (len(integ[::5]), 3)); integ[::9, 6] = rng.uniform(-4.0, 4.0, len(integ[::9]))
+        integ = f32r(integ)
+        out.update(errobs_state=state, errobs_goal=goal.astype(np.float32), errobs_integ=integ.astype(np.float32))
+        env = make_env("coupled")
+        apply_coeffs(env, "coupled", cs)
+        for fw, dims in (("MONO", [23]), ("MODUL", [15, 3])):
+            obs = [np.zeros((n, k), np.float32) for k in dims]
+            nxt = np.zeros((n, 8))
+            for i in range(n):
+                inject(env, state[i], goal[i], integ[i])
+                o = env.get_norm_error_state(fw)
+                for k in range(len(dims)):
+                    obs[k][i] = o[k]
+                nxt[i] = read_integ(env)
+            for k in range(len(dims)):
+                out[f"errobs_{fw}_obs{k}"] = obs[k]
+            out[f"errobs_{fw}_next_integ"] = nxt
+    np.savez_compressed(os.path.join(OUT, f"onestep_coeffs_{name}.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if ARGV[:1] == ["td3"]:  # f3: the shipped TD3-EMLP actors in the loop (needs tools/_plum_shim)
@@ -874,6 +1041,10 @@ if __name__ == "__main__":
         init_x = {2: [0.1, -0.15, -0.3], 3: [-0.2, 0.1, -0.6], 4: [0.3, 0.2, -0.1], 5: [-0.1, 0.05, -0.2]}
         for fw in ("MODUL", "MONO"):
             gen_closedloop_td3(fw, shipped[fw], rep, modes=((2, 1300), (3, 500), (4, 300), (5, 6900)), suffix="_modes2345", init_x=init_x)
+        sys.exit(0)
+    if ARGV[:1] == ["coeffs"]:  # every runtime coefficient off its default, two sets
+        for name in sorted(COEFF_SETS):
+            gen_onestep_coeffs(name)
         sys.exit(0)
     if ARGV[:1] == ["errobs"]:  # only get_norm_error_state(framework) in both formats on both wrapper classes
         gen_errobs_formats()

@@ -656,6 +656,36 @@ template <> struct KindTraits<QR_KIND_QUAD>      { static constexpr int A = 4, D
 template <> struct KindTraits<QR_KIND_COUPLED>   { static constexpr int A = 4, D0 = 23, D1 = 0, NAG = 1; };
 template <> struct KindTraits<QR_KIND_DECOUPLED> { static constexpr int A = 5, D0 = 15, D1 = 3, NAG = 2; };
 
+// Half one of store_rows for all of a kind's observation rows: this thread's row(s) into the tile(s) (Decoupled: both agents').
+template <int KIND>
+__device__ __forceinline__ void obs_to_lds(const float (&o0)[KindTraits<KIND>::D0], const float (&o1)[KindTraits<KIND>::D1 ? KindTraits<KIND>::D1 : 1],
+                                           float* tile0, float* tile1, int tid) {
+  rows_to_lds<KindTraits<KIND>::D0>(o0, tile0, tid);
+  if constexpr (KindTraits<KIND>::D1 > 0) rows_to_lds<KindTraits<KIND>::D1>(o1, tile1, tid);
+}
+
+// Quad-v0's observation: the state in the reference's order (x, v, vec_F(R), W), as float32 or float64 rows
+template <typename O, typename X, typename TR, typename TW>
+__device__ __forceinline__ void quad_state_row(const X (&x)[3], const X (&v)[3], const TR (&R)[9], const TW (&W)[3], O (&o)[18]) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { o[j] = (O)x[j]; o[3 + j] = (O)v[j]; o[15 + j] = (O)W[j]; }
+#pragma unroll
+  for (int j = 0; j < 9; ++j) o[6 + j] = (O)R[j];
+}
+
+// One action row of rows [.][A] -> lane registers.  A = 4: one 16-byte load per lane.  A = 5: five dword
+// loads per lane (a wave covers 1280 contiguous bytes; L1 merges the sectors).
+template <int A>
+__device__ __forceinline__ void load_action_row(const float* abase, unsigned lane, float (&dst)[A]) {
+  if constexpr (A == 4) {
+    const float4 v = reinterpret_cast<const float4*>(abase)[lane];
+    dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < A; ++j) dst[j] = abase[lane * A + j];
+  }
+}
+
 // What the action map needs of the env's PARAMETERS only (quad.py:389-404 and the reciprocals): constant between two resets of an
 // env, so a rollout forms it once per episode instead of once per env-step (~35 instructions, a v_rcp_f64 among them, off the
 // stepping wave's path per step).  The same expressions on the same float32 parameter words as a one-step launch: the same bits.

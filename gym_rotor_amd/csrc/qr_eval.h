@@ -80,8 +80,7 @@ __global__ __launch_bounds__(64, 1) void eval_kernel(const EvalLaunch in) {
 #pragma unroll
     for (int f = 0; f < 8; ++f) w.integ[f] = integ.load(f, ufirst, ll);
   }
-#pragma unroll
-  for (int f = 0; f < 12; ++f) w.goal[f] = f == 6 ? 1.0f : 0.0f;  // hover default (quad.py:98-101)
+  hover_goal(w.goal);
   if ((!TRAJ || kStateful) && ka.goal != nullptr) {  // (stateless generator modes form the goal in registers every step)
     const SoA<float> goal(ka.goal, 12, L);
 #pragma unroll
@@ -145,25 +144,14 @@ __global__ __launch_bounds__(64, 1) void eval_kernel(const EvalLaunch in) {
     integrate_sel<MAG>(w.x, w.v, w.q, w.W, dyn, nsub, T(c.dt) * recip(T(nsub)));
     renorm_quat(w.q);
 
-    // ---- observation, reward, done (step_kernel's wrapper branch) ----
+    // ---- observation, reward, done (as step_kernel's wrapper branch) ----
     T R[9];
     float o0[D0], o1[D1];
-    float rwd[NAG];
+    float rraw[NAG], rwd[NAG];
     bool dn[NAG];
     quat_to_R(w.q, R);
     error_obs<KIND, T, X>(w, R, c, o0, o1);
-    if constexpr (KIND == QR_KIND_COUPLED) {  // coupled:78-110
-      const float r = -c.Cx * sq3(&o0[0]) + -c.CIx * sq3(&o0[3]) + -c.Cv * sq3(&o0[6]) +
-                      -c.Cb1 * fabsf(o0[18]) + -c.CIb1 * (o0[19] * o0[19]) + -c.CW * sq3(&o0[20]);
-      rwd[0] = interp01(r, c.rmin_mono, c.inv_nrmin_mono);
-      dn[0] = out3(&o0[0]) | out3(&o0[6]) | out3(&o0[20]);
-    } else {  // decoupled:92-140
-      const float r1 = -c.Cx * sq3(&o0[0]) + -c.CIx * sq3(&o0[3]) + -c.Cv * sq3(&o0[6]) + -c.Cw12 * sq3(&o0[12]);
-      const float r2 = -c.Cb1 * fabsf(o1[0]) + -c.CIb1 * (o1[1] * o1[1]) + -c.CW3 * (o1[2] * o1[2]);
-      rwd[0] = interp01(r1, c.rmin_1, c.inv_nrmin_1); rwd[NAG - 1] = interp01(r2, c.rmin_2, c.inv_nrmin_2);
-      dn[0] = out3(&o0[0]) | out3(&o0[6]) | out3(&o0[12]);
-      dn[NAG - 1] = !(fabsf(o1[2]) < 1.0f);
-    }
+    wrapper_reward_done<KIND>(o0, o1, c, rraw, rwd, dn);
     bool any_done = false;
 #pragma unroll
     for (int g = 0; g < NAG; ++g) {

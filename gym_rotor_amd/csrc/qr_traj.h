@@ -219,6 +219,29 @@ __device__ __forceinline__ float sq3(const float* v) { return v[0] * v[0] + v[1]
 __device__ __forceinline__ bool out3(const float* v) { return !(fabsf(v[0]) < 1.0f) | !(fabsf(v[1]) < 1.0f) | !(fabsf(v[2]) < 1.0f); }
 __device__ __forceinline__ float interp01(float r, float rmin, float inv_nrmin) { return clampT((r - rmin) * inv_nrmin, 0.0f, 1.0f); }
 
+// The wrappers' reward and termination, per agent, from the float32 observation rows — float32 arithmetic on the float32 obs:
+// the raw reward, its np.interp normalisation and the done flag.  (The crash override is the caller's.)
+template <int KIND>
+__device__ __forceinline__ void wrapper_reward_done(const float (&o0)[KindTraits<KIND>::D0], const float (&o1)[KindTraits<KIND>::D1 ? KindTraits<KIND>::D1 : 1],
+                                                    const Coeffs& c, float (&rraw)[KindTraits<KIND>::NAG], float (&rwd)[KindTraits<KIND>::NAG],
+                                                    bool (&dn)[KindTraits<KIND>::NAG]) {
+  constexpr int NAG = KindTraits<KIND>::NAG;
+  if constexpr (KIND == QR_KIND_COUPLED) {  // coupled:78-110
+    const float r = -c.Cx * sq3(&o0[0]) + -c.CIx * sq3(&o0[3]) + -c.Cv * sq3(&o0[6]) +
+                    -c.Cb1 * fabsf(o0[18]) + -c.CIb1 * (o0[19] * o0[19]) + -c.CW * sq3(&o0[20]);
+    rraw[0] = r;
+    rwd[0] = interp01(r, c.rmin_mono, c.inv_nrmin_mono);
+    dn[0] = out3(&o0[0]) | out3(&o0[6]) | out3(&o0[20]);
+  } else {  // decoupled:92-140
+    const float r1 = -c.Cx * sq3(&o0[0]) + -c.CIx * sq3(&o0[3]) + -c.Cv * sq3(&o0[6]) + -c.Cw12 * sq3(&o0[12]);
+    const float r2 = -c.Cb1 * fabsf(o1[0]) + -c.CIb1 * (o1[1] * o1[1]) + -c.CW3 * (o1[2] * o1[2]);
+    rraw[0] = r1; rraw[NAG - 1] = r2;
+    rwd[0] = interp01(r1, c.rmin_1, c.inv_nrmin_1); rwd[NAG - 1] = interp01(r2, c.rmin_2, c.inv_nrmin_2);
+    dn[0] = out3(&o0[0]) | out3(&o0[6]) | out3(&o0[12]);
+    dn[NAG - 1] = !(fabsf(o1[2]) < 1.0f);
+  }
+}
+
 // ---- SoA access through buffer resources ------------------------------------------------
 // Field f of env (first + lane) of a [F][L] buffer lives at byte (f*L + first + lane)*sizeof(E).
 // `first` and L are wave-uniform, so the access is issued as
@@ -259,6 +282,12 @@ struct SoA {
     }
   }
 };
+
+// the goal of an env without a goal buffer: hover at the origin, b1d = e1 (quad.py:98-101)
+__device__ __forceinline__ void hover_goal(float (&goal)[12]) {
+#pragma unroll
+  for (int f = 0; f < 12; ++f) goal[f] = f == 6 ? 1.0f : 0.0f;
+}
 
 // ---- attitude in memory: "smallest three" ---------------------------------------------------
 // The step is bound by bytes, so the unit quaternion is stored as THREE components: the one of
@@ -362,8 +391,7 @@ __device__ __forceinline__ void idle_work(Work<T, X>& w, const Coeffs& c) {  // 
   for (int f = 0; f < 3; ++f) { w.x[f] = X(0); w.v[f] = X(0); w.W[f] = T(0); }
 #pragma unroll
   for (int f = 0; f < 4; ++f) w.q[f] = T(f == 0 ? 1 : 0);
-#pragma unroll
-  for (int f = 0; f < 12; ++f) w.goal[f] = f == 6 ? 1.0f : 0.0f;
+  hover_goal(w.goal);
 #pragma unroll
   for (int f = 0; f < 8; ++f) w.integ[f] = 0.0f;
 #pragma unroll

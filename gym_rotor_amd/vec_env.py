@@ -907,14 +907,14 @@ class QuadVecEnv:
                                 goal, action_source, variant)
 
     def _has_both_step_launches(self) -> bool:
-        """Does qr_step have a helper-wave AND a plain instantiation for this env?  (quadrotor_kernels.hip: wants_helper /
+        """Does qr_step have a helper-wave AND a plain instantiation for this env?  (qr_launch.h: wants_helper /
         wants_helper_traj — in-launch resets, the default layout, external goals or the stateless generator modes.)"""
         return self.auto_reset and self.layout == "mixed" and self.goal_mode in (None, 0, 1, 6)
 
     def _effective_step_threshold(self) -> int:
         """The tile count up to which step() of THIS env takes the helper-wave launch under the compiled rule: the process'
         thresholds (qr_launch_thresholds) with the launcher's own reductions for >= 2 substeps and the fused goal generator
-        (quadrotor_kernels.hip: wants_helper / wants_helper_traj)."""
+        (qr_launch.h: wants_helper / wants_helper_traj)."""
         thr = _lib.launch_thresholds()
         if self.kind == "quad":
             return thr["step_quad"] if (self.substeps <= 1 and self.goal_mode is None) else min(thr["step_quad"], 2560)

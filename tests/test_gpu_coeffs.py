@@ -487,7 +487,7 @@ def test_launch_rule_follows_w_lim(kind):
     (wants_adapt).  W_lim = 5.1: the plain kernel.  W_lim = 4 pi: the rate-adaptive one, and while every env is in regime (|W|
     below w_adapt; the envs are re-sampled at 4 pi) its results are the plain kernel's (w_adapt = 0):
     * qr_rollout_actor (the wrappers): bit for bit — in regime it runs the plain kernel's code path;
-    * qr_rollout on given actions: the rate-adaptive instantiation forms its quaternion stages in delta form (quadrotor_kernels.hip:
+    * qr_rollout on given actions: the rate-adaptive instantiation forms its quaternion stages in delta form (qr_step.h:
       kDelta), so not the same bits; the bars of test_adaptive_kernel_in_regime's free run apply until the first differing done flag
       (after it the two runs re-sample different envs)."""
     from gym_rotor_amd.constants import QuadConstants

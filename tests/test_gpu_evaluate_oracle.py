@@ -17,7 +17,7 @@ KINDS = ("coupled", "decoupled")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the table: which instantiation a case launches, by the launcher's rule restated (launch_eval_kind in quadrotor_kernels.hip)
+# the table: which instantiation a case launches, by the launcher's rule restated (launch_eval_kind in qr_launch.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def instance_of(kind, layout, substeps, goal_mode):
     """(kind, layout, TRAJ, MAG): TRAJ 0 without a goal mode, 1 for the stateless modes 0 / 1 / 6, 2 for the stateful 2-5; Magnus

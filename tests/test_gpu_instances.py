@@ -1,4 +1,4 @@
-"""Every step_kernel instantiation the library holds (175: quadrotor_kernels.hip QR_INSTANCES x MAG) is reachable through the public API,
+"""Every step_kernel instantiation the library holds (175: qr_launch.h QR_INSTANCES x MAG) is reachable through the public API,
 runs, and agrees with the float64 layout's instantiation of the same workload — and the process' launch counters (qr_launch_stats)
 show that all of them were really launched ("nothing records which instantiations the GPU tests launch").
 Also here: qr_touch, the do-nothing kernel bench.py prices a step against."""

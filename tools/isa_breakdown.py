@@ -4,7 +4,7 @@
 Builds the device code with full debug info (one env kind, default layout: ~10 s), disassembles ONE instantiation and asks
 llvm-symbolizer for the inline stack of every instruction address.  Each instruction is attributed to
   * the SECTION of step_kernel it was inlined into: the `//@sec <name>` marker comment nearest above the step_kernel line of its
-    outermost frame (quadrotor_kernels.hip), and
+    outermost frame (qr_step.h), and
   * the function called directly from step_kernel at that point (integrate, action_map, quad_done, store_state, ...).
 Static counts; the per-env-step loop of a multi-step instantiation and the substep loop are marked by their sections.
 
@@ -20,7 +20,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-SRC = os.path.join(ROOT, "gym_rotor_amd", "csrc", "quadrotor_kernels.hip")
+SRC = os.path.join(ROOT, "gym_rotor_amd", "csrc", "quadrotor_kernels.hip")   # the translation unit
+STEP_SRC = os.path.join(ROOT, "gym_rotor_amd", "csrc", "qr_step.h")        # step_kernel and its //@sec markers
 
 p = argparse.ArgumentParser()
 p.add_argument("--kind", type=int, default=0)
@@ -69,7 +70,7 @@ blocks = [b for b in sy.split("\n\n") if b.strip()]
 assert len(blocks) == len(insts), (len(blocks), len(insts))
 
 # section markers of step_kernel
-src = open(SRC).read().splitlines()
+src = open(STEP_SRC).read().splitlines()
 sec_at, cur = {}, "prologue"
 for n, l in enumerate(src, 1):
     m = re.search(r"//@sec\s+(\S+)", l)
@@ -95,7 +96,7 @@ for (addr, op), b in zip(insts, blocks):
     sec, callee = "?", "(step_kernel)"
     for k in range(len(frames) - 1, -1, -1):
         fn, loc = frames[k]
-        if "step_kernel" in fn and "quadrotor_kernels.hip" in loc:
+        if "step_kernel" in fn and "qr_step.h" in loc:
             ln = int(loc.split(":")[-2])
             sec = sec_at.get(ln, "?")
             if k > 0:

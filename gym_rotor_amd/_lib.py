@@ -31,7 +31,7 @@ ERRORS = {-1: "QR_E_NULL: a required pointer is NULL", -2: "QR_E_KIND: bad env k
 SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_error_obs_format", "qr_reset", "qr_get_state", "qr_set_state", "qr_check_state",
            "qr_traj_start", "qr_get_desired", "qr_gae",
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
-           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor")
+           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population")
 
 
 class QrCoeffs(C.Structure):
@@ -79,6 +79,10 @@ class QrEvalOut(C.Structure):
                 ("success", C.c_void_p), ("final_error", C.c_void_p), ("obs0", C.c_void_p), ("obs1", C.c_void_p)]
 
 
+class QrPopulation(C.Structure):
+    _fields_ = [("n_policies", C.c_int32), ("envs_per_policy", C.c_int32)]
+
+
 class QrLaunchPlan(C.Structure):
     _fields_ = [("grid", C.c_int32), ("block", C.c_int32), ("launches", C.c_int32),
                 ("traj", C.c_int32), ("adapt", C.c_int32), ("policy", C.c_int32), ("single", C.c_int32), ("help", C.c_int32), ("hrew", C.c_int32),
@@ -118,6 +122,8 @@ def load():
     lib.qr_rollout_actor.argtypes = [P(QrEnv), P(QrPolicyRollout), C.c_int32, C.c_int32, P(QrStepOut), C.c_void_p]
     lib.qr_evaluate_actor.restype = C.c_int
     lib.qr_evaluate_actor.argtypes = [P(QrEnv), P(QrPolicyRollout), C.c_int32, C.c_int32, P(QrEvalOut), C.c_void_p]
+    lib.qr_evaluate_population.restype = C.c_int
+    lib.qr_evaluate_population.argtypes = [P(QrEnv), P(QrPolicyRollout), P(QrPopulation), C.c_int32, C.c_int32, P(QrEvalOut), C.c_void_p]
     lib.qr_error_obs.restype = C.c_int
     lib.qr_error_obs.argtypes = [P(QrEnv), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.qr_error_obs_format.restype = C.c_int

@@ -19,11 +19,26 @@ struct EvalArgs {
   uint8_t* success;     // [N][NAG] main.py:366-373 (length == max_steps and |ex|_inf <= 0.01; MODUL agent 1: |eb1| <= 0.01)
   float* final_error;   // [N][4]   ex, eb1 of the last step; may be NULL
   int32_t max_steps;
+  // qr_evaluate_population: the env batch is P blocks of tiles_per_policy 64-env tiles, one policy each, of which the first
+  // envs_per_policy envs are flown.  qr_evaluate_actor is P = 1: the host fills in N and the whole grid (do_evaluate).
+  int32_t envs_per_policy;
+  int32_t tiles_per_policy;
 };
 struct EvalLaunch {
   Args a;
   EvalArgs e;
 };
+
+// Policy p's copy of an actor whose tensors are stacked [P][...] (contiguous; the pointers are policy 0's): every tensor starts
+// p * numel elements later.  The log_std sources stay as the host left them for an evaluation: cleared, never read.
+template <int D, int H, int A>
+__device__ __forceinline__ ActorW actor_of_policy(const ActorW& w, unsigned p) {
+  ActorW o = w;
+  o.fc1_w += p * unsigned(H * D); o.fc1_b += p * unsigned(H);
+  o.fc2_w += p * unsigned(H * H); o.fc2_b += p * unsigned(H);
+  o.mean_w += p * unsigned(A * H); o.mean_b += p * unsigned(A);
+  return o;
+}
 
 // One lane = one env, one 64-lane wave = one tile, as in step_kernel's POLICY path without a helper wave — and with its arithmetic:
 // the deterministic action of the actor(s) on the current observation (MFMA actor; Decoupled agent 1 per lane from LDS), the fused
@@ -31,7 +46,8 @@ struct EvalLaunch {
 // done and the crash override, then pack / unpack of the attitude as every multi-step launch does between env-steps.  No per-step
 // row is written and nothing is ever re-sampled.  A lane FREEZES at the first step that sets any agent's done flag (or at max_steps):
 // it writes its state, integrators, generator state, final rows and results back right there, once, and its registers are dead from
-// then on.  The wave keeps feeding them through the actor — the MFMAs need the whole wave — and discards what comes out; it leaves
+// then on.  A tile belongs to ONE policy (EvalArgs: policy = tile / tiles_per_policy, wave-uniform, formed once in the prologue): it
+// loads that policy's weights and flies the block's first envs_per_policy envs; the padding envs behind them are never live.  The wave keeps feeding them through the actor — the MFMAs need the whole wave — and discards what comes out; it leaves
 // the loop as soon as no lane is live (a ballot: the loop condition stays wave-uniform), so a crashing policy costs only as many
 // steps as its longest-surviving env.  Frozen lanes fly on unaccounted; nothing they compute reaches memory or another lane (each
 // env is one column of the actor's GEMMs).  Every evaluated step starts in regime (the lane stops at the first observation with
@@ -61,9 +77,10 @@ __global__ __launch_bounds__(64, 1) void eval_kernel(const EvalLaunch in) {
   const unsigned ufirst = blockIdx.x * 64u;
   const int64_t first = (int64_t)ufirst;
   const int64_t i = first + tid;
-  const int n_envs = (int)ka.n;
   const int64_t L = ka.ld;
-  const int rows = min(n_envs - (int)ufirst, 64);
+  const unsigned tpp = (unsigned)ke.tiles_per_policy;
+  const unsigned policy = blockIdx.x / tpp;  // wave-uniform
+  const int rows = min(ke.envs_per_policy - (int)((blockIdx.x - policy * tpp) * 64u), 64);
   const bool active = tid < rows;
   const unsigned ll = min(lane, (unsigned)(rows - 1));  // lanes past a ragged tail read the tail's last env and are never live
   const Coeffs& c = ka.c;
@@ -99,8 +116,8 @@ __global__ __launch_bounds__(64, 1) void eval_kernel(const EvalLaunch in) {
   ActorMfma<D0, true> actor0;  // (the host clears the log_std sources: only the mean head is formed)
   load_rows<64, D0>(ka.obs0_in + first * D0, po0, smem, tid, rows);
   if constexpr (KT::D1 > 0) load_rows<64, D1>(ka.obs1_in + first * D1, po1, smem, tid, rows);
-  actor0.load(ka.actor[0], tid);
-  if constexpr (KT::D1 > 0) Actor1::fill(wsm, ka.actor[1], tid);
+  actor0.load(actor_of_policy<D0, 16, 4>(ka.actor[0], policy), tid);
+  if constexpr (KT::D1 > 0) Actor1::fill(wsm, actor_of_policy<3, 4, 1>(ka.actor[1], policy), tid);
   tile_sync<64>();
 
   bool live = active;

@@ -392,7 +392,7 @@ static int do_rollout(const QrEnv* env, const float* action, const QrPolicyRollo
 // qr_evaluate_actor: eval_kernel over the whole grid, one 64-env tile per workgroup.  Instantiations: both wrappers x TRAJ 0 / 1 / 2 x
 // (default layout: RK4 and Magnus; uniform layouts: RK4) = 24, none of them a step_kernel (not in QR_INSTANCES, not counted by
 // qr_launch_stats).  The integrator follows pick_instance's rule for a plain actor rollout: Magnus for two or more substeps in the
-// default layout.
+// default layout.  qr_evaluate_population launches the same kernels: which policy a tile flies is data (EvalArgs), not an instantiation.
 template <int KIND, typename XV, typename QW>
 static void launch_eval_kind(const EvalLaunch& k, hipStream_t s) {
   constexpr bool kMixed = std::is_same<XV, float>::value && std::is_same<QW, double>::value;
@@ -427,12 +427,21 @@ static int launch_eval(const EvalLaunch& k, int kind, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-static int do_evaluate(const QrEnv* env, const QrPolicyRollout* pol, int32_t max_steps, int32_t substeps, const QrEvalOut* out,
-                       void* stream) {
+// `pop` == NULL: qr_evaluate_actor, one policy over all N envs.  Otherwise qr_evaluate_population's block layout (quadrotor_hip.h).
+static int do_evaluate(const QrEnv* env, const QrPolicyRollout* pol, const QrPopulation* pop, int32_t max_steps, int32_t substeps,
+                       const QrEvalOut* out, void* stream) {
   EvalLaunch k{};
   Args& a = k.a;
   if (int rc = fill_env(a, env)) return rc;
   if (!pol || !out) return QR_E_NULL;
+  const int64_t tiles = (a.n + 63) / 64;
+  k.e.envs_per_policy = (int32_t)a.n; k.e.tiles_per_policy = (int32_t)(tiles > 0 ? tiles : 1);
+  if (pop) {
+    if (pop->n_policies < 1 || pop->envs_per_policy < 1) return QR_E_SIZE;
+    const int64_t tpp = ((int64_t)pop->envs_per_policy + 63) / 64;
+    if (a.n != (int64_t)pop->n_policies * tpp * 64) return QR_E_SIZE;
+    k.e.envs_per_policy = pop->envs_per_policy; k.e.tiles_per_policy = (int32_t)tpp;
+  }
   if (env->kind == QR_KIND_QUAD) return QR_E_KIND;
   if (substeps < 1 || max_steps < 1) return QR_E_SIZE;
   if (!env->integ || !pol->actors || !pol->obs0_in || !out->obs0 || !out->episode_return || !out->benchmark || !out->length ||

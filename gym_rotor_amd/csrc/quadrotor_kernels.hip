@@ -40,7 +40,7 @@
 //   qr_traj.h      goal generator (trajectory_generator.py modes 0/1/6), SoA buffer accessor
 //   qr_actor.h     PPO actor (MFMA / LDS forms), action sampling
 //   qr_step.h      launch thresholds, Quad-v0 reward / termination, the helper wave, step_kernel (step / rollout)
-//   qr_eval.h      batched policy evaluation (qr_evaluate_actor): eval_kernel
+//   qr_eval.h      batched policy evaluation (qr_evaluate_actor, qr_evaluate_population): eval_kernel
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
@@ -103,7 +103,13 @@ int qr_rollout_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t n_
 
 int qr_evaluate_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t max_steps, int32_t substeps, const QrEvalOut* out,
                       void* stream) {
-  return qr::do_evaluate(env, policy, max_steps, substeps, out, stream);
+  return qr::do_evaluate(env, policy, nullptr, max_steps, substeps, out, stream);
+}
+
+int qr_evaluate_population(const QrEnv* env, const QrPolicyRollout* policy, const QrPopulation* pop, int32_t max_steps,
+                           int32_t substeps, const QrEvalOut* out, void* stream) {
+  if (!pop) return QR_E_NULL;
+  return qr::do_evaluate(env, policy, pop, max_steps, substeps, out, stream);
 }
 
 int qr_error_obs_format(const QrEnv* env, int32_t format, float* obs0, float* obs1, void* stream) {

@@ -82,3 +82,101 @@ def evaluate_policy(kind: str, actors: Sequence, num_episodes: int, traj_mode: O
     obs = env.get_norm_error_state()
     out = env.evaluate(actors, max_steps=int(round(eval_seconds / env.dt)), obs=obs, max_action=max_action)
     return EvalResult.from_dict(out)
+
+
+@dataclass
+class PopulationResult:
+    """Per-episode results of a population evaluation.  `flat` holds the per-env tensors of `QuadVecEnv.evaluate_population`
+    ([N, ...], N = P * Epad, padding rows included); the attributes below are their [P, E, ...] VIEWS with the padding sliced
+    off.  `result[p]` is the `EvalResult` of policy p."""
+    flat: dict
+    n_policies: int
+    envs_per_policy: int
+
+    def _view(self, key):
+        from .policy import population_view
+        t = self.flat.get(key)
+        return None if t is None else population_view(t, self.n_policies, self.envs_per_policy)
+
+    episode_return = property(lambda self: self._view("episode_return"))   # [P, E, n_agents] float64
+    benchmark = property(lambda self: self._view("benchmark"))             # [P, E] float64
+    length = property(lambda self: self._view("length"))                   # [P, E] int32
+    terminated = property(lambda self: self._view("terminated"))           # [P, E] bool
+    success = property(lambda self: self._view("success"))                 # [P, E, n_agents] bool
+    final_error = property(lambda self: self._view("final_error"))         # [P, E, 4] float32
+
+    def __len__(self) -> int:
+        return self.n_policies
+
+    def __getitem__(self, p: int) -> EvalResult:
+        fe = self.final_error
+        return EvalResult(self.episode_return[p], self.benchmark[p], self.length[p], self.terminated[p], self.success[p],
+                          None if fe is None else fe[p])
+
+    def per_policy(self) -> dict:
+        """The means over each policy's E episodes (float64, unrounded; one [P, E] torch reduction each): episode_return
+        [P, n_agents] (summary()'s eval_reward), benchmark [P] (benchmark_reward), success [P, n_agents] (success_rate), length [P]
+        (mean_length), terminated [P] (terminated_fraction)."""
+        return {"episode_return": self.episode_return.double().mean(1), "benchmark": self.benchmark.double().mean(1),
+                "success": self.success.double().mean(1), "length": self.length.double().mean(1),
+                "terminated": self.terminated.double().mean(1)}
+
+    def best(self, key: str = "benchmark") -> int:
+        """Index of the policy with the largest per_policy()[key] (summed over the agents where there are two; the first one on
+        a tie)."""
+        v = self.per_policy()[key]
+        if v.dim() > 1:
+            v = v.sum(1)
+        return int(torch.argmax(v))
+
+
+def evaluate_population(kind: str, population, episodes_per_policy: int, traj_mode: Optional[int] = 0, seed: int = 1992,
+                        eval_seconds: float = 5.0, common_episodes: bool = True, device="cuda", substeps: int = 1,
+                        layout: str = "mixed", env_offset: int = 0, max_action: float = 1.0) -> PopulationResult:
+    """`evaluate_policy` for the P policies of a `policy.ActorPopulation` in ONE launch (`QuadVecEnv.evaluate_population`): policy
+    p flies E = `episodes_per_policy` episodes on its own block of an env of P * roundup(E, 64) envs.
+
+    common_episodes=True (common random numbers): the E episodes are prepared ONCE on an E-env env exactly as evaluate_policy
+    prepares them — reset(env_type='eval', seed), mark_traj_start + get_desired(store_goal=True) with a fused generator, the first
+    observation — and that state (state, parameters, integrators, goal, generator state, observation rows) is copied into every
+    policy's block.  Policy p's results are then those of evaluate_policy(kind, population[p], E, ...), episode by episode, and
+    two policies are compared on the same episodes: a paired comparison.
+    common_episodes=False: the big env is reset as a whole, so every episode of every policy has its own draws.
+
+    Sharding is by slicing the population: each rank evaluates `population.select(slice)` (with the same seed and, for common
+    episodes, the same env_offset) and keeps its own PopulationResult; there is nothing to reduce across ranks until the caller
+    compares per_policy() figures."""
+    from .policy import population_layout, population_tile
+    if kind == "quad":
+        raise ValueError("evaluate_population needs kind 'coupled' or 'decoupled' (Quad-v0 has no actor)")
+    P, E = len(population), int(episodes_per_policy)
+    _, n = population_layout(P, E)
+
+    def prepared(num_envs):
+        env = QuadVecEnv(kind, num_envs, device=device, seed=seed, substeps=substeps, layout=layout, goal_mode=traj_mode,
+                         env_offset=env_offset, autotune=False)
+        env.reset("eval", seed=seed)
+        if traj_mode is not None:
+            env.get_desired(store_goal=True)
+        return env, env.get_norm_error_state()
+
+    if common_episodes:
+        src, src_obs = prepared(E)
+        env = QuadVecEnv(kind, n, device=device, seed=seed, substeps=substeps, layout=layout, goal_mode=traj_mode,
+                         env_offset=env_offset, autotune=False)
+        for name in ("_pos_vel", "_att_rate", "_integ", "_params", "_goal", "_traj"):   # SoA [fields, N]
+            s, d = getattr(src, name), getattr(env, name)
+            if s is None:
+                continue
+            if d is None:   # (the goal buffer of a stateless generator mode exists from get_desired(store_goal=True) on)
+                d = env._soa(s.shape[0], s.dtype)
+                setattr(env, name, d)
+            population_tile(s, P, E, d, env_dim=1)
+        env._sync_structs()
+        population_tile(src._episode, P, E, env._episode)
+        src_obs = [src_obs] if isinstance(src_obs, torch.Tensor) else list(src_obs)
+        obs = [population_tile(o, P, E, torch.zeros(n, o.shape[1], dtype=o.dtype, device=o.device)) for o in src_obs]
+    else:
+        env, obs = prepared(n)
+    out = env.evaluate_population(population, E, max_steps=int(round(eval_seconds / env.dt)), obs=obs, max_action=max_action)
+    return PopulationResult(out, P, E)

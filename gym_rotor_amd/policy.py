@@ -131,3 +131,169 @@ def random_actors(kind: str, device, generator=None, log_std: float = 0.0, algo:
             a.log_std_b = torch.full((adim,), float(log_std), device=device)
             a.log_std, a.squash = None, _lib.ACTOR_TANH_SAMPLE
     return actors
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# a population of policies for QuadVecEnv.evaluate_population (qr_evaluate_population)
+# ----------------------------------------------------------------------------------------------------------------
+def population_layout(n_policies: int, envs_per_policy: int):
+    """(Epad, N) of qr_evaluate_population's block layout: P policies of E episodes each live on ONE env of N = P * Epad envs,
+    Epad = E rounded up to a multiple of 64 (a 64-env tile never holds two policies).  Policy p owns envs [p Epad, p Epad + E)."""
+    P, E = int(n_policies), int(envs_per_policy)
+    if P < 1 or E < 1:
+        raise ValueError("a population needs n_policies >= 1 and envs_per_policy >= 1")
+    epad = (E + 63) // 64 * 64
+    return epad, P * epad
+
+
+def population_env_index(n_policies: int, envs_per_policy: int, device=None) -> torch.Tensor:
+    """int64 [P, E]: the env that flies episode e of policy p (p * Epad + e) — the live envs, in block order."""
+    epad, _ = population_layout(n_policies, envs_per_policy)
+    return torch.arange(n_policies, device=device)[:, None] * epad + torch.arange(envs_per_policy, device=device)[None, :]
+
+
+def population_view(t: torch.Tensor, n_policies: int, envs_per_policy: int, env_dim: int = 0) -> torch.Tensor:
+    """The [.., P, E, ..] view of a tensor whose dimension `env_dim` runs over the N = P * Epad envs: the padding sliced off,
+    no copy."""
+    epad, n = population_layout(n_policies, envs_per_policy)
+    env_dim = env_dim % t.dim()
+    if t.shape[env_dim] != n:
+        raise ValueError(f"dimension {env_dim} has {t.shape[env_dim]} entries, the population layout {n} = {n_policies} x {epad}")
+    return t.unflatten(env_dim, (n_policies, epad)).narrow(env_dim + 1, 0, envs_per_policy)
+
+
+def population_tile(block: torch.Tensor, n_policies: int, envs_per_policy: int, out: torch.Tensor, env_dim: int = 0) -> torch.Tensor:
+    """Copy `block` — E entries along `env_dim`, the prepared state of E episodes — into every policy's block of `out` (N entries
+    along `env_dim`).  The padding envs of `out` keep what they hold."""
+    env_dim = env_dim % out.dim()
+    if block.dim() != out.dim() or block.shape[env_dim] != envs_per_policy:
+        raise ValueError(f"the block has {block.shape[env_dim]} entries along dimension {env_dim}, not {envs_per_policy}")
+    population_view(out, n_policies, envs_per_policy, env_dim).copy_(block.unsqueeze(env_dim))
+    return out
+
+
+_WEIGHTS = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mean_w", "mean_b")
+
+
+class ActorPopulation:
+    """P policies of one form as stacked tensors: per agent ONE `ActorParams` whose tensors carry a leading [P] dimension
+    (contiguous float32), which is how qr_evaluate_population reads them — the pointers are policy 0's, policy p's tensor starts
+    p * numel elements later.  `len(pop)` is P; `pop[p]` are the ordinary per-agent ActorParams VIEWS of policy p (no copy:
+    `evaluate` and `rollout_actor` take them as they are, and an in-place update of the stack is seen through them)."""
+
+    def __init__(self, agents: Sequence[ActorParams]):
+        self.agents = list(agents)
+        if not self.agents:
+            raise ValueError("a population needs at least one agent")
+        sizes = {getattr(a, n).shape[0] for a in self.agents for n in ActorParams.NAMES if getattr(a, n) is not None}
+        if len(sizes) != 1:
+            raise ValueError(f"stacked actor tensors disagree on the number of policies: {sorted(sizes)}")
+        self.n_policies = int(sizes.pop())
+
+    def __len__(self) -> int:
+        return self.n_policies
+
+    def __getitem__(self, p: int) -> List[ActorParams]:
+        p = int(p)
+        if not -self.n_policies <= p < self.n_policies:
+            raise IndexError(f"policy {p} of {self.n_policies}")
+        return [ActorParams(*[None if getattr(a, n) is None else getattr(a, n)[p] for n in ActorParams.NAMES], a.squash)
+                for a in self.agents]
+
+    def __iter__(self):
+        return (self[p] for p in range(self.n_policies))
+
+    def select(self, index) -> "ActorPopulation":
+        """The sub-population of the policies `index` names (a slice: views; an index tensor / list: copies) — how a population is
+        sharded: every rank evaluates its own slice."""
+        def take(t):
+            if t is None:
+                return None
+            s = t[index]
+            return s if s.is_contiguous() else s.contiguous()
+        return ActorPopulation([ActorParams(*[take(getattr(a, n)) for n in ActorParams.NAMES], a.squash) for a in self.agents])
+
+    @classmethod
+    def stack(cls, members: Sequence[Sequence[ActorParams]]) -> "ActorPopulation":
+        """From P ordinary actor lists (one ActorParams per agent each).  All members must have the same number of agents, tensor
+        sizes, dtype and device, and ONE form: the same `squash` rule and the same log_std source per agent.  ValueError otherwise."""
+        members = [list(m) for m in members]
+        if not members:
+            raise ValueError("stack needs at least one policy")
+        first = members[0]
+        agents = []
+        for m in members:
+            if len(m) != len(first):
+                raise ValueError(f"policies with {len(first)} and {len(m)} actors cannot be stacked")
+        for k, ref in enumerate(first):
+            cols = {}
+            for n in ActorParams.NAMES:
+                r = getattr(ref, n)
+                for m in members:
+                    t = getattr(m[k], n)
+                    if (t is None) != (r is None) or m[k].squash != ref.squash:
+                        raise ValueError(f"agent {k}: all policies of a population share one form (squash rule and log_std source)")
+                    if t is not None and (t.shape != r.shape or t.dtype != r.dtype or t.device != r.device):
+                        raise ValueError(f"agent {k}: actor tensor {n} differs in size, dtype or device between policies "
+                                         f"({tuple(t.shape)} {t.dtype} on {t.device} against {tuple(r.shape)} {r.dtype} on {r.device})")
+                cols[n] = None if r is None else torch.stack([getattr(m[k], n) for m in members]).contiguous()
+            agents.append(ActorParams(**cols, squash=ref.squash))
+        return cls(agents)
+
+    @classmethod
+    def perturb(cls, base_actors: Sequence[ActorParams], n: int, sigma: float, generator=None, antithetic: bool = True, eps=None):
+        """The evolution-strategy constructor: n policies theta + sigma eps_i around `base_actors`, over ALL weight and bias tensors
+        (fc1, fc2 and the mean head; the log_std source is copied, evaluation never reads it).  eps ~ N(0, 1) from `generator`.
+        antithetic (n even): pairs are adjacent — policy 2k is theta + sigma eps_k, policy 2k + 1 is theta - sigma eps_k, with the
+        SAME float32 product sigma eps_k, so a pair's mean is theta up to the one rounding of each member to float32.
+        Returns (population, eps): eps is one dict per agent, tensor name -> [n, ...] float32, row i the draw of policy i (row
+        2k + 1 = -row 2k when antithetic) — what the estimator sum_i fitness_i eps_i / (n sigma) needs.
+        `eps`: given draws in that form instead of the generator's ([n, ...] per tensor; antithetic: the even rows are used)."""
+        n = int(n)
+        if n < 1 or (antithetic and n % 2):
+            raise ValueError("perturb needs n >= 1, and an even n when antithetic")
+        agents, draws = [], []
+        for k, a in enumerate(base_actors):
+            cols, e_k = {}, {}
+            for name in ActorParams.NAMES:
+                t = getattr(a, name)
+                if t is None:
+                    cols[name] = None
+                elif name not in _WEIGHTS:
+                    cols[name] = t.detach().unsqueeze(0).expand(n, *t.shape).contiguous()
+                else:
+                    t = t.detach()
+                    half = n // 2 if antithetic else n
+                    if eps is not None:
+                        given = eps[k][name]
+                        if tuple(given.shape) != (n,) + tuple(t.shape):
+                            raise ValueError(f"eps[{k}][{name!r}] must be [{n}, ...] like the stacked tensor")
+                        e = (given[0::2] if antithetic else given).to(t)
+                    else:
+                        e = torch.randn((half,) + tuple(t.shape), dtype=t.dtype, device=t.device, generator=generator)
+                    d = float(sigma) * e
+                    if antithetic:
+                        cols[name] = torch.stack([t + d, t - d], 1).reshape((n,) + tuple(t.shape)).contiguous()
+                        e_k[name] = torch.stack([e, -e], 1).reshape((n,) + tuple(t.shape))
+                    else:
+                        cols[name], e_k[name] = (t + d).contiguous(), e
+            agents.append(ActorParams(**cols, squash=a.squash))
+            draws.append(e_k)
+        return cls(agents), draws
+
+    def check(self, kind: str, device):
+        """The host-side argument check of evaluate_population: the reference's sizes for `kind`, contiguous float32 on `device`."""
+        dims = ACTOR_DIMS[kind]
+        if len(self.agents) != len(dims):
+            raise ValueError(f"kind {kind!r} needs {len(dims)} actor(s)")
+        for a, d in zip(self.agents, dims):
+            for n in ActorParams.NAMES:
+                t = getattr(a, n)
+                if t is not None and (t.dtype != torch.float32 or t.device != device or not t.is_contiguous()):
+                    raise ValueError(f"stacked actor tensor {n} must be a contiguous float32 tensor on {device}")
+        for a_, d in zip(self[0], dims):
+            a_.check(d, device)
+
+    def c_array(self):
+        """QrActor array of policy 0 — the stacked-tensor rule's base pointers."""
+        return c_actor_array(self[0])

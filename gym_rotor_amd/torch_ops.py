@@ -189,6 +189,40 @@ def qr_evaluate_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Opti
         _lib.check(_lib.load().qr_evaluate_actor(C.byref(e), C.byref(pol), max_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_evaluate_actor")
 
 
+@torch.library.custom_op(f"{_NS}::qr_evaluate_population",
+                         mutates_args=("pos_vel", "att_rate", "integ", "goal", "traj", "steps", "action_out", "episode_return", "benchmark",
+                                       "length", "terminated", "success", "final_error", "obs0", "obs1"))
+def qr_evaluate_population(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Optional[torch.Tensor], params: Optional[torch.Tensor],
+                           goal: Optional[torch.Tensor], traj: Optional[torch.Tensor], episode: Optional[torch.Tensor],
+                           steps: Optional[torch.Tensor], reset_count: Optional[torch.Tensor],
+                           actor0: List[torch.Tensor], actor1: List[torch.Tensor], squash: List[int],
+                           obs0_in: torch.Tensor, obs1_in: Optional[torch.Tensor], action_out: Optional[torch.Tensor],
+                           episode_return: torch.Tensor, benchmark: torch.Tensor, length: torch.Tensor, terminated: torch.Tensor,
+                           success: torch.Tensor, final_error: Optional[torch.Tensor], obs0: torch.Tensor, obs1: Optional[torch.Tensor],
+                           envs_per_policy: int, max_steps: int, substeps: int, max_action: float, cfg: List[int],
+                           coeffs: List[float]) -> None:
+    """qr_evaluate_actor for P policies in one launch (qr_evaluate_population).  Actors as in qr_evaluate_actor with every tensor
+    STACKED [P, ...] (contiguous; P is read off actor0[0]); the env holds P * roundup(envs_per_policy, 64) envs, policy p owns
+    [p Epad, p Epad + E); rows are per env, padding rows untouched."""
+    from .policy import ActorPopulation
+    e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
+    population = ActorPopulation(_actor_params(actor0, actor1, squash))
+    if e.kind in (_lib.KIND_COUPLED, _lib.KIND_DECOUPLED):  # (Quad-v0: the library answers QR_E_KIND)
+        population.check(_lib.KIND_NAME[e.kind], pos_vel.device)
+    arr = population.c_array()
+    pop = _lib.QrPopulation(len(population), int(envs_per_policy))
+    pol = _lib.QrPolicyRollout()
+    pol.actors = arr
+    pol.obs0_in, pol.obs1_in = obs0_in.data_ptr(), _p(obs1_in)
+    pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _p(action_out)
+    o = _lib.QrEvalOut()
+    o.episode_return, o.benchmark, o.length, o.terminated = _p(episode_return), _p(benchmark), _p(length), _p(terminated)
+    o.success, o.final_error, o.obs0, o.obs1 = _p(success), _p(final_error), _p(obs0), _p(obs1)
+    with torch.cuda.device(pos_vel.device):
+        _lib.check(_lib.load().qr_evaluate_population(C.byref(e), C.byref(pol), C.byref(pop), max_steps, substeps, C.byref(o),
+                                                      _stream(pos_vel)), "qr_evaluate_population")
+
+
 @torch.library.custom_op(f"{_NS}::qr_error_obs", mutates_args=("integ", "obs0", "obs1"))
 def qr_error_obs(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: torch.Tensor, goal: Optional[torch.Tensor],
                  obs0: torch.Tensor, obs1: Optional[torch.Tensor], cfg: List[int], coeffs: List[float], fmt: int = -1) -> None:
@@ -313,6 +347,19 @@ def evaluate(env, actors, max_steps: int, obs, out: dict, max_action: float = 1.
                                               out["episode_return"], out["benchmark"], out["length"], out["terminated"], out["success"],
                                               out.get("final_error"), out["obs0"], out.get("obs1"), int(max_steps), env.substeps,
                                               float(max_action), cfg, co)
+
+
+def evaluate_population(env, population, envs_per_policy: int, max_steps: int, obs, out: dict, max_action: float = 1.0) -> None:
+    """`env.evaluate_population(population, envs_per_policy, max_steps, obs)` as ONE torch op on the env's buffers: results land in
+    `out`, per env [N, ...] as QuadVecEnv.evaluate_population returns them ("action" and "final_error" optional)."""
+    t, cfg, co = env_args(env)
+    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    lists, squash = _actor_lists(population.agents)
+    torch.ops.gym_rotor_amd.qr_evaluate_population(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None,
+                                                   out.get("action"), out["episode_return"], out["benchmark"], out["length"],
+                                                   out["terminated"], out["success"], out.get("final_error"), out["obs0"],
+                                                   out.get("obs1"), int(envs_per_policy), int(max_steps), env.substeps,
+                                                   float(max_action), cfg, co)
 
 
 def error_obs(env, framework: Optional[str] = None, out=None) -> None:

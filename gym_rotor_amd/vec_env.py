@@ -535,6 +535,36 @@ class QuadVecEnv:
         `out`: the same dict with preallocated tensors ("final_error" and "action" may be left out).  The rows become the env's
         current observation; the exploration-noise stream of rollout_actor does not advance."""
         actors = self._check_actors(actors, "evaluate")
+        from .policy import c_actor_array
+        return self._evaluate_launch(c_actor_array(actors), None, max_steps, obs, max_action, out)
+
+    def evaluate_population(self, population, envs_per_policy: int, max_steps: Optional[int] = None, obs=None, max_action: float = 1.0,
+                            out: Optional[dict] = None) -> dict:
+        """`evaluate` for P policies in ONE launch (qr_evaluate_population): `population` is a `policy.ActorPopulation` of P
+        policies, each flown over E = `envs_per_policy` episodes.  Called on an env of N = P * Epad envs, Epad = E rounded up to a
+        multiple of 64 (`policy.population_layout`): policy p owns envs [p Epad, p Epad + E) and flies them with its own weights,
+        exactly as `evaluate(population[p])` flies an E-env env from the same states and observation rows — the same kernels and
+        arithmetic.  The Epad - E padding envs behind each block are never flown: their state, integrators, generator state and
+        episode_steps stay as they are, their rows of `obs` are ignored and their rows of every output are not written (zeros
+        when this method allocates them).  Returns and side effects are `evaluate`'s, per env [N, ...]
+        (`policy.population_view` gives the [P, E, ...] views): the rows become the env's current observation, episode_steps
+        advances by `length`, the exploration-noise stream does not advance."""
+        from .policy import ActorPopulation, population_layout
+        if self.kind == "quad":
+            raise ValueError("evaluate_population needs kind 'coupled' or 'decoupled' (the reference trains on the wrappers)")
+        if not self.obs_rows:
+            raise ValueError("evaluate_population needs obs_rows=True")
+        if not isinstance(population, ActorPopulation):
+            raise TypeError("population must be a policy.ActorPopulation (ActorPopulation.stack / .perturb)")
+        P, E = len(population), int(envs_per_policy)
+        epad, n = population_layout(P, E)
+        if n != self.num_envs:
+            raise ValueError(f"{P} policies x {E} episodes need an env of {P} x {epad} = {n} envs, this one has {self.num_envs}")
+        population.check(self.kind, self.device)
+        return self._evaluate_launch(population.c_array(), _lib.QrPopulation(P, E), max_steps, obs, max_action, out)
+
+    def _evaluate_launch(self, arr, pop, max_steps, obs, max_action, out) -> dict:
+        """The launch behind evaluate (pop None) and evaluate_population: argument checks, the C structs, one library call."""
         T = int(round(5.0 / self.dt)) if max_steps is None else int(max_steps)
         if T < 1:
             raise ValueError("max_steps must be >= 1")
@@ -547,16 +577,15 @@ class QuadVecEnv:
                 "obs0": ((N, self.obs_dims[0]), torch.float32), "action": ((N, A), torch.float32)}
         if len(self.obs_dims) > 1:
             want["obs1"] = ((N, self.obs_dims[1]), torch.float32)
-        if out is None:
-            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
+        if out is None:  # (a population's padding rows are never written: zeros rather than whatever the allocator returns)
+            alloc = torch.empty if pop is None else torch.zeros
+            out = {k: alloc(shape, dtype=dt, device=dev) for k, (shape, dt) in want.items()}
         for k, (shape, dt) in want.items():
             t = out.get(k)
             if t is None and k in ("final_error", "action"):
                 continue
             if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
-        from .policy import c_actor_array
-        arr = c_actor_array(actors)
         pol = _lib.QrPolicyRollout()
         pol.actors = arr
         pol.obs0_in, pol.obs1_in = obs[0].data_ptr(), (obs[1].data_ptr() if len(obs) > 1 else None)
@@ -566,8 +595,12 @@ class QuadVecEnv:
         o.terminated, o.success, o.final_error = _ptr(out["terminated"]), _ptr(out["success"]), _ptr(out.get("final_error"))
         o.obs0, o.obs1 = _ptr(out["obs0"]), _ptr(out.get("obs1"))
         with self._on_device():
-            rc = self._lib.qr_evaluate_actor(C.byref(self._cenv), C.byref(pol), T, self.substeps, C.byref(o), self._stream())
-        _lib.check(rc, "qr_evaluate_actor")
+            if pop is None:
+                rc = self._lib.qr_evaluate_actor(C.byref(self._cenv), C.byref(pol), T, self.substeps, C.byref(o), self._stream())
+            else:
+                rc = self._lib.qr_evaluate_population(C.byref(self._cenv), C.byref(pol), C.byref(pop), T, self.substeps, C.byref(o),
+                                                      self._stream())
+        _lib.check(rc, "qr_evaluate_actor" if pop is None else "qr_evaluate_population")
         self._last_obs = out["obs0"] if len(self.obs_dims) == 1 else (out["obs0"], out["obs1"])
         return out
 

@@ -308,6 +308,26 @@ typedef struct QrEvalOut {
 int qr_evaluate_actor(const QrEnv* env, const QrPolicyRollout* policy, int32_t max_steps, int32_t substeps,
                       const QrEvalOut* out, void* stream);
 
+/* The block layout of qr_evaluate_population: P policies, E episodes each, on ONE env of N = P * Epad envs, Epad = E rounded up
+ * to a multiple of 64 (a 64-env tile never holds two policies).  Policy p owns envs [p * Epad, p * Epad + E); the Epad - E
+ * padding envs behind them are never flown. */
+typedef struct QrPopulation {
+  int32_t n_policies;       /* P >= 1 */
+  int32_t envs_per_policy;  /* E >= 1; env->num_envs must equal P * roundup(E, 64) */
+} QrPopulation;
+
+/* qr_evaluate_actor for P policies in ONE launch (checkpoint selection, sweeps, the fitness of a perturbed population): the same
+ * kernels, arithmetic, freeze and write-back per env; only the weights differ per block.  Stacked-tensor rule: every tensor of
+ * policy->actors[k] is a contiguous float32 [P][...] stack of the per-policy tensors of QrActor's sizes; the QrActor pointers
+ * point at policy 0 and policy p's tensor starts p * numel elements later (fc1_w [P][hidden][obs_dim], fc1_b [P][hidden], ...).
+ * The log_std sources are never read (one of them must still be set, as for qr_evaluate_actor) and squash is shared.
+ * policy->obs0_in / obs1_in, policy->action_out and every array of `out` are indexed by env, [N][...], as in qr_evaluate_actor;
+ * padding rows are ignored on input and untouched on output, and so are the padding envs' state, integrators, generator state
+ * and `steps`.  n_policies = 1 with envs_per_policy = N is qr_evaluate_actor, bit for bit.  QR_E_NULL for a NULL pop; QR_E_SIZE
+ * for P < 1, E < 1 or num_envs != P * roundup(E, 64); every other check is qr_evaluate_actor's. */
+int qr_evaluate_population(const QrEnv* env, const QrPolicyRollout* policy, const QrPopulation* pop, int32_t max_steps,
+                           int32_t substeps, const QrEvalOut* out, void* stream);
+
 /* Replaces QuadEnv.get_norm_error_state(framework) (quad.py:421-466): normalised error
  * observation of the CURRENT state; advances both trapezoid integrators (same side
  * effect as the reference).  kind must be COUPLED or DECOUPLED. */

@@ -8,6 +8,14 @@ Both wrappers at --envs (65 536) envs and T = 1000 steps (eval_max_steps), with 
   random        the reference's initial actor (random_actors), from the eval reset distribution: episodes crash early.
 Prints one JSON line per (kind, actor) with us per launch and per 65 536-env step (launch time / T), the mean episode length and
 the speed-up, and checks that both paths give the same lengths.
+
+--population: QuadVecEnv.evaluate_population (qr_evaluate_population: P policies x E episodes in one launch) instead, with
+ActorPopulation.perturb-ed trained-like actors from rest at the goal, both wrappers, one JSON line per row:
+  (a) "vs_single"  P = envs / 64 policies x 64 episodes against ONE single-policy evaluate of the same envs (policy 0), and — the
+                   control with identical work per tile — against the population launch of P copies of policy 0;
+  (b) "vs_loop"    --loop-policies (32) policies x 64 episodes in one launch against a Python loop of evaluate calls on a 64-env
+                   env, one per policy (the only way before): per-policy cost of each.  Both restore their starts before every
+                   evaluation (a comparison on common starts needs that); the restore alone is timed and reported too.
 """
 import argparse
 import json
@@ -62,13 +70,101 @@ def timed(fn, reps):
     return float(np.median(times))
 
 
+def _rest(env):
+    n = env.num_envs
+    s = np.zeros((n, 18))
+    s[:, 6:15] = np.eye(3).reshape(-1, order="F")
+    env.set_state(s, integ=np.zeros((n, 8)))
+    return [o.clone() for o in env.get_norm_error_state()]
+
+
+def population_rows(a):
+    from gym_rotor_amd import ActorPopulation
+    from gym_rotor_amd.policy import population_layout
+    T, E = a.steps, 64
+    for kind in a.kinds.split(","):
+        gen = torch.Generator("cuda").manual_seed(0)
+        # ---- (a) one launch of P x 64 against one single-policy launch of the same envs ----
+        P = max(a.envs // E, 1)
+        _, N = population_layout(P, E)
+        pop, _ = ActorPopulation.perturb(hover_actors(kind), P, a.sigma, generator=gen)
+        copies = ActorPopulation.stack([pop[0]] * P)
+        env = QuadVecEnv(kind, N, device="cuda", seed=1992, autotune=False)
+        obs = _rest(env)
+        sd = env.state_dict()
+
+        def run(fn):
+            def go():
+                env.load_state_dict(sd)
+                return fn()
+            return go
+
+        single = run(lambda: env.evaluate(pop[0], max_steps=T, obs=obs))
+        many = run(lambda: env.evaluate_population(pop, E, max_steps=T, obs=obs))
+        same = run(lambda: env.evaluate_population(copies, E, max_steps=T, obs=obs))
+        r_single, r_many, r_same = single(), many(), same()
+        torch.cuda.synchronize()
+        identical = all(bool(torch.equal(r_single[k], r_same[k])) for k in r_single)
+        lens = [float(r["length"].double().mean()) for r in (r_single, r_many)]
+        longest = [int(r["length"].max()) for r in (r_single, r_many)]   # (a launch lasts as long as its longest-lived tile)
+        del r_single, r_many, r_same
+        t_single, t_many, t_same = timed(single, a.reps), timed(many, a.reps), timed(same, a.reps)
+        print(json.dumps({"row": "vs_single", "kind": kind, "envs": N, "policies": P, "episodes_per_policy": E, "max_steps": T,
+                          "sigma": a.sigma, "single_us": round(t_single, 1), "population_us": round(t_many, 1),
+                          "population_of_copies_us": round(t_same, 1), "ratio": round(t_many / t_single, 3),
+                          "ratio_copies": round(t_same / t_single, 3), "mean_length_single": round(lens[0], 1),
+                          "mean_length_population": round(lens[1], 1),
+                          "max_length_single": longest[0], "max_length_population": longest[1], "copies_identical_to_single": identical}), flush=True)
+        del env
+        torch.cuda.empty_cache()
+        # ---- (b) one launch of 32 x 64 against a loop of 32 evaluate calls on a 64-env env ----
+        P = a.loop_policies
+        _, N = population_layout(P, E)
+        pop, _ = ActorPopulation.perturb(hover_actors(kind), P, a.sigma, generator=gen)
+        big, small = (QuadVecEnv(kind, n, device="cuda", seed=1992, autotune=False) for n in (N, E))
+        obs_big, obs_small = _rest(big), _rest(small)
+        sd_big, sd_small = big.state_dict(), small.state_dict()
+        members = [pop[p] for p in range(P)]
+
+        def one_launch():
+            big.load_state_dict(sd_big)
+            return big.evaluate_population(pop, E, max_steps=T, obs=obs_big)
+
+        def loop():
+            out = []
+            for m in members:
+                small.load_state_dict(sd_small)
+                out.append(small.evaluate(m, max_steps=T, obs=obs_small))
+            return out
+
+        r_pop, r_loop = one_launch(), loop()
+        torch.cuda.synchronize()
+        agree = all(bool(torch.equal(r_pop[k][p * E:(p + 1) * E], r_loop[p][k])) for p in range(P) for k in r_pop)
+        mean_len = float(r_pop["length"].double().mean())
+        del r_pop, r_loop
+        t_pop, t_loop = timed(one_launch, a.reps), timed(loop, a.reps)
+        t_rb, t_rs = timed(lambda: big.load_state_dict(sd_big), a.reps), timed(lambda: small.load_state_dict(sd_small), a.reps)
+        print(json.dumps({"row": "vs_loop", "kind": kind, "policies": P, "episodes_per_policy": E, "max_steps": T, "sigma": a.sigma,
+                          "mean_length": round(mean_len, 1), "population_us": round(t_pop, 1), "loop_us": round(t_loop, 1),
+                          "population_us_per_policy": round(t_pop / P, 1), "loop_us_per_policy": round(t_loop / P, 1),
+                          "restore_us_population": round(t_rb, 1), "restore_us_loop_per_policy": round(t_rs, 1),
+                          "speedup": round(t_loop / t_pop, 2), "loop_identical_to_population": agree}), flush=True)
+        del big, small
+        torch.cuda.empty_cache()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--envs", type=int, default=65536)
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--kinds", default="coupled,decoupled")
+    p.add_argument("--population", action="store_true", help="the evaluate_population rows instead")
+    p.add_argument("--loop-policies", type=int, default=32)
+    p.add_argument("--sigma", type=float, default=0.01, help="ActorPopulation.perturb's sigma around the trained-like actor")
     a = p.parse_args()
+    if a.population:
+        return population_rows(a)
     N, T = a.envs, a.steps
     for kind in a.kinds.split(","):
         for actor_name in ("trained-like", "random"):

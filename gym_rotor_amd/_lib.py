@@ -83,6 +83,37 @@ class QrPopulation(C.Structure):
     _fields_ = [("n_policies", C.c_int32), ("envs_per_policy", C.c_int32)]
 
 
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def step_out(out, truncated: bool) -> QrStepOut:
+    """QrStepOut over a mapping of output tensors keyed by the member names, `terminated` for the member `done`; a missing or
+    None entry is a null pointer.  truncated=False: the env has no step counter, the `truncated` member stays null."""
+    o = QrStepOut(*(ptr(out.get("terminated" if name == "done" else name)) for name, _ in QrStepOut._fields_))
+    if not truncated:
+        o.truncated = None
+    return o
+
+
+def eval_out(out) -> QrEvalOut:
+    """QrEvalOut over a mapping keyed by the member names (the keys of QuadVecEnv.evaluate's dict); missing or None: null."""
+    return QrEvalOut(*(ptr(out.get(name)) for name, _ in QrEvalOut._fields_))
+
+
+def policy_rollout(actors_c, obs, *, action_out, logprob_out=None, noise=None, noise_seed=0, step_base=0, max_action=1.0, deterministic=False):
+    """QrPolicyRollout of one policy launch.  actors_c: the QrActor array (policy.c_actor_array / ActorPopulation.c_array) — the
+    struct only points at it, so the caller keeps `actors_c` alive until the library call has returned.  obs: the one or two
+    observation tensors the first action is computed from (the second may be None)."""
+    p = QrPolicyRollout()
+    p.actors = actors_c
+    p.obs0_in, p.obs1_in, p.noise = ptr(obs[0]), (ptr(obs[1]) if len(obs) > 1 else None), ptr(noise)
+    p.noise_seed, p.step_base = int(noise_seed) & (2 ** 64 - 1), int(step_base)
+    p.max_action, p.deterministic = float(max_action), int(bool(deterministic))
+    p.action_out, p.logprob_out = ptr(action_out), ptr(logprob_out)
+    return p
+
+
 class QrLaunchPlan(C.Structure):
     _fields_ = [("grid", C.c_int32), ("block", C.c_int32), ("launches", C.c_int32),
                 ("traj", C.c_int32), ("adapt", C.c_int32), ("policy", C.c_int32), ("single", C.c_int32), ("help", C.c_int32), ("hrew", C.c_int32),

@@ -64,6 +64,30 @@ class EvalResult:
                 "episodes": int(n)}
 
 
+def _prepare_episodes(kind, num_envs, traj_mode, seed, **env_kw):
+    """(env, obs): `num_envs` evaluation episodes at their start as eval_policy prepares them (main.py:305-309) — reset(env_type=
+    'eval', seed), with a fused generator mark_traj_start + the first get_desired(store_goal=True), the first observation."""
+    env = QuadVecEnv(kind, int(num_envs), seed=seed, goal_mode=traj_mode, autotune=False, **env_kw)
+    env.reset("eval", seed=seed)
+    if traj_mode is not None:
+        env.get_desired(store_goal=True)
+    return env, env.get_norm_error_state()
+
+
+def _tile_episodes(src: QuadVecEnv, src_obs, env: QuadVecEnv, P: int) -> list:
+    """Copy the prepared episodes of `src` (E envs: state, parameters, integrators, goal, generator state, episode index) into every
+    one of the P policies' blocks of `env` (P * Epad envs); returns `src_obs` tiled the same way, zeros in the padding rows."""
+    from .policy import population_tile
+    E = src.num_envs
+    if src._goal is not None:   # (the goal buffer of a stateless generator mode exists from get_desired(store_goal=True) on)
+        env._ensure_goal()
+    for name in ("_pos_vel", "_att_rate", "_integ", "_params", "_goal", "_traj"):   # SoA [fields, N]
+        if getattr(src, name) is not None:
+            population_tile(getattr(src, name), P, E, getattr(env, name), env_dim=1)
+    population_tile(src._episode, P, E, env._episode)
+    return [population_tile(o, P, E, torch.zeros(env.num_envs, o.shape[1], dtype=o.dtype, device=o.device)) for o in src_obs]
+
+
 def evaluate_policy(kind: str, actors: Sequence, num_episodes: int, traj_mode: Optional[int] = 0, seed: int = 1992,
                     eval_seconds: float = 5.0, device="cuda", substeps: int = 1, layout: str = "mixed", env_offset: int = 0,
                     max_action: float = 1.0) -> EvalResult:
@@ -74,12 +98,7 @@ def evaluate_policy(kind: str, actors: Sequence, num_episodes: int, traj_mode: O
     episode (shard_range), so that a sharded evaluation draws the same episodes as a single-device one."""
     if kind == "quad":
         raise ValueError("evaluate_policy needs kind 'coupled' or 'decoupled' (Quad-v0 has no actor)")
-    env = QuadVecEnv(kind, int(num_episodes), device=device, seed=seed, substeps=substeps, layout=layout, goal_mode=traj_mode,
-                     env_offset=env_offset, autotune=False)
-    env.reset("eval", seed=seed)
-    if traj_mode is not None:
-        env.get_desired(store_goal=True)
-    obs = env.get_norm_error_state()
+    env, obs = _prepare_episodes(kind, num_episodes, traj_mode, seed, device=device, substeps=substeps, layout=layout, env_offset=env_offset)
     out = env.evaluate(actors, max_steps=int(round(eval_seconds / env.dt)), obs=obs, max_action=max_action)
     return EvalResult.from_dict(out)
 
@@ -146,37 +165,17 @@ def evaluate_population(kind: str, population, episodes_per_policy: int, traj_mo
     Sharding is by slicing the population: each rank evaluates `population.select(slice)` (with the same seed and, for common
     episodes, the same env_offset) and keeps its own PopulationResult; there is nothing to reduce across ranks until the caller
     compares per_policy() figures."""
-    from .policy import population_layout, population_tile
+    from .policy import population_layout
     if kind == "quad":
         raise ValueError("evaluate_population needs kind 'coupled' or 'decoupled' (Quad-v0 has no actor)")
     P, E = len(population), int(episodes_per_policy)
     _, n = population_layout(P, E)
-
-    def prepared(num_envs):
-        env = QuadVecEnv(kind, num_envs, device=device, seed=seed, substeps=substeps, layout=layout, goal_mode=traj_mode,
-                         env_offset=env_offset, autotune=False)
-        env.reset("eval", seed=seed)
-        if traj_mode is not None:
-            env.get_desired(store_goal=True)
-        return env, env.get_norm_error_state()
-
+    env_kw = dict(device=device, substeps=substeps, layout=layout, env_offset=env_offset)
     if common_episodes:
-        src, src_obs = prepared(E)
-        env = QuadVecEnv(kind, n, device=device, seed=seed, substeps=substeps, layout=layout, goal_mode=traj_mode,
-                         env_offset=env_offset, autotune=False)
-        for name in ("_pos_vel", "_att_rate", "_integ", "_params", "_goal", "_traj"):   # SoA [fields, N]
-            s, d = getattr(src, name), getattr(env, name)
-            if s is None:
-                continue
-            if d is None:   # (the goal buffer of a stateless generator mode exists from get_desired(store_goal=True) on)
-                d = env._soa(s.shape[0], s.dtype)
-                setattr(env, name, d)
-            population_tile(s, P, E, d, env_dim=1)
-        env._sync_structs()
-        population_tile(src._episode, P, E, env._episode)
-        src_obs = [src_obs] if isinstance(src_obs, torch.Tensor) else list(src_obs)
-        obs = [population_tile(o, P, E, torch.zeros(n, o.shape[1], dtype=o.dtype, device=o.device)) for o in src_obs]
+        src, src_obs = _prepare_episodes(kind, E, traj_mode, seed, **env_kw)
+        env = QuadVecEnv(kind, n, seed=seed, goal_mode=traj_mode, autotune=False, **env_kw)
+        obs = _tile_episodes(src, src_obs, env, P)
     else:
-        env, obs = prepared(n)
+        env, obs = _prepare_episodes(kind, n, traj_mode, seed, **env_kw)
     out = env.evaluate_population(population, E, max_steps=int(round(eval_seconds / env.dt)), obs=obs, max_action=max_action)
     return PopulationResult(out, P, E)

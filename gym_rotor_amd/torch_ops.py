@@ -33,8 +33,7 @@ _COEFF_NAMES = [n for n, _ in _lib.QrCoeffs._fields_]
 N_CFG = 7
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+_p = _lib.ptr
 
 
 def _gpu(t: torch.Tensor):
@@ -79,16 +78,15 @@ def _stream(t: torch.Tensor):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def _out_struct(obs0, obs1, reward, reward_raw, done, truncated, final_obs0, final_obs1):
-    o = _lib.QrStepOut()
-    o.obs0, o.obs1, o.reward, o.reward_raw = _p(obs0), _p(obs1), _p(reward), _p(reward_raw)
-    o.done, o.truncated, o.final_obs0, o.final_obs1 = _p(done), _p(truncated), _p(final_obs0), _p(final_obs1)
-    return o
+def _out_struct(*tensors):
+    """QrStepOut of an op's positional output tensors, in _OUT_MUT's order (a None `truncated` is a null pointer either way)."""
+    return _lib.step_out(dict(zip(_OUT_KEYS, tensors)), True)
 
 
 # (goal: written by the fused goal generator's stateful modes 2-5, whose xd / vd / b1d / Wd persist there)
 _ENV_MUT = ("pos_vel", "att_rate", "integ", "params", "goal", "traj", "episode", "steps", "reset_count")
 _OUT_MUT = ("obs0", "obs1", "reward", "reward_raw", "done", "truncated", "final_obs0", "final_obs1")
+_OUT_KEYS = tuple("terminated" if k == "done" else k for k in _OUT_MUT)   # the ops call QrStepOut.done by its member name
 
 
 @torch.library.custom_op(f"{_NS}::qr_step", mutates_args=_ENV_MUT + _OUT_MUT)
@@ -135,13 +133,9 @@ def qr_rollout_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Optio
     tensors; actor1 = [] for COUPLED); squash = QR_ACTOR_* per agent."""
     from .policy import c_actor_array
     e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
-    arr = c_actor_array(_actor_params(actor0, actor1, squash))
-    pol = _lib.QrPolicyRollout()
-    pol.actors = arr
-    pol.obs0_in, pol.obs1_in, pol.noise = obs0_in.data_ptr(), _p(obs1_in), _p(noise)
-    pol.noise_seed, pol.step_base = int(noise_seed) & (2 ** 64 - 1), int(step_base)
-    pol.max_action, pol.deterministic = float(max_action), int(bool(deterministic))
-    pol.action_out, pol.logprob_out = action_out.data_ptr(), _p(logprob_out)
+    arr = c_actor_array(_actor_params(actor0, actor1, squash))   # (kept alive here: the struct only points at it)
+    pol = _lib.policy_rollout(arr, (obs0_in, obs1_in), action_out=action_out, logprob_out=logprob_out, noise=noise, noise_seed=noise_seed,
+                              step_base=step_base, max_action=max_action, deterministic=deterministic)
     o = _out_struct(obs0, obs1, reward, reward_raw, done, truncated, final_obs0, final_obs1)
     with torch.cuda.device(pos_vel.device):
         _lib.check(_lib.load().qr_rollout_actor(C.byref(e), C.byref(pol), n_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_rollout_actor")
@@ -175,18 +169,9 @@ def qr_evaluate_actor(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ: Opti
                       max_steps: int, substeps: int, max_action: float, cfg: List[int], coeffs: List[float]) -> None:
     """Learner.eval_policy for every env in one launch (qr_evaluate_actor): the deterministic actor(s) from each env's current state
     until its first done or max_steps; per-env results as in QrEvalOut.  Actors as in qr_rollout_actor."""
-    from .policy import c_actor_array
-    e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
-    arr = c_actor_array(_actor_params(actor0, actor1, squash))
-    pol = _lib.QrPolicyRollout()
-    pol.actors = arr
-    pol.obs0_in, pol.obs1_in = obs0_in.data_ptr(), _p(obs1_in)
-    pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _p(action_out)
-    o = _lib.QrEvalOut()
-    o.episode_return, o.benchmark, o.length, o.terminated = _p(episode_return), _p(benchmark), _p(length), _p(terminated)
-    o.success, o.final_error, o.obs0, o.obs1 = _p(success), _p(final_error), _p(obs0), _p(obs1)
-    with torch.cuda.device(pos_vel.device):
-        _lib.check(_lib.load().qr_evaluate_actor(C.byref(e), C.byref(pol), max_steps, substeps, C.byref(o), _stream(pos_vel)), "qr_evaluate_actor")
+    _evaluate_op(None, _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs),
+                 _actor_params(actor0, actor1, squash), (obs0_in, obs1_in), action_out,
+                 (episode_return, benchmark, length, terminated, success, final_error, obs0, obs1), max_steps, substeps, max_action, pos_vel)
 
 
 @torch.library.custom_op(f"{_NS}::qr_evaluate_population",
@@ -204,23 +189,27 @@ def qr_evaluate_population(pos_vel: torch.Tensor, att_rate: torch.Tensor, integ:
     """qr_evaluate_actor for P policies in one launch (qr_evaluate_population).  Actors as in qr_evaluate_actor with every tensor
     STACKED [P, ...] (contiguous; P is read off actor0[0]); the env holds P * roundup(envs_per_policy, 64) envs, policy p owns
     [p Epad, p Epad + E); rows are per env, padding rows untouched."""
-    from .policy import ActorPopulation
-    e = _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs)
-    population = ActorPopulation(_actor_params(actor0, actor1, squash))
-    if e.kind in (_lib.KIND_COUPLED, _lib.KIND_DECOUPLED):  # (Quad-v0: the library answers QR_E_KIND)
-        population.check(_lib.KIND_NAME[e.kind], pos_vel.device)
-    arr = population.c_array()
-    pop = _lib.QrPopulation(len(population), int(envs_per_policy))
-    pol = _lib.QrPolicyRollout()
-    pol.actors = arr
-    pol.obs0_in, pol.obs1_in = obs0_in.data_ptr(), _p(obs1_in)
-    pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _p(action_out)
-    o = _lib.QrEvalOut()
-    o.episode_return, o.benchmark, o.length, o.terminated = _p(episode_return), _p(benchmark), _p(length), _p(terminated)
-    o.success, o.final_error, o.obs0, o.obs1 = _p(success), _p(final_error), _p(obs0), _p(obs1)
+    _evaluate_op(int(envs_per_policy), _env_struct(pos_vel, att_rate, integ, params, goal, traj, episode, steps, reset_count, cfg, coeffs),
+                 _actor_params(actor0, actor1, squash), (obs0_in, obs1_in), action_out,
+                 (episode_return, benchmark, length, terminated, success, final_error, obs0, obs1), max_steps, substeps, max_action, pos_vel)
+
+
+def _evaluate_op(envs_per_policy: Optional[int], e, actors, obs, action_out, outs, max_steps, substeps, max_action, pos_vel):
+    """The body of qr_evaluate_actor (envs_per_policy None: `actors` are one policy's) and qr_evaluate_population (`actors` hold
+    stacked [P, ...] tensors); outs: the result tensors in QrEvalOut's member order.  One library call on pos_vel's device."""
+    from .policy import ActorPopulation, c_actor_array
+    if envs_per_policy is None:
+        arr, call, tail = c_actor_array(actors), _lib.load().qr_evaluate_actor, ()
+    else:
+        population = ActorPopulation(actors)
+        if e.kind in (_lib.KIND_COUPLED, _lib.KIND_DECOUPLED):  # (Quad-v0: the library answers QR_E_KIND)
+            population.check(_lib.KIND_NAME[e.kind], pos_vel.device)
+        pop = _lib.QrPopulation(len(population), envs_per_policy)
+        arr, call, tail = population.c_array(), _lib.load().qr_evaluate_population, (C.byref(pop),)
+    pol = _lib.policy_rollout(arr, obs, action_out=action_out, max_action=max_action, deterministic=True)   # (arr stays alive here)
+    o = _lib.eval_out(dict(zip((n for n, _ in _lib.QrEvalOut._fields_), outs)))
     with torch.cuda.device(pos_vel.device):
-        _lib.check(_lib.load().qr_evaluate_population(C.byref(e), C.byref(pol), C.byref(pop), max_steps, substeps, C.byref(o),
-                                                      _stream(pos_vel)), "qr_evaluate_population")
+        _lib.check(call(C.byref(e), C.byref(pol), *tail, max_steps, substeps, C.byref(o), _stream(pos_vel)), call.__name__)
 
 
 @torch.library.custom_op(f"{_NS}::qr_error_obs", mutates_args=("integ", "obs0", "obs1"))
@@ -299,9 +288,7 @@ def _outs(env, out):
     if out is None:
         out = {"obs0": env._obs0, "obs1": env._obs1, "reward": env._reward, "reward_raw": env._reward_raw, "terminated": env._done,
                "truncated": env._trunc if env._steps is not None else None, "final_obs0": env._final0, "final_obs1": env._final1}
-    trunc = out.get("truncated") if env._steps is not None else None
-    return (out.get("obs0"), out.get("obs1"), out["reward"], out.get("reward_raw"), out["terminated"], trunc,
-            out.get("final_obs0"), out.get("final_obs1"))
+    return tuple(out.get(k) if k != "truncated" or env._steps is not None else None for k in _OUT_KEYS)
 
 
 def step(env, action: torch.Tensor, out: Optional[dict] = None) -> None:
@@ -337,29 +324,26 @@ def _actor_lists(actors):
     return lists, squash
 
 
+def _evaluate_args(env, agents, obs, out, steps, max_action):
+    """Positional arguments of the two evaluate ops; steps = ([envs_per_policy,] max_steps), the only part in which they differ."""
+    t, cfg, co = env_args(env)
+    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    lists, squash = _actor_lists(agents)
+    return (*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None, out.get("action"), out["episode_return"],
+            out["benchmark"], out["length"], out["terminated"], out["success"], out.get("final_error"), out["obs0"], out.get("obs1"),
+            *(int(v) for v in steps), env.substeps, float(max_action), cfg, co)
+
+
 def evaluate(env, actors, max_steps: int, obs, out: dict, max_action: float = 1.0) -> None:
     """`env.evaluate(actors, max_steps, obs)` as ONE torch op on the env's buffers: results land in `out` (the keys of the dict
     QuadVecEnv.evaluate returns; "action" and "final_error" optional)."""
-    t, cfg, co = env_args(env)
-    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
-    lists, squash = _actor_lists(actors)
-    torch.ops.gym_rotor_amd.qr_evaluate_actor(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None, out.get("action"),
-                                              out["episode_return"], out["benchmark"], out["length"], out["terminated"], out["success"],
-                                              out.get("final_error"), out["obs0"], out.get("obs1"), int(max_steps), env.substeps,
-                                              float(max_action), cfg, co)
+    torch.ops.gym_rotor_amd.qr_evaluate_actor(*_evaluate_args(env, actors, obs, out, (max_steps,), max_action))
 
 
 def evaluate_population(env, population, envs_per_policy: int, max_steps: int, obs, out: dict, max_action: float = 1.0) -> None:
     """`env.evaluate_population(population, envs_per_policy, max_steps, obs)` as ONE torch op on the env's buffers: results land in
     `out`, per env [N, ...] as QuadVecEnv.evaluate_population returns them ("action" and "final_error" optional)."""
-    t, cfg, co = env_args(env)
-    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
-    lists, squash = _actor_lists(population.agents)
-    torch.ops.gym_rotor_amd.qr_evaluate_population(*t, lists[0], lists[1], squash, obs[0], obs[1] if len(obs) > 1 else None,
-                                                   out.get("action"), out["episode_return"], out["benchmark"], out["length"],
-                                                   out["terminated"], out["success"], out.get("final_error"), out["obs0"],
-                                                   out.get("obs1"), int(envs_per_policy), int(max_steps), env.substeps,
-                                                   float(max_action), cfg, co)
+    torch.ops.gym_rotor_amd.qr_evaluate_population(*_evaluate_args(env, population.agents, obs, out, (envs_per_policy, max_steps), max_action))
 
 
 def error_obs(env, framework: Optional[str] = None, out=None) -> None:

@@ -28,8 +28,7 @@ from .constants import ACTION_DIM, FRAMEWORK, KINDS, N_AGENTS, OBS_DIMS, QuadCon
 from .spaces import Box
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr
 
 
 # Raw handle of torch's current stream / current device with as little Python as possible: step()
@@ -288,6 +287,23 @@ class QuadVecEnv:
         """[fields, N] view of a zeroed [fields, ld] buffer (the view starts at the buffer's base)."""
         return torch.zeros(fields, self._ld, dtype=dtype, device=self.device)[:, :self.num_envs]
 
+    def _ensure_goal(self) -> torch.Tensor:
+        """The [12, N] goal buffer, made on first use (zeros); launches captured before that hold a null goal pointer: new epoch."""
+        if self._goal is None:
+            self._goal = self._soa(12, torch.float32)
+            self._cenv.goal = self._goal.data_ptr()
+            self._epoch += 1
+        return self._goal
+
+    def _ensure_params(self) -> torch.Tensor:
+        """The [6, N] parameter buffer, made on first use (use_UDM=False: the nominal parameters); new epoch like _ensure_goal."""
+        if self._params is None:
+            self._params = self._soa(6, torch.float32)
+            self._params.copy_(torch.tensor(self.constants.nominal_params, dtype=torch.float32, device=self.device)[:, None].expand(6, self.num_envs))
+            self._cenv.params = self._params.data_ptr()
+            self._epoch += 1
+        return self._params
+
     def _sync_structs(self):
         self._epoch = getattr(self, "_epoch", 0) + 1   # launches captured before this point hold stale pointers / flags (CapturedStep)
         e, o = self._cenv, self._cout
@@ -338,10 +354,9 @@ class QuadVecEnv:
             actions = actions.clone()
         return actions
 
-    def _check_out(self, out: dict, lead: tuple, policy: bool = False):
-        """Caller-owned output tensors are written by raw pointer: validate shape, dtype, device and
-        contiguity (a mismatch would silently corrupt memory)."""
-        N, dev = self.num_envs, self.device
+    def _out_spec(self, lead: tuple, policy: bool = False):
+        """(required, optional) {key: (shape, dtype)} of the output tensors of step(out=) / rollout() / rollout_actor() (policy)."""
+        N = self.num_envs
         want = {"reward": (lead + (N, self.n_agents), torch.float32), "terminated": (lead + (N, self.n_agents), torch.bool)}
         if self.obs_rows or self.kind != "quad":
             want["obs0"] = (lead + (N, self.obs_dims[0]), torch.float32)
@@ -354,6 +369,20 @@ class QuadVecEnv:
                     "final_obs0": (lead + (N, self.obs_dims[0]), torch.float32)}
         if len(self.obs_dims) > 1:
             optional["final_obs1"] = (lead + (N, self.obs_dims[1]), torch.float32)
+        return want, optional
+
+    def _alloc_out(self, lead: tuple, policy: bool = False) -> dict:
+        """What rollout() / rollout_actor() (policy) return without `out`: the required tensors, `truncated`, the policy's `logprob`;
+        the done flags zeroed, the rest uninitialised."""
+        want, optional = self._out_spec(lead, policy)
+        want.update({k: optional[k] for k in (("truncated", "logprob") if policy else ("truncated",))})
+        return {k: (torch.zeros if dt == torch.bool else torch.empty)(shape, dtype=dt, device=self.device) for k, (shape, dt) in want.items()}
+
+    def _check_out(self, out: dict, lead: tuple, policy: bool = False):
+        """Caller-owned output tensors are written by raw pointer: validate shape, dtype, device and
+        contiguity (a mismatch would silently corrupt memory)."""
+        dev = self.device
+        want, optional = self._out_spec(lead, policy)
         if out.get("final_obs0") is not None:
             if not self.auto_reset:
                 raise ValueError("out['final_obs0'] needs auto_reset=True")
@@ -390,11 +419,7 @@ class QuadVecEnv:
             self._last_obs = self._obs()
             return self._last_obs, self._reward, self._done, self._trunc, {}
         self._check_out(out, ())
-        o = _lib.QrStepOut()
-        o.obs0, o.obs1, o.reward = _ptr(out.get("obs0")), _ptr(out.get("obs1")), _ptr(out["reward"])
-        o.reward_raw, o.done = _ptr(out.get("reward_raw")), _ptr(out["terminated"])
-        o.truncated = _ptr(out.get("truncated")) if self._steps is not None else None
-        o.final_obs0, o.final_obs1 = _ptr(out.get("final_obs0")), _ptr(out.get("final_obs1"))
+        o = _lib.step_out(out, self._steps is not None)
         with self._on_device():
             rc = self._lib.qr_step(C.byref(self._cenv), a.data_ptr(), self.substeps, C.byref(o), self._stream())
         _lib.check(rc, "qr_step")
@@ -409,21 +434,12 @@ class QuadVecEnv:
             raise ValueError("rollout actions must be [T, N, A]")
         T = actions.shape[0]
         a = self._check_actions(actions, lead=(T,))
-        N, dev = self.num_envs, self.device
         if out is None:
-            out = {"obs0": torch.empty(T, N, self.obs_dims[0], dtype=torch.float32, device=dev) if self.obs_rows else None,
-                   "reward": torch.empty(T, N, self.n_agents, dtype=torch.float32, device=dev),
-                   "terminated": torch.zeros(T, N, self.n_agents, dtype=torch.bool, device=dev),
-                   "truncated": torch.zeros(T, N, dtype=torch.bool, device=dev)}
-            if self._obs1 is not None:
-                out["obs1"] = torch.empty(T, N, self.obs_dims[1], dtype=torch.float32, device=dev)
+            out = self._alloc_out((T,))
+            out.setdefault("obs0", None)   # Quad-v0 without observation rows
         else:
             self._check_out(out, (T,))
-        o = _lib.QrStepOut()
-        o.obs0, o.obs1, o.reward = _ptr(out.get("obs0")), _ptr(out.get("obs1")), _ptr(out["reward"])
-        o.reward_raw, o.done = _ptr(out.get("reward_raw")), _ptr(out["terminated"])
-        o.truncated = _ptr(out["truncated"]) if self._steps is not None else None
-        o.final_obs0, o.final_obs1 = _ptr(out.get("final_obs0")), _ptr(out.get("final_obs1"))
+        o = _lib.step_out(out, self._steps is not None)
         with self._on_device():
             rc = self._lib.qr_rollout(C.byref(self._cenv), a.data_ptr(), T, self.substeps, C.byref(o), self._stream())
         _lib.check(rc, "qr_rollout")
@@ -455,30 +471,14 @@ class QuadVecEnv:
             if tuple(noise.shape) != (T, N, A) or noise.dtype != torch.float32 or noise.device != dev or not noise.is_contiguous():
                 raise ValueError(f"noise must be contiguous float32 [{T}, {N}, {A}] on {dev}")
         if out is None:
-            out = {"obs0": torch.empty(T, N, self.obs_dims[0], dtype=torch.float32, device=dev),
-                   "action": torch.empty(T, N, A, dtype=torch.float32, device=dev),
-                   "logprob": torch.empty(T, N, A, dtype=torch.float32, device=dev),
-                   "reward": torch.empty(T, N, self.n_agents, dtype=torch.float32, device=dev),
-                   "terminated": torch.zeros(T, N, self.n_agents, dtype=torch.bool, device=dev),
-                   "truncated": torch.zeros(T, N, dtype=torch.bool, device=dev)}
-            if len(self.obs_dims) > 1:
-                out["obs1"] = torch.empty(T, N, self.obs_dims[1], dtype=torch.float32, device=dev)
+            out = self._alloc_out((T,), policy=True)
         else:
             self._check_out(out, (T,), policy=True)
-        arr = _policy.c_actor_array(actors)
-        pol = _lib.QrPolicyRollout()
-        pol.actors = arr
-        pol.obs0_in, pol.obs1_in = obs[0].data_ptr(), (obs[1].data_ptr() if len(obs) > 1 else None)
-        pol.noise = _ptr(noise)
-        pol.noise_seed = (self.seed if noise_seed is None else int(noise_seed)) & (2 ** 64 - 1)
-        pol.step_base = self._policy_steps
-        pol.max_action, pol.deterministic = float(max_action), int(bool(deterministic))
-        pol.action_out, pol.logprob_out = out["action"].data_ptr(), _ptr(out.get("logprob"))
-        o = _lib.QrStepOut()
-        o.obs0, o.obs1, o.reward = _ptr(out.get("obs0")), _ptr(out.get("obs1")), _ptr(out["reward"])
-        o.reward_raw, o.done = _ptr(out.get("reward_raw")), _ptr(out["terminated"])
-        o.truncated = _ptr(out["truncated"]) if self._steps is not None else None
-        o.final_obs0, o.final_obs1 = _ptr(out.get("final_obs0")), _ptr(out.get("final_obs1"))
+        arr = _policy.c_actor_array(actors)   # (kept alive here: the struct only points at it)
+        pol = _lib.policy_rollout(arr, obs, action_out=out["action"], logprob_out=out.get("logprob"), noise=noise,
+                                  noise_seed=self.seed if noise_seed is None else noise_seed, step_base=self._policy_steps,
+                                  max_action=max_action, deterministic=deterministic)
+        o = _lib.step_out(out, self._steps is not None)
         with self._on_device():
             rc = self._lib.qr_rollout_actor(C.byref(self._cenv), C.byref(pol), T, self.substeps, C.byref(o), self._stream())
         _lib.check(rc, "qr_rollout_actor")
@@ -586,14 +586,8 @@ class QuadVecEnv:
                 continue
             if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
                 raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shape} on {dev}")
-        pol = _lib.QrPolicyRollout()
-        pol.actors = arr
-        pol.obs0_in, pol.obs1_in = obs[0].data_ptr(), (obs[1].data_ptr() if len(obs) > 1 else None)
-        pol.max_action, pol.deterministic, pol.action_out = float(max_action), 1, _ptr(out.get("action"))
-        o = _lib.QrEvalOut()
-        o.episode_return, o.benchmark, o.length = _ptr(out["episode_return"]), _ptr(out["benchmark"]), _ptr(out["length"])
-        o.terminated, o.success, o.final_error = _ptr(out["terminated"]), _ptr(out["success"]), _ptr(out.get("final_error"))
-        o.obs0, o.obs1 = _ptr(out["obs0"]), _ptr(out.get("obs1"))
+        pol = _lib.policy_rollout(arr, obs, action_out=out.get("action"), max_action=max_action, deterministic=True)
+        o = _lib.eval_out(out)
         with self._on_device():
             if pop is None:
                 rc = self._lib.qr_evaluate_actor(C.byref(self._cenv), C.byref(pol), T, self.substeps, C.byref(o), self._stream())
@@ -768,10 +762,7 @@ class QuadVecEnv:
         """quad.py:413-418.  b1d_dot is accepted and ignored (unused by the step path)."""
         if self.goal_mode is not None:
             raise RuntimeError("this env generates its goals on the device (goal_mode); set_goal_state() would be ignored by step()")
-        if self._goal is None:
-            self._goal = self._soa(12, torch.float32)
-            self._cenv.goal = self._goal.data_ptr()
-            self._epoch += 1
+        self._ensure_goal()
         self._goal[0:3] = self._rows3(xd, "xd")
         self._goal[3:6] = self._rows3(vd, "vd")
         self._goal[6:9] = self._rows3(b1d, "b1d")
@@ -805,10 +796,8 @@ class QuadVecEnv:
             raise RuntimeError("get_desired needs a goal_mode (0..6)")
         rows = torch.zeros(self.num_envs, 15, dtype=torch.float32, device=self.device)
         m = None if mask is None else torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-        if store_goal and self._goal is None:
-            self._goal = self._soa(12, torch.float32)
-            self._cenv.goal = self._goal.data_ptr()
-            self._epoch += 1
+        if store_goal:
+            self._ensure_goal()
         with self._on_device():
             _lib.check(self._lib.qr_get_desired(C.byref(self._cenv), _ptr(m), rows.data_ptr(), int(store_goal), self._stream()), "qr_get_desired")
         return rows[:, 0:3], rows[:, 3:6], rows[:, 6:9], rows[:, 9:12], rows[:, 12:15]
@@ -861,12 +850,7 @@ class QuadVecEnv:
         if integ_src is not None:
             put(self._integ, integ_src)
         if params_src is not None:
-            if self._params is None:
-                self._params = self._soa(6, torch.float32)
-                self._params.copy_(torch.tensor(self.constants.nominal_params, dtype=torch.float32, device=self.device)[:, None].expand(6, self.num_envs))
-                self._cenv.params = self._params.data_ptr()
-                self._epoch += 1
-            put(self._params, params_src)
+            put(self._ensure_params(), params_src)
 
     def final_observation(self):
         """Terminal observation rows of the envs re-sampled by the LAST step() (final_obs=True): rows of

@@ -49,11 +49,9 @@ class _Flight:
         self.pad[self.idx.reshape(-1)] = False
         assert int(self.pad.sum()) == P * (self.epad - E)
         for k in SOA:
+            if k == "goal" and self.sd[k] is not None:   # (the goal buffer of a stateless mode: made by get_desired(store_goal=True))
+                env._ensure_goal()
             buf = getattr(env, "_" + k)
-            if buf is None and self.sd[k] is not None:   # (the goal buffer of a stateless mode: made by get_desired(store_goal=True))
-                buf = env._soa(self.sd[k].shape[0], self.sd[k].dtype)
-                setattr(env, "_" + k, buf)
-                env._sync_structs()
             if buf is not None:
                 buf[:, self.pad] = float("nan")
                 population_tile(self.sd[k], P, E, buf, env_dim=1)

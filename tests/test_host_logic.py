@@ -839,3 +839,77 @@ def test_launch_cache_roundtrip_and_near_threshold(tmp_path, monkeypatch):
     assert lc.path() is None and lc.lookup(k1) is None and not lc.store(k1, {"picked": "helper"})
     monkeypatch.delenv("QR_LAUNCH_CACHE")
     assert lc.path().endswith(os.path.join(".cache", "gym_rotor_amd", "launch.json"))
+
+
+# ---- the launch-struct builders of _lib (CPU tensors have a data_ptr(): no GPU involved) -----------------------------------
+# The two places where a struct member is NOT filled from the mapping entry of its own name:
+STEP_OUT_KEY = {"done": "terminated"}    # QrStepOut.done is the `terminated` tensor of every caller-facing dict
+POLICY_SCALARS = {"noise_seed", "step_base", "max_action", "deterministic"}   # QrPolicyRollout: values, not tensors; and all of
+#                                          its members come from policy_rollout's arguments (actors_c, obs, keywords), not a dict
+
+
+def _distinct(names):
+    """One small tensor per name, every data_ptr() different and non-zero."""
+    ts = {n: torch.zeros(4) for n in names}
+    assert len({t.data_ptr() for t in ts.values()}) == len(ts) and all(t.data_ptr() for t in ts.values())
+    return ts
+
+
+def _members(struct):
+    return [n for n, _ in struct._fields_]
+
+
+def test_step_out_builder_maps_every_member():
+    L = _lib()
+    keys = [STEP_OUT_KEY.get(n, n) for n in _members(L.QrStepOut)]
+    assert "done" not in keys and "terminated" in keys
+    ts = _distinct(keys)
+    o = L.step_out(ts, True)
+    for n, k in zip(_members(L.QrStepOut), keys):     # (a member added later without a tensor of its name fails here)
+        assert getattr(o, n) == ts[k].data_ptr(), n
+    o = L.step_out(ts, False)                          # no step counter: `truncated` is null, and only it
+    for n, k in zip(_members(L.QrStepOut), keys):
+        assert getattr(o, n) == (None if n == "truncated" else ts[k].data_ptr()), n
+    for gone in keys:                                  # an absent key and a None entry: that member null, the others as before
+        for sparse in ({k: t for k, t in ts.items() if k != gone}, {**ts, gone: None}):
+            o = L.step_out(sparse, True)
+            for n, k in zip(_members(L.QrStepOut), keys):
+                assert getattr(o, n) == (None if k == gone else ts[k].data_ptr()), (gone, n)
+    assert all(getattr(L.step_out({}, True), n) is None for n in _members(L.QrStepOut))
+
+
+def test_eval_out_builder_maps_every_member():
+    L = _lib()
+    names = _members(L.QrEvalOut)
+    ts = _distinct(names)
+    o = L.eval_out(ts)
+    for n in names:
+        assert getattr(o, n) == ts[n].data_ptr(), n
+    for gone in names:
+        for sparse in ({k: t for k, t in ts.items() if k != gone}, {**ts, gone: None}):
+            o = L.eval_out(sparse)
+            for n in names:
+                assert getattr(o, n) == (None if n == gone else ts[n].data_ptr()), (gone, n)
+
+
+def test_policy_rollout_builder_maps_every_member():
+    L = _lib()
+    names = _members(L.QrPolicyRollout)
+    pointers = [n for n in names if n != "actors" and n not in POLICY_SCALARS]
+    assert set(pointers) == {"obs0_in", "obs1_in", "noise", "action_out", "logprob_out"}   # a new member needs a line below
+    ts = _distinct(pointers)
+    arr = (L.QrActor * 2)()
+    p = L.policy_rollout(arr, [ts["obs0_in"], ts["obs1_in"]], action_out=ts["action_out"], logprob_out=ts["logprob_out"], noise=ts["noise"],
+                         noise_seed=2 ** 64 + 5, step_base=7, max_action=0.5, deterministic=True)
+    assert C.addressof(p.actors.contents) == C.addressof(arr)
+    for n in pointers:
+        assert getattr(p, n) == ts[n].data_ptr(), n
+    assert (p.noise_seed, p.step_base, p.max_action, p.deterministic) == (5, 7, 0.5, 1)
+    assert L.policy_rollout(arr, [ts["obs0_in"]], action_out=None, noise_seed=-1).noise_seed == 2 ** 64 - 1   # masked, not an error
+    for flag, want in ((False, 0), (True, 1), (0, 0), (3, 1), (torch.tensor(True), 1)):
+        assert L.policy_rollout(arr, [ts["obs0_in"]], action_out=None, deterministic=flag).deterministic == want
+    for obs in ([ts["obs0_in"]], (ts["obs0_in"], None)):      # one observation tensor, or the ops' (obs0_in, None)
+        p = L.policy_rollout(arr, obs, action_out=ts["action_out"])    # the defaults: what an evaluate launch leaves out
+        assert p.obs0_in == ts["obs0_in"].data_ptr() and p.action_out == ts["action_out"].data_ptr()
+        assert all(getattr(p, n) is None for n in ("obs1_in", "noise", "logprob_out"))
+        assert (p.noise_seed, p.step_base, p.max_action, p.deterministic) == (0, 0, 1.0, 0)

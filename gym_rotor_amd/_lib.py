@@ -31,7 +31,8 @@ ERRORS = {-1: "QR_E_NULL: a required pointer is NULL", -2: "QR_E_KIND: bad env k
 SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_error_obs_format", "qr_reset", "qr_get_state", "qr_set_state", "qr_check_state",
            "qr_traj_start", "qr_get_desired", "qr_gae",
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
-           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population")
+           "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
+           "qr_critic_values", "qr_critic_next_values")
 
 
 class QrCoeffs(C.Structure):
@@ -81,6 +82,15 @@ class QrEvalOut(C.Structure):
 
 class QrPopulation(C.Structure):
     _fields_ = [("n_policies", C.c_int32), ("envs_per_policy", C.c_int32)]
+
+
+class QrCritic(C.Structure):
+    _fields_ = [("fc1_w", C.c_void_p), ("fc1_b", C.c_void_p), ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p),
+                ("fc3_w", C.c_void_p), ("fc3_b", C.c_void_p),
+                ("in0", C.c_int32), ("in1", C.c_int32), ("hidden_dim", C.c_int32), ("reserved0", C.c_int32)]
+
+
+CRITIC_MAX_IN, CRITIC_MAX_HIDDEN = 24, 64   # qr_critic_values: padded input width, padded hidden width
 
 
 def ptr(t):
@@ -174,6 +184,11 @@ def load():
     lib.qr_gae.restype = C.c_int
     lib.qr_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_float,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.qr_critic_values.restype = C.c_int
+    lib.qr_critic_values.argtypes = [P(QrCritic), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.qr_critic_next_values.restype = C.c_int
+    lib.qr_critic_next_values.argtypes = [P(QrCritic), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

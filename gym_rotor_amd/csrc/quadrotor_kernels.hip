@@ -42,6 +42,7 @@
 //   qr_step.h      launch thresholds, Quad-v0 reward / termination, the helper wave, step_kernel (step / rollout)
 //   qr_eval.h      batched policy evaluation (qr_evaluate_actor, qr_evaluate_population): eval_kernel
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
+//   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -59,9 +60,48 @@
 #include "qr_step.h"
 #include "qr_eval.h"
 #include "qr_aux.h"
+#include "qr_critic.h"
 #include "qr_launch.h"
 
+namespace qr {
+// Argument checks and the launch of both critic entry points; done = NULL: the values mode.
+static int do_critic(const QrCritic* c, const float* rows0, const float* rows1, const uint8_t* done, int32_t n_agents, const uint8_t* truncated,
+                     int64_t n_rows, int64_t n_envs, const float* value, float* out, int32_t stride, bool next, void* stream) {
+  if (!c) return QR_E_NULL;
+  if (c->in0 < 0 || c->in1 < 0 || c->in0 > kCriticIn || c->in1 > kCriticIn || c->in0 + c->in1 < 1 || c->in0 + c->in1 > kCriticIn) return QR_E_SIZE;
+  if (c->hidden_dim < 1 || c->hidden_dim > 64 || n_rows < 0 || n_envs < 0 || stride < 1 || (next && n_agents < 1)) return QR_E_SIZE;
+  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b || !out) return QR_E_NULL;
+  if ((c->in0 && !rows0) || (c->in1 && !rows1) || (next && (!done || !value))) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, rows0, rows1, value, out};
+  for (const void* p : floats)
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
+  if (n_rows == 0) return 0;
+  const CriticArgs a{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->in0 ? rows0 : nullptr, c->in1 ? rows1 : nullptr,
+                     done, truncated, value, out, n_rows, n_envs, c->in0, c->in1, c->hidden_dim, stride, n_agents};
+  // grid-stride over the tiles: at most the waves that are resident at once, two per SIMD (256 CUs x 4 SIMDs x 2)
+  const int64_t tiles = (n_rows + 63) / 64;
+  const dim3 grid((unsigned)(tiles < 2048 ? tiles : 2048));
+  if (next) hipLaunchKernelGGL(critic_kernel<true>, grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(critic_kernel<false>, grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+}  // namespace qr
+
 extern "C" {
+
+int qr_critic_values(const QrCritic* critic, const float* obs0, const float* obs1, int64_t n_rows, float* value, int32_t value_stride,
+                     void* stream) {
+  return qr::do_critic(critic, obs0, obs1, nullptr, 0, nullptr, n_rows, 0, nullptr, value, value_stride, false, stream);
+}
+
+int qr_critic_next_values(const QrCritic* critic, const float* final_obs0, const float* final_obs1, const uint8_t* done, int32_t n_agents,
+                          const uint8_t* truncated, int32_t n_steps, int64_t n_envs, const float* value, float* next_value,
+                          int32_t value_stride, void* stream) {
+  if (!critic) return QR_E_NULL;
+  if (n_steps < 1) return QR_E_SIZE;
+  return qr::do_critic(critic, final_obs0, final_obs1, done, n_agents, truncated, n_envs < 0 ? n_envs : (int64_t)n_steps * n_envs, n_envs, value,
+                       next_value, value_stride, true, stream);
+}
 
 #ifdef QR_SPAN
 int qr_debug_set_span(void* buf) {  // diagnostic build only: device buffer [slots][2 * tiles][2] of uint64 (NULL = off) for the NEXT launches

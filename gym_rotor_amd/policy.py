@@ -1,4 +1,5 @@
-"""Actor parameters for the policy-in-the-loop rollout (`QuadVecEnv.rollout_actor`).
+"""Actor parameters for the policy-in-the-loop rollout (`QuadVecEnv.rollout_actor`), critic parameters for the on-device values
+of a horizon (`RolloutStorage.compute_values`).
 
 The networks are the reference's MLP actors: `MLP_Actor_PPO` (algos/ppo/ppo_mlp.py:6-58: fc1 -> relu
 -> fc2 -> relu -> mean_linear -> tanh, plus a state-independent `log_std`), `MLP_Actor_TD3`
@@ -107,6 +108,147 @@ class ActorParams:
         q.obs_dim, q.hidden_dim, q.action_dim = self.dims
         q.squash = int(self.squash)
         return q
+
+
+@dataclass
+class CriticParams:
+    """One agent's critic for `RolloutStorage.compute_values`: the reference's `MLP_Critic` / `MLP_Critic_CTDE`
+    (algos/ppo/ppo_mlp.py:64-126: fc1 -> tanh -> fc2 -> tanh -> fc3), any input width up to 24 and hidden width up to 64.
+    The tensors are the module's own (contiguous float32, torch.nn.Linear layout), used by the kernel in place.
+    inputs: which agents' observation rows form the input row, in order — (0,) or (1,): that agent's own row (MLP_Critic);
+    (0, 1): both rows concatenated (MLP_Critic_CTDE's torch.cat)."""
+    fc1_w: torch.Tensor
+    fc1_b: torch.Tensor
+    fc2_w: torch.Tensor
+    fc2_b: torch.Tensor
+    fc3_w: torch.Tensor
+    fc3_b: torch.Tensor
+    inputs: tuple = (0,)
+
+    NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
+
+    def __post_init__(self):
+        self.inputs = tuple(int(i) for i in self.inputs)
+        if self.inputs not in ((0,), (1,), (0, 1)):
+            raise ValueError(f"critic inputs must be (0,), (1,) or (0, 1), got {self.inputs}")
+        if self.fc1_w.dim() != 2:
+            raise ValueError("critic tensor fc1_w must be [hidden, in]")
+        hidden, din = self.fc1_w.shape
+        if not 1 <= din <= _lib.CRITIC_MAX_IN or not 1 <= hidden <= _lib.CRITIC_MAX_HIDDEN:
+            raise ValueError(f"critic sizes in = {din}, hidden = {hidden} are outside 1..{_lib.CRITIC_MAX_IN} / 1..{_lib.CRITIC_MAX_HIDDEN}")
+        shapes = {"fc1_w": (hidden, din), "fc1_b": (hidden,), "fc2_w": (hidden, hidden), "fc2_b": (hidden,), "fc3_w": (1, hidden), "fc3_b": (1,)}
+        for n in self.NAMES:
+            t = getattr(self, n)
+            if tuple(t.shape) != shapes[n] or t.dtype != torch.float32 or t.device != self.fc1_w.device or not t.is_contiguous():
+                raise ValueError(f"critic tensor {n} must be a contiguous float32 {shapes[n]} tensor on {self.fc1_w.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    @property
+    def dims(self):
+        """(input width, hidden width)"""
+        return (self.fc1_w.shape[1], self.fc1_w.shape[0])
+
+    @property
+    def device(self):
+        return self.fc1_w.device
+
+    @classmethod
+    def from_module(cls, critic, inputs=(0,)) -> "CriticParams":
+        """From a module shaped like the reference's critics (attributes fc1, fc2, fc3)."""
+        return cls(critic.fc1.weight.data, critic.fc1.bias.data, critic.fc2.weight.data, critic.fc2.bias.data,
+                   critic.fc3.weight.data, critic.fc3.bias.data, inputs)
+
+    def as_c(self, row_widths: Sequence[int]) -> _lib.QrCritic:
+        """The launch struct for observation rows of these widths (one per agent): in0 / in1 are the widths of the rows this
+        critic reads, 0 for the others."""
+        take = [int(row_widths[k]) if k in self.inputs and k < len(row_widths) else 0 for k in range(2)]
+        if max(self.inputs) >= len(row_widths) or sum(take) != self.dims[0]:
+            raise ValueError(f"critic with inputs {self.inputs} reads {self.dims[0]} columns, the observation rows are {list(row_widths)} wide")
+        q = _lib.QrCritic()
+        for n in self.NAMES:
+            setattr(q, n, getattr(self, n).data_ptr())
+        q.in0, q.in1 = take
+        q.hidden_dim = self.dims[1]
+        return q
+
+
+def _element_stride(t: torch.Tensor, what: str) -> int:
+    """The one stride between consecutive elements of `t` in row-major order (a column of a contiguous [.., n_agents] tensor)."""
+    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]
+    for (_, s), (n1, s1) in zip(dims, dims[1:]):
+        if s != s1 * n1:
+            raise ValueError(f"{what} must have one element stride (a column of a contiguous tensor), got shape {tuple(t.shape)} strides {t.stride()}")
+    stride = dims[-1][1] if dims else 1
+    if stride < 1:
+        raise ValueError(f"{what} must have a positive element stride")
+    return stride
+
+
+def _critic_launch_args(critic: CriticParams, rows, n_rows: int, value: torch.Tensor, what: str):
+    dev = value.device
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if critic.device != dev:
+        raise ValueError(f"{what}: the critic's tensors are on {critic.device}, the values on {dev}")
+    rows = list(rows) + [None] * (2 - len(rows))
+    widths = []
+    for k, r in enumerate(rows[:2]):
+        if r is None:
+            widths.append(0)
+            continue
+        if r.dtype != torch.float32 or r.device != dev or not r.is_contiguous() or r.dim() < 2 or r[..., 0].numel() != n_rows:
+            raise ValueError(f"{what}: observation rows {k} must be contiguous float32 [{n_rows} rows, D] on {dev}")
+        widths.append(r.shape[-1])
+    while widths and widths[-1] == 0:
+        widths.pop()
+    q = critic.as_c(widths)
+    return q, (_lib.ptr(rows[0]) if q.in0 else None), (_lib.ptr(rows[1]) if q.in1 else None)
+
+
+def critic_values(critic: CriticParams, obs, value: torch.Tensor) -> None:
+    """value.flatten()[i] = V(row i) in one launch (qr_critic_values).  obs: the per-agent observation row tensors [.., D_k]
+    (contiguous float32; an agent the critic does not read may be None); value: float32, one element per row, with ONE element
+    stride — e.g. `storage.value[..., k]`."""
+    if value.dtype != torch.float32:
+        raise ValueError("critic_values: value must be float32")
+    n_rows, stride = value.numel(), _element_stride(value, "value")
+    q, p0, p1 = _critic_launch_args(critic, obs, n_rows, value, "critic_values")
+    if n_rows == 0:   # nothing to launch (and an empty tensor has no address to pass)
+        return
+    with torch.cuda.device(value.device):
+        rc = _lib.load().qr_critic_values(C.byref(q), p0, p1, n_rows, value.data_ptr(), stride,
+                                          torch.cuda.current_stream(value.device).cuda_stream)
+    _lib.check(rc, "qr_critic_values")
+
+
+def critic_next_values(critic: CriticParams, final_obs, done: torch.Tensor, truncated: Optional[torch.Tensor], value: torch.Tensor,
+                       next_value: torch.Tensor) -> None:
+    """next_value[t, n] = V(final_obs[t, n]) where the env was re-sampled in step t (any agent's done, or truncated), value[t+1, n]
+    elsewhere, in one launch (qr_critic_next_values).  final_obs: per-agent [T, N, D_k]; done [T, N, n_agents] bool / uint8;
+    truncated [T, N] or None; value [T+1, N] and next_value [T, N] float32 with the same single element stride."""
+    if next_value.dim() != 2 or value.dim() != 2:
+        raise ValueError("critic_next_values: value must be [T+1, N] and next_value [T, N]")
+    T, N = next_value.shape
+    dev = next_value.device
+    if value.dtype != torch.float32 or next_value.dtype != torch.float32 or value.device != dev or tuple(value.shape) != (T + 1, N):
+        raise ValueError(f"critic_next_values: value must be float32 [{T + 1}, {N}] and next_value float32 [{T}, {N}] on one device")
+    stride = _element_stride(next_value, "next_value")
+    if T * N > 1 and _element_stride(value, "value") != stride:
+        raise ValueError("critic_next_values: value and next_value must have the same element stride")
+    flags = [("done", done, 3)] + ([("truncated", truncated, 2)] if truncated is not None else [])
+    for name, t, nd in flags:
+        if t.dtype not in (torch.bool, torch.uint8) or t.device != dev or not t.is_contiguous() or t.dim() != nd or tuple(t.shape[:2]) != (T, N):
+            raise ValueError(f"critic_next_values: {name} must be contiguous bool / uint8 [{T}, {N}{', n_agents' if nd == 3 else ''}] on {dev}")
+    if done.shape[2] < 1:
+        raise ValueError("critic_next_values: done needs at least one agent column")
+    q, p0, p1 = _critic_launch_args(critic, final_obs, T * N, next_value, "critic_next_values")
+    if T >= 1 and N == 0:
+        return
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_critic_next_values(C.byref(q), p0, p1, done.data_ptr(), done.shape[2], _lib.ptr(truncated), T, N,
+                                               value.data_ptr(), next_value.data_ptr(), stride,
+                                               torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_critic_next_values")
 
 
 def c_actor_array(actors: Sequence[ActorParams]):

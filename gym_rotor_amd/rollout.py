@@ -5,7 +5,8 @@ Batched replacement of the reference's PPO data path: `ReplayBuffer` (NumPy arra
 and the Python GAE loop + advantage normalisation in `PPO.train` (algos/ppo/ppo.py:134-147).
 Transitions of N envs stay on the GPU as `[T, N, ...]` tensors; `QuadVecEnv.step(..., out=slot)`
 writes observation / reward / done rows straight into them; GAE is one HIP launch
-(`qr_gae`: reverse scan over T per (env, agent) column).  Normalisation statistics can be
+(`qr_gae`: reverse scan over T per (env, agent) column), and so are the critic's values between the two
+(`qr_critic_values`, `qr_critic_next_values`: `compute_values`).  Normalisation statistics can be
 all-reduced over the env shards (RCCL when launched under torchrun; gloo in the CPU tests).
 """
 from __future__ import annotations
@@ -112,6 +113,26 @@ class RolloutStorage:
             rows = [f[idx] for f in self.final_obs]
             nv[idx] = critic(rows).reshape(-1, self.n_agents).to(nv.dtype)
         return nv
+
+    def compute_values(self, critics) -> torch.Tensor:
+        """The critic over the whole horizon on the device: fills `value` with V(obs[t]) for all T+1 rows and returns the
+        reference's V(obs_next), [T, N, n_agents], ready for compute_gae(next_value=...) — what `next_values(module)` gives after
+        the module has filled `value`, without the module, the gather of reset rows or its host synchronisation.
+        critics: one `CriticParams` per agent (`CriticParams.from_module(module, inputs=...)`).  One launch per critic for the
+        values (qr_critic_values) and, with final_obs, one for the next values (qr_critic_next_values); without final_obs the
+        result is the view value[1:]."""
+        from .policy import CriticParams, critic_next_values, critic_values
+        critics = [critics] if isinstance(critics, CriticParams) else list(critics)
+        if len(critics) != self.n_agents:
+            raise ValueError(f"compute_values needs one CriticParams per agent ({self.n_agents}), got {len(critics)}")
+        for k, c in enumerate(critics):
+            critic_values(c, self.obs, self.value[..., k])
+        if self.final_obs is None:
+            return self.value[1:]
+        next_value = torch.empty(self.T, self.N, self.n_agents, dtype=torch.float32, device=self.device)
+        for k, c in enumerate(critics):
+            critic_next_values(c, self.final_obs, self.done, self.truncated, self.value[..., k], next_value[..., k])
+        return next_value
 
     def collect(self, env, actors, **kw) -> dict:
         """One horizon with the actor(s) inside the step kernel (qr_rollout_actor): obs row 0 is the

@@ -281,6 +281,35 @@ def qr_gae(reward: torch.Tensor, done: torch.Tensor, value: torch.Tensor, gamma:
     _lib.check(rc, "qr_gae")
 
 
+def _critic_params(critic: Sequence[torch.Tensor], inputs: Sequence[int]):
+    from .policy import CriticParams
+    if len(critic) != 6:
+        raise ValueError("a critic is 6 tensors: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b")
+    return CriticParams(*critic, tuple(inputs))
+
+
+@torch.library.custom_op(f"{_NS}::qr_critic_values", mutates_args=("value",))
+def qr_critic_values(critic: List[torch.Tensor], inputs: List[int], obs0: Optional[torch.Tensor], obs1: Optional[torch.Tensor],
+                     value: torch.Tensor) -> None:
+    """V(row) of the reference's MLP critic for every observation row (qr_critic_values).  critic = fc1_w, fc1_b, fc2_w, fc2_b, fc3_w,
+    fc3_b; inputs = [0], [1] or [0, 1]: the row tensors it reads (obsK: contiguous float32 [.., D_k]); value: float32, one element
+    per row with one element stride (`values[..., k]` of a contiguous [.., n_agents] tensor)."""
+    from .policy import critic_values
+    _gpu(value)
+    critic_values(_critic_params(critic, inputs), (obs0, obs1), value)
+
+
+@torch.library.custom_op(f"{_NS}::qr_critic_next_values", mutates_args=("next_value",))
+def qr_critic_next_values(critic: List[torch.Tensor], inputs: List[int], final_obs0: Optional[torch.Tensor], final_obs1: Optional[torch.Tensor],
+                          done: torch.Tensor, truncated: Optional[torch.Tensor], value: torch.Tensor, next_value: torch.Tensor) -> None:
+    """The reference's V(obs_next) of a [T, N] horizon (qr_critic_next_values): V(final_obs) where the env was re-sampled (any agent's
+    done [T, N, n_agents], or truncated [T, N]), value[t+1] elsewhere.  value [T+1, N], next_value [T, N]: float32, the same single
+    element stride.  Critic as in qr_critic_values."""
+    from .policy import critic_next_values
+    _gpu(next_value)
+    critic_next_values(_critic_params(critic, inputs), (final_obs0, final_obs1), done, truncated, value, next_value)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

@@ -396,6 +396,35 @@ int qr_gae(const float* reward, const uint8_t* done, const float* value, const f
            int32_t n_steps, int64_t n_cols, float gamma, float lam,
            float* advantage, float* td_target, double* partials, void* stream);
 
+/* The reference's MLP critics for a whole PPO horizon, between the collection launch and qr_gae:
+ *     v = fc3(tanh(fc2(tanh(fc1(x)))))        MLP_Critic / MLP_Critic_CTDE, algos/ppo/ppo_mlp.py:64-126
+ * on float32 AoS rows, weights in torch.nn.Linear layout, used in place.  The input row x is the first in0 columns of the
+ * obs0 row followed by the first in1 columns of the obs1 row (MLP_Critic_CTDE's torch.cat); in0 / in1 are 0 or the full
+ * width of that row tensor, which is also its row stride.  1 <= in0 + in1 <= 24, 1 <= hidden_dim <= 64. */
+typedef struct QrCritic {
+  const float *fc1_w, *fc1_b;       /* [hidden][in0+in1], [hidden] */
+  const float *fc2_w, *fc2_b;       /* [hidden][hidden],  [hidden] */
+  const float *fc3_w, *fc3_b;       /* [1][hidden], [1]            */
+  int32_t in0, in1;                 /* columns taken from the obs0 / obs1 rows: 0 or the full row width */
+  int32_t hidden_dim, reserved0;
+} QrCritic;
+/* value[i * value_stride] = V(row i) for i < n_rows — agent k's critic writes column k of a [.., n_agents] tensor with
+ * value = base + k, value_stride = n_agents.  One launch; n_rows = 0 launches nothing.  QR_E_NULL for a NULL critic, weight or
+ * value pointer, or a NULL row pointer whose in0 / in1 is not 0; QR_E_SIZE for sizes outside the ranges above, n_rows < 0 or
+ * value_stride < 1; QR_E_ALIGN for a float pointer that is not 4-byte aligned. */
+int qr_critic_values(const QrCritic* critic, const float* obs0, const float* obs1, int64_t n_rows,
+                     float* value, int32_t value_stride, void* stream);
+/* The reference's V(obs_next) (ppo.py:128-131) for the [T][N] transitions of an auto-resetting env, one launch:
+ *     next_value[t][n] = reset(t, n) ? V(final_obs[t][n]) : value[t+1][n],   reset = any of done[t][n][0..n_agents) or truncated[t][n]
+ * value is [T+1][N] (row t+1 = V of the observation after step t, filled by the call above), next_value [T][N], both with element
+ * stride value_stride; final_obs0 / final_obs1 [T][N][in0 / in1] (QrStepOut.final_obs*), done [T][N][n_agents], truncated [T][N] or
+ * NULL.  The choice is a select: rows of final_obs of envs that did not reset are never used, whatever they hold.  Errors as
+ * above, and QR_E_SIZE for n_steps < 1, n_envs < 0 or n_agents < 1; n_envs = 0 launches nothing. */
+int qr_critic_next_values(const QrCritic* critic, const float* final_obs0, const float* final_obs1,
+                          const uint8_t* done, int32_t n_agents, const uint8_t* truncated,
+                          int32_t n_steps, int64_t n_envs, const float* value, float* next_value,
+                          int32_t value_stride, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

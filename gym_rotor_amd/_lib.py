@@ -32,7 +32,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_traj_start", "qr_get_desired", "qr_gae",
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
-           "qr_critic_values", "qr_critic_next_values")
+           "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -91,6 +91,23 @@ class QrCritic(C.Structure):
 
 
 CRITIC_MAX_IN, CRITIC_MAX_HIDDEN = 24, 64   # qr_critic_values: padded input width, padded hidden width
+
+
+class QrPpoBatch(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("final_obs", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p),
+                ("action", C.c_void_p), ("logp_old", C.c_void_p), ("advantage", C.c_void_p), ("index", C.c_void_p),
+                ("noise", C.c_void_p), ("nominal", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("batch", C.c_int64), ("n_envs", C.c_int64), ("n_steps", C.c_int32), ("n_agents", C.c_int32),
+                ("row_stride", C.c_int32), ("col_offset", C.c_int32), ("adv_stride", C.c_int32), ("max_workgroups", C.c_int32),
+                ("clip", C.c_float), ("entropy_coef", C.c_float), ("lam_T", C.c_float), ("lam_S", C.c_float), ("lam_M", C.c_float),
+                ("max_action", C.c_float)]
+
+
+PPO_GRAD_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mean_w", "mean_b", "log_std")   # qr_ppo_actor_grad: the gradient tensors, in order
+
+
+class QrPpoGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PPO_GRAD_NAMES + ("stats",)]
 
 
 def ptr(t):
@@ -189,6 +206,10 @@ def load():
     lib.qr_critic_next_values.restype = C.c_int
     lib.qr_critic_next_values.argtypes = [P(QrCritic), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.qr_ppo_actor_grad.restype = C.c_int
+    lib.qr_ppo_actor_grad.argtypes = [P(QrActor), P(QrPpoBatch), P(QrPpoGrad), C.c_void_p]
+    lib.qr_ppo_actor_workspace_bytes.restype = C.c_int64
+    lib.qr_ppo_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -43,6 +43,7 @@
 //   qr_eval.h      batched policy evaluation (qr_evaluate_actor, qr_evaluate_population): eval_kernel
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
 //   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
+//   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -61,6 +62,7 @@
 #include "qr_eval.h"
 #include "qr_aux.h"
 #include "qr_critic.h"
+#include "qr_ppo.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -85,9 +87,81 @@ static int do_critic(const QrCritic* c, const float* rows0, const float* rows1, 
   else hipLaunchKernelGGL(critic_kernel<false>, grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
+
+// The grid of qr_ppo_actor_grad: a function of the batch and max_workgroups only (0: the waves resident at once, one per SIMD at
+// the kernel's register count: 256 CUs x 4).
+static int64_t ppo_grid(int64_t batch, int32_t max_workgroups) {
+  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : 1024;
+  return tiles < cap ? tiles : cap;
+}
+
+static int ppo_np(int32_t d, int32_t h, int32_t a) {  // length of a partial vector; 0: not one of the rollout's actor sizes
+  if (d == 23 && h == 16 && a == 4) return PpoLayout<23, 16, 4>::NP;
+  if (d == 15 && h == 16 && a == 4) return PpoLayout<15, 16, 4>::NP;
+  if (d == 3 && h == 4 && a == 1) return PpoLayout<3, 4, 1>::NP;
+  return 0;
+}
+
+static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* g, void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  if (c->squash != QR_ACTOR_TANH_MEAN || c->log_std_w || c->log_std_b) return QR_E_KIND;
+  const int np = ppo_np(c->obs_dim, c->hidden_dim, c->action_dim);
+  if (!np || b->batch < 1 || b->n_steps < 1 || b->n_envs < 1 || b->row_stride < 1 || b->adv_stride < 1 || b->max_workgroups < 0) return QR_E_SIZE;
+  if (b->col_offset < 0 || b->col_offset + c->action_dim > b->row_stride || (b->final_obs && b->n_agents < 1)) return QR_E_SIZE;
+  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->mean_w || !c->mean_b || !c->log_std) return QR_E_NULL;
+  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->mean_w || !g->mean_b || !g->log_std || !g->stats) return QR_E_NULL;
+  if (!b->obs || !b->action || !b->logp_old || !b->advantage || !b->workspace || (b->final_obs && !b->done)) return QR_E_NULL;
+  if ((b->lam_S != 0.0f && !b->noise) || (b->lam_M != 0.0f && !b->nominal)) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->mean_w, c->mean_b, c->log_std, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b,
+                                g->mean_w, g->mean_b, g->log_std, g->stats, b->obs, b->final_obs, b->action, b->logp_old, b->advantage, b->noise,
+                                b->nominal};
+  for (const void* p : floats)
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(b->workspace)) & 7u) return QR_E_ALIGN;
+  const int64_t grid = ppo_grid(b->batch, b->max_workgroups);
+  if (b->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  const int D = c->obs_dim, H = c->hidden_dim, A = c->action_dim;
+  const double B = (double)b->batch, ba = B * A;
+  PpoArgs a{};
+  a.w = ActorW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->mean_w, c->mean_b, c->log_std, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
+  a.obs = b->obs; a.final_obs = b->final_obs; a.done = b->done; a.truncated = b->truncated;
+  a.action = b->action + b->col_offset; a.logp_old = b->logp_old + b->col_offset; a.advantage = b->advantage; a.index = b->index;
+  a.noise = b->lam_S != 0.0f ? b->noise : nullptr; a.nominal = b->lam_M != 0.0f ? b->nominal : nullptr;
+  a.partials = static_cast<double*>(b->workspace);
+  a.B = b->batch; a.N = b->n_envs; a.rows = (int64_t)b->n_steps * b->n_envs;
+  a.act_stride = b->row_stride; a.adv_stride = b->adv_stride; a.n_agents = b->n_agents;
+  a.clip = b->clip; a.max_action = b->max_action; a.lam_T = b->lam_T; a.lam_S = b->lam_S; a.lam_M = b->lam_M;
+  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * b->lam_T / ba); a.c_S = (float)(2.0 * b->lam_S / ba); a.c_M = (float)(2.0 * b->lam_M / ba);
+  PpoReduceArgs r{};
+  r.partials = a.partials;
+  float* const grads[7] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std};
+  const int sizes[7] = {H * D, H, H * H, H, A * H, A, A};
+  for (int k = 0; k < 7; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
+  r.stats = g->stats; r.log_std = c->log_std; r.n_parts = (int32_t)grid; r.np = np; r.action_dim = A; r.B = B;
+  r.entropy_coef = b->entropy_coef; r.lam_T = b->lam_T; r.lam_S = b->lam_S; r.lam_M = b->lam_M;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (D == 23) hipLaunchKernelGGL((ppo_actor_kernel<23, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  else if (D == 15) hipLaunchKernelGGL((ppo_actor_kernel<15, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((ppo_actor_kernel<3, 4, 1>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)((r.off[7] + 3) / 4 + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream) {
+  return qr::do_ppo_actor(actor, batch, grad, stream);
+}
+
+int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups) {
+  const int np = qr::ppo_np(obs_dim, hidden_dim, action_dim);
+  if (!np || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * np * (int64_t)sizeof(double);
+}
 
 int qr_critic_values(const QrCritic* critic, const float* obs0, const float* obs1, int64_t n_rows, float* value, int32_t value_stride,
                      void* stream) {

@@ -1,5 +1,6 @@
 """Actor parameters for the policy-in-the-loop rollout (`QuadVecEnv.rollout_actor`), critic parameters for the on-device values
-of a horizon (`RolloutStorage.compute_values`).
+of a horizon (`RolloutStorage.compute_values`), the PPO actor loss and its gradients for one minibatch (`ppo_actor_grad`,
+`actor_loss`).
 
 The networks are the reference's MLP actors: `MLP_Actor_PPO` (algos/ppo/ppo_mlp.py:6-58: fc1 -> relu
 -> fc2 -> relu -> mean_linear -> tanh, plus a state-independent `log_std`), `MLP_Actor_TD3`
@@ -249,6 +250,154 @@ def critic_next_values(critic: CriticParams, final_obs, done: torch.Tensor, trun
                                                value.data_ptr(), next_value.data_ptr(), stride,
                                                torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "qr_critic_next_values")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the actor half of a PPO minibatch update (qr_ppo_actor_grad)
+# ----------------------------------------------------------------------------------------------------------------
+PPO_ACTOR_DIMS = tuple(d for dims in ACTOR_DIMS.values() for d in dims)   # the sizes qr_ppo_actor_grad is built for
+_GRAD_SHAPES = lambda D, H, A: {"fc1_w": (H, D), "fc1_b": (H,), "fc2_w": (H, H), "fc2_b": (H,), "mean_w": (A, H), "mean_b": (A,), "log_std": (A,)}
+
+
+def ppo_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `ppo_actor_grad` launch needs (qr_ppo_actor_workspace_bytes)."""
+    n = _lib.load().qr_ppo_actor_workspace_bytes(int(dims[0]), int(dims[1]), int(dims[2]), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_ppo_actor_workspace_bytes")
+    return int(n)
+
+
+def _rows_view(t: torch.Tensor, T: int, N: int, A: int, col_offset: int, what: str, dev):
+    """Row stride of a float32 [T, N, >= col_offset + A] tensor whose rows lie one row stride apart (the storage's own [T, N, 5]
+    rows, or a per-agent view of them)."""
+    if t.dtype != torch.float32 or t.device != dev or t.dim() != 3 or tuple(t.shape[:2]) != (T, N) or t.shape[2] < col_offset + A:
+        raise ValueError(f"ppo_actor_grad: {what} must be float32 [{T}, {N}, >= {col_offset + A}] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    rs = t.stride(1)
+    if (t.shape[2] > 1 and t.stride(2) != 1) or rs < t.shape[2] or (T > 1 and t.stride(0) != N * rs):
+        raise ValueError(f"ppo_actor_grad: {what} must be rows of a contiguous [T, N, W] tensor, got strides {t.stride()}")
+    return rs
+
+
+def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, logp_old: torch.Tensor, advantage: torch.Tensor,
+                   index: Optional[torch.Tensor] = None, *, final_obs: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                   truncated: Optional[torch.Tensor] = None, clip: float = 0.2, entropy_coef: float = 0.0, lam_T: float = 0.0,
+                   lam_S: float = 0.0, lam_M: float = 0.0, noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None,
+                   max_action: float = 1.0, col_offset: int = 0, grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None, max_workgroups: int = 0):
+    """PPO's actor loss (ppo.py:169-182 + policy_regularization.py) and its gradients for ONE agent and one minibatch, in one launch
+    plus a small reduction (qr_ppo_actor_grad) — no autograd, no copies of the minibatch's rows.
+    obs [T+1, N, D] contiguous float32 (the storage's rows of this agent); action / logp_old [T, N, ..]: this agent's columns start at
+    `col_offset` of each row (a per-agent view with col_offset = 0, or the storage's [T, N, 5] rows with the agent's offset);
+    advantage: float32, T * N elements with one element stride (`advantage[..., k]`); index: int64 [B] rows of the flat [T * N]
+    transitions, None = all of them in order.  final_obs [T, N, D] with done [T, N, n_agents] (and truncated [T, N]) give the
+    reference's obs_next for lam_T (without them: obs[t + 1]).  noise [D]: the ONE draw of N(0, 0.05) the spatial term adds to every
+    row (required when lam_S != 0); nominal [A]: `RolloutStorage.nominal_action` (required when lam_M != 0).
+    Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std — `grads` given:
+    overwritten in place — and stats float32 [4] = loss, mean surrogate, clip fraction, mean of (rho - 1) - log rho."""
+    dev = obs.device
+    if actor.dims not in PPO_ACTOR_DIMS:
+        raise ValueError(f"ppo_actor_grad: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
+    if actor.squash != _lib.ACTOR_TANH_MEAN or actor.log_std_w is not None or actor.log_std is None:
+        raise ValueError("ppo_actor_grad: the actor must be of MLP_Actor_PPO's form: the tanh-of-mean rule and a log_std parameter, no log_std head")
+    actor.check(actor.dims, dev)
+    D, H, A = actor.dims
+    if obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[0] < 2 or obs.shape[2] != D or not obs.is_contiguous():
+        raise ValueError(f"ppo_actor_grad: obs must be contiguous float32 [T+1, N, {D}], got {obs.dtype} {tuple(obs.shape)}")
+    T, N = obs.shape[0] - 1, obs.shape[1]
+    if N < 1:
+        raise ValueError("ppo_actor_grad: obs holds no env")
+    col_offset = int(col_offset)
+    if col_offset < 0:
+        raise ValueError("ppo_actor_grad: col_offset must be >= 0")
+    rs = _rows_view(action, T, N, A, col_offset, "action", dev)
+    if _rows_view(logp_old, T, N, A, col_offset, "logp_old", dev) != rs:
+        raise ValueError("ppo_actor_grad: action and logp_old must have the same row stride")
+    if advantage.dtype != torch.float32 or advantage.device != dev or advantage.numel() != T * N:
+        raise ValueError(f"ppo_actor_grad: advantage must be float32 with {T * N} elements on {dev}")
+    adv_stride = _element_stride(advantage, "advantage")
+    n_agents = 0
+    if final_obs is not None:
+        if final_obs.dtype != torch.float32 or final_obs.device != dev or tuple(final_obs.shape) != (T, N, D) or not final_obs.is_contiguous():
+            raise ValueError(f"ppo_actor_grad: final_obs must be contiguous float32 [{T}, {N}, {D}] on {dev}")
+        if done is None:
+            raise ValueError("ppo_actor_grad: final_obs needs done")
+        flags = [("done", done, 3)] + ([("truncated", truncated, 2)] if truncated is not None else [])
+        for name, t, nd in flags:
+            if t.dtype not in (torch.bool, torch.uint8) or t.device != dev or not t.is_contiguous() or t.dim() != nd or tuple(t.shape[:2]) != (T, N):
+                raise ValueError(f"ppo_actor_grad: {name} must be contiguous bool / uint8 [{T}, {N}{', n_agents' if nd == 3 else ''}] on {dev}")
+        n_agents = done.shape[2]
+        if n_agents < 1:
+            raise ValueError("ppo_actor_grad: done needs at least one agent column")
+    else:
+        done = truncated = None
+    if index is not None:
+        if index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError(f"ppo_actor_grad: index must be a contiguous int64 [B] tensor on {dev}")
+        B = index.numel()
+    else:
+        B = T * N
+    vecs = {}
+    for name, t, n, lam in (("noise", noise, D, lam_S), ("nominal", nominal, A, lam_M)):
+        if lam == 0:
+            vecs[name] = None
+            continue
+        if t is None:
+            raise ValueError(f"ppo_actor_grad: {name} is required when lam_{'S' if name == 'noise' else 'M'} != 0")
+        if t.dtype != torch.float32 or t.device != dev or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"ppo_actor_grad: {name} must be a contiguous float32 tensor of {n} elements on {dev}")
+        vecs[name] = t
+    shapes = _GRAD_SHAPES(D, H, A)
+    if grads is None:
+        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
+    for n, s in shapes.items():
+        g = grads.get(n)
+        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
+            raise ValueError(f"ppo_actor_grad: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError(f"ppo_actor_grad: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
+        for n in shapes:
+            grads[n].zero_()
+        stats.zero_()
+        return grads, stats
+    need = ppo_workspace_bytes((D, H, A), B, max_workgroups)
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"ppo_actor_grad: workspace must be a contiguous tensor on {dev}")
+    b = _lib.QrPpoBatch()
+    b.obs, b.final_obs, b.done, b.truncated = obs.data_ptr(), _lib.ptr(final_obs), _lib.ptr(done), _lib.ptr(truncated)
+    b.action, b.logp_old, b.advantage, b.index = action.data_ptr(), logp_old.data_ptr(), advantage.data_ptr(), _lib.ptr(index)
+    b.noise, b.nominal = _lib.ptr(vecs["noise"]), _lib.ptr(vecs["nominal"])
+    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    b.batch, b.n_envs, b.n_steps, b.n_agents = B, N, T, n_agents
+    b.row_stride, b.col_offset, b.adv_stride, b.max_workgroups = rs, col_offset, adv_stride, int(max_workgroups)
+    b.clip, b.entropy_coef, b.lam_T, b.lam_S, b.lam_M, b.max_action = (float(v) for v in (clip, entropy_coef, lam_T, lam_S, lam_M, max_action))
+    g = _lib.QrPpoGrad(*[grads[n].data_ptr() for n in _lib.PPO_GRAD_NAMES], stats.data_ptr())
+    q = actor.as_c()
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_ppo_actor_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ppo_actor_grad")
+    return grads, stats
+
+
+def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional[torch.Tensor] = None, **coeffs) -> torch.Tensor:
+    """The actor update of a training loop, as the reference writes it, without autograd: runs `storage.actor_grad` for agent k on the
+    live `module` (attributes fc1, fc2, mean_linear, log_std — its tensors are read in place) and writes the gradients into
+    `module.<param>.grad` in place (log_std in the module's [1, A] shape), as `loss.backward()` after `zero_grad()` leaves them.
+    Returns stats (stats[0] = the loss).  The optimiser step, gradient clipping and the schedule stay torch, on these .grad tensors."""
+    params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.mean_linear.weight, module.mean_linear.bias,
+              module.log_std)
+    grads = {}
+    for n, p in zip(_lib.PPO_GRAD_NAMES, params):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    _, stats = storage.actor_grad(k, ActorParams.from_module(module), advantage, index, grads=grads, **coeffs)
+    return stats
 
 
 def c_actor_array(actors: Sequence[ActorParams]):

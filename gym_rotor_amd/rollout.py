@@ -6,7 +6,8 @@ and the Python GAE loop + advantage normalisation in `PPO.train` (algos/ppo/ppo.
 Transitions of N envs stay on the GPU as `[T, N, ...]` tensors; `QuadVecEnv.step(..., out=slot)`
 writes observation / reward / done rows straight into them; GAE is one HIP launch
 (`qr_gae`: reverse scan over T per (env, agent) column), and so are the critic's values between the two
-(`qr_critic_values`, `qr_critic_next_values`: `compute_values`).  Normalisation statistics can be
+(`qr_critic_values`, `qr_critic_next_values`: `compute_values`), and so is the actor's loss with its gradients per minibatch
+(`qr_ppo_actor_grad`: `actor_grad`).  Normalisation statistics can be
 all-reduced over the env shards (RCCL when launched under torchrun; gloo in the CPU tests).
 """
 from __future__ import annotations
@@ -68,6 +69,7 @@ class RolloutStorage:
         self.advantage = torch.zeros(T, N, self.n_agents, **f32)
         self.td_target = torch.zeros(T, N, self.n_agents, **f32)
         self._lib = _lib.load()
+        self._ppo_workspace = {}   # (agent, B, max_workgroups) -> workspace of actor_grad
 
     def set_initial_obs(self, obs):
         obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
@@ -133,6 +135,38 @@ class RolloutStorage:
         for k, c in enumerate(critics):
             critic_next_values(c, self.final_obs, self.done, self.truncated, self.value[..., k], next_value[..., k])
         return next_value
+
+    def actor_grad(self, k: int, actor, advantage: torch.Tensor, index: Optional[torch.Tensor] = None, **coeffs):
+        """PPO's actor loss and its gradients for agent k on the minibatch `index` (int64 rows of the flat [T * N] transitions; None:
+        all of them) in one launch that reads this storage in place (`policy.ppo_actor_grad`): obs[k], the agent's columns of
+        the shared action / logprob rows, final_obs / done / truncated for the reference's obs_next.  advantage: [T, N, n_agents]
+        (agent k's column is taken) or [T, N].  coeffs: clip, entropy_coef, lam_T, lam_S, lam_M, noise, nominal, max_action, grads,
+        stats, max_workgroups.  The workspace is kept per (agent, B, max_workgroups).  Returns (grads, stats)."""
+        from .policy import ppo_actor_grad, ppo_workspace_bytes
+        k = int(k)
+        if not 0 <= k < self.n_agents:
+            raise ValueError(f"agent {k} of {self.n_agents}")
+        adv = advantage[..., k] if advantage.dim() == 3 else advantage
+        B = self.T * self.N if index is None else index.numel()
+        mw = int(coeffs.get("max_workgroups", 0))
+        key = (k, B, mw)
+        if B and key not in self._ppo_workspace:
+            self._ppo_workspace[key] = torch.empty(ppo_workspace_bytes(actor.dims, B, mw) // 8, dtype=torch.float64, device=self.device)
+        fin = {} if self.final_obs is None else dict(final_obs=self.final_obs[k], done=self.done, truncated=self.truncated)
+        return ppo_actor_grad(actor, self.obs[k], self.act_all, self.logprob_all, adv, index, col_offset=sum(self.action_dims[:k]),
+                              workspace=self._ppo_workspace.get(key), **fin, **coeffs)
+
+    @staticmethod
+    def nominal_action(env, k: int, max_action: float = 1.0, device=None) -> torch.Tensor:
+        """The nominal action of the magnitude term (policy_regularization.py:30-46), float32 [A_k]: the hover thrust mapped into
+        [-max_action, max_action] followed by zero moments (MONO, and MODUL agent 0); zero for MODUL agent 1 (the yaw moment)."""
+        import numpy as np
+        if env.n_agents == 2 and int(k) == 1:
+            vals = [0.0]
+        else:
+            f = float(np.interp(4.0 * env.hover_force, [4.0 * env.min_force, 4.0 * env.max_force], [-max_action, max_action]))
+            vals = [f, 0.0, 0.0, 0.0]
+        return torch.tensor(vals, dtype=torch.float32, device=env.device if device is None else device)
 
     def collect(self, env, actors, **kw) -> dict:
         """One horizon with the actor(s) inside the step kernel (qr_rollout_actor): obs row 0 is the

@@ -310,6 +310,25 @@ def qr_critic_next_values(critic: List[torch.Tensor], inputs: List[int], final_o
     critic_next_values(_critic_params(critic, inputs), (final_obs0, final_obs1), done, truncated, value, next_value)
 
 
+@torch.library.custom_op(f"{_NS}::qr_ppo_actor_grad", mutates_args=("grads", "stats"))
+def qr_ppo_actor_grad(actor: List[torch.Tensor], obs: torch.Tensor, final_obs: Optional[torch.Tensor], done: Optional[torch.Tensor],
+                      truncated: Optional[torch.Tensor], action: torch.Tensor, logp_old: torch.Tensor, advantage: torch.Tensor,
+                      index: Optional[torch.Tensor], noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor],
+                      grads: List[torch.Tensor], stats: torch.Tensor, col_offset: int, clip: float, entropy_coef: float, lam_T: float,
+                      lam_S: float, lam_M: float, max_action: float, max_workgroups: int = 0) -> None:
+    """PPO's actor loss and its gradients for one agent and one minibatch (qr_ppo_actor_grad).  actor = fc1_w, fc1_b, fc2_w, fc2_b,
+    mean_w, mean_b, log_std; grads = seven float32 tensors of those sizes, overwritten; stats float32 [4].  Everything else as
+    policy.ppo_actor_grad."""
+    from .policy import ActorParams, ppo_actor_grad
+    _gpu(obs)
+    if len(actor) != 7 or len(grads) != 7:
+        raise ValueError("the actor and its gradients are 7 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std")
+    ppo_actor_grad(ActorParams(*actor[:6], actor[6].reshape(-1)), obs, action, logp_old, advantage, index, final_obs=final_obs, done=done,
+                   truncated=truncated, clip=clip, entropy_coef=entropy_coef, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, noise=noise,
+                   nominal=nominal, max_action=max_action, col_offset=col_offset, grads=dict(zip(_lib.PPO_GRAD_NAMES, grads)), stats=stats,
+                   max_workgroups=max_workgroups)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

@@ -425,6 +425,52 @@ int qr_critic_next_values(const QrCritic* critic, const float* final_obs0, const
                           int32_t n_steps, int64_t n_envs, const float* value, float* next_value,
                           int32_t value_stride, void* stream);
 
+/* The actor half of one PPO minibatch update (PPO.train, algos/ppo/ppo.py:169-182, with algos/policy_regularization.py) for ONE
+ * agent, read from the rollout storage in place: loss and gradients with respect to the actor's seven tensors, without autograd.
+ * A row i of the minibatch is an index into the flat [T * N] transitions (i = t N + n):
+ *     mu    = actor(obs[i]) (QR_ACTOR_TANH_MEAN form, log_std parameter s)      lp_j = Normal(mu_j, exp(s_j)).log_prob(action[i][j])
+ *     rho   = exp(sum_j lp_j - sum_j logp_old[i][j])          S = min(rho adv_i, clamp(rho, 1 - clip, 1 + clip) adv_i)
+ *     loss  = -(1/B) sum_i (S_i + entropy_coef sum_j (0.5 + 0.5 log 2 pi + s_j))
+ *             + lam_T mean (c(mu(obs[i])) - c(mu(obs_next[i])))^2 + lam_S mean (c(mu(obs[i])) - c(mu(obs[i] + noise)))^2
+ *             + lam_M mean (c(mu(obs[i])) - nominal)^2,         c = clamp to +-max_action, means over the B x action_dim elements
+ * obs_next[i] = final_obs[i] where any of done[i][0..n_agents) or truncated[i] is set, obs[i + N] elsewhere (qr_critic_next_values'
+ * rule; final_obs NULL: always obs[i + N], done / truncated unread).  The gradients are torch autograd's: min and clamp route
+ * them as torch.min / torch.clamp do.  A coefficient lam_* equal to 0 skips that term's passes.
+ *   obs [T+1][N][obs_dim], final_obs [T][N][obs_dim]; action / logp_old: row i at base + i * row_stride + col_offset (the
+ *   Decoupled storage's [T][N][5] rows serve both agents); advantage: element i at advantage[i * adv_stride]; index: int64
+ *   [batch] or NULL (rows 0 .. batch - 1; repeats are legal, a value outside [0, T N) is clamped into it); noise [obs_dim]
+ *   (required when lam_S != 0), nominal [action_dim] (required when lam_M != 0).
+ * Two launches: one wavefront per workgroup accumulates its share of the 64-row tiles and writes ONE partial vector into
+ * `workspace`; a second kernel sums the partial vectors in float64 in a fixed order.  The same inputs and grid give the same
+ * bits (no atomics).  The grid is min(ceil(batch / 64), max_workgroups), max_workgroups = 0: the library's rule (1024). */
+typedef struct QrPpoBatch {
+  const float* obs;        const float* final_obs;
+  const uint8_t* done;     const uint8_t* truncated;
+  const float* action;     const float* logp_old;
+  const float* advantage;
+  const int64_t* index;
+  const float* noise;      const float* nominal;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_ppo_actor_workspace_bytes(...); 8-byte aligned */
+  int64_t batch, n_envs;                              /* B >= 1; N */
+  int32_t n_steps, n_agents;                          /* T; columns of done */
+  int32_t row_stride, col_offset;                     /* of the action and logp_old rows */
+  int32_t adv_stride, max_workgroups;
+  float clip, entropy_coef, lam_T, lam_S, lam_M, max_action;
+} QrPpoBatch;
+/* Outputs, overwritten: the gradient tensors in the shapes of the QrActor's (log_std [action_dim]) and stats [4] = loss, mean S_i,
+ * share of rows with rho outside [1 - clip, 1 + clip], mean of (rho - 1) - log rho. */
+typedef struct QrPpoGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *mean_w, *mean_b, *log_std, *stats;
+} QrPpoGrad;
+/* QR_E_NULL for a NULL struct, weight, input, output or workspace pointer (final_obs, truncated, index optional; done required
+ * with final_obs; noise / nominal as above); QR_E_KIND for squash != QR_ACTOR_TANH_MEAN or an actor with a log_std head;
+ * QR_E_SIZE for sizes other than qr_rollout_actor's (23,16,4), (15,16,4), (3,4,1), batch < 1, n_steps < 1, n_envs < 1, strides
+ * < 1, a column offset outside the row, max_workgroups < 0 or a workspace that is too small; QR_E_ALIGN for a float pointer that is
+ * not 4-byte aligned or an index / workspace pointer that is not 8-byte aligned.  Nothing is launched on an error. */
+int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream);
+/* Bytes of workspace qr_ppo_actor_grad needs for this actor size, batch and max_workgroups; QR_E_SIZE (< 0) where it would refuse them. */
+int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -32,7 +32,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_traj_start", "qr_get_desired", "qr_gae",
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
-           "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes")
+           "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
+           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -108,6 +109,19 @@ PPO_GRAD_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mean_w", "mean_b", "log_s
 
 class QrPpoGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_GRAD_NAMES + ("stats",)]
+
+
+class QrCriticBatch(C.Structure):
+    _fields_ = [("obs0", C.c_void_p), ("obs1", C.c_void_p), ("target", C.c_void_p), ("index", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("batch", C.c_int64), ("rows", C.c_int64), ("target_stride", C.c_int32),
+                ("max_workgroups", C.c_int32), ("l2_reg", C.c_float), ("reserved0", C.c_int32)]
+
+
+PPO_CRITIC_GRAD_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")   # qr_ppo_critic_grad: the gradient tensors, in order
+
+
+class QrCriticGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in PPO_CRITIC_GRAD_NAMES + ("stats",)]
 
 
 def ptr(t):
@@ -210,6 +224,10 @@ def load():
     lib.qr_ppo_actor_grad.argtypes = [P(QrActor), P(QrPpoBatch), P(QrPpoGrad), C.c_void_p]
     lib.qr_ppo_actor_workspace_bytes.restype = C.c_int64
     lib.qr_ppo_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_ppo_critic_grad.restype = C.c_int
+    lib.qr_ppo_critic_grad.argtypes = [P(QrCritic), P(QrCriticBatch), P(QrCriticGrad), C.c_void_p]
+    lib.qr_ppo_critic_workspace_bytes.restype = C.c_int64
+    lib.qr_ppo_critic_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -44,6 +44,7 @@
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
 //   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
+//   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -63,6 +64,7 @@
 #include "qr_aux.h"
 #include "qr_critic.h"
 #include "qr_ppo.h"
+#include "qr_ppo_critic.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -149,9 +151,68 @@ static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* 
   hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)((r.off[7] + 3) / 4 + 1)), dim3(256), 0, s, r);
   return (int)hipGetLastError();
 }
+
+// The grid of qr_ppo_critic_grad: a function of the batch and max_workgroups only (0: the waves resident at once, one per SIMD at
+// the kernel's register count: 256 CUs x 4; its 29 KB of LDS admit five workgroups per CU).
+static int64_t ppo_critic_grid(int64_t batch, int32_t max_workgroups) {
+  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : 1024;
+  return tiles < cap ? tiles : cap;
+}
+
+static bool ppo_critic_sizes_ok(int64_t in0, int64_t in1, int64_t hidden) {
+  return in0 >= 0 && in1 >= 0 && in0 <= kCriticIn && in1 <= kCriticIn && in0 + in1 >= 1 && in0 + in1 <= kCriticIn && hidden >= 1 && hidden <= 64;
+}
+
+static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCriticGrad* g, void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  if (!ppo_critic_sizes_ok(c->in0, c->in1, c->hidden_dim)) return QR_E_SIZE;
+  if (b->batch < 1 || b->rows < 1 || b->target_stride < 1 || b->max_workgroups < 0) return QR_E_SIZE;
+  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b) return QR_E_NULL;
+  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->fc3_w || !g->fc3_b || !g->stats) return QR_E_NULL;
+  if ((c->in0 && !b->obs0) || (c->in1 && !b->obs1) || !b->target || !b->workspace) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w,
+                                g->fc3_b, g->stats, b->obs0, b->obs1, b->target};
+  for (const void* p : floats)
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(b->workspace)) & 7u) return QR_E_ALIGN;
+  const int D = c->in0 + c->in1, H = c->hidden_dim;
+  const PpoCriticLayout Y(D, H);
+  const int64_t grid = ppo_critic_grid(b->batch, b->max_workgroups);
+  if (b->workspace_bytes < grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  PpoCriticArgs a{};
+  a.fc1_w = c->fc1_w; a.fc1_b = c->fc1_b; a.fc2_w = c->fc2_w; a.fc2_b = c->fc2_b; a.fc3_w = c->fc3_w; a.fc3_b = c->fc3_b;
+  a.rows0 = c->in0 ? b->obs0 : nullptr; a.rows1 = c->in1 ? b->obs1 : nullptr;
+  a.target = b->target; a.index = b->index; a.partials = static_cast<double*>(b->workspace);
+  a.B = b->batch; a.rows = b->rows; a.in0 = c->in0; a.in1 = c->in1; a.hidden = H; a.tgt_stride = b->target_stride;
+  a.g_scale = (float)(2.0 / (double)b->batch);
+  PpoCriticReduceArgs r{};
+  r.partials = a.partials;
+  r.weight[0] = c->fc1_w; r.weight[1] = c->fc2_w; r.weight[2] = c->fc3_w;
+  float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b};
+  const int starts[7] = {Y.w1, Y.b1, Y.w2, Y.b2, Y.w3, Y.b3, Y.st};
+  for (int k = 0; k < 6; ++k) r.grad[k] = grads[k];
+  for (int k = 0; k < 7; ++k) r.off[k] = starts[k];
+  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch; r.l2_reg = b->l2_reg;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(ppo_critic_kernel, dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(ppo_critic_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const QrCriticGrad* grad, void* stream) {
+  return qr::do_ppo_critic(critic, batch, grad, stream);
+}
+
+int64_t qr_ppo_critic_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {
+  if (!qr::ppo_critic_sizes_ok(in_dim, 0, hidden_dim) || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_critic_grid(batch, max_workgroups) * qr::PpoCriticLayout(in_dim, hidden_dim).np * (int64_t)sizeof(double);
+}
 
 int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream) {
   return qr::do_ppo_actor(actor, batch, grad, stream);

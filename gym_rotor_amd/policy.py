@@ -1,6 +1,6 @@
 """Actor parameters for the policy-in-the-loop rollout (`QuadVecEnv.rollout_actor`), critic parameters for the on-device values
 of a horizon (`RolloutStorage.compute_values`), the PPO actor loss and its gradients for one minibatch (`ppo_actor_grad`,
-`actor_loss`).
+`actor_loss`), the PPO critic loss and its gradients for one minibatch (`ppo_critic_grad`, `critic_loss`).
 
 The networks are the reference's MLP actors: `MLP_Actor_PPO` (algos/ppo/ppo_mlp.py:6-58: fc1 -> relu
 -> fc2 -> relu -> mean_linear -> tanh, plus a state-independent `log_std`), `MLP_Actor_TD3`
@@ -397,6 +397,108 @@ def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional
             p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
         grads[n] = p.grad
     _, stats = storage.actor_grad(k, ActorParams.from_module(module), advantage, index, grads=grads, **coeffs)
+    return stats
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the critic half of a PPO minibatch update (qr_ppo_critic_grad)
+# ----------------------------------------------------------------------------------------------------------------
+def ppo_critic_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `ppo_critic_grad` launch needs (qr_ppo_critic_workspace_bytes); dims = (input width, hidden width)."""
+    n = _lib.load().qr_ppo_critic_workspace_bytes(int(dims[0]), int(dims[1]), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_ppo_critic_workspace_bytes")
+    return int(n)
+
+
+def ppo_critic_grad(critic: CriticParams, obs, target: torch.Tensor, index: Optional[torch.Tensor] = None, *, l2_reg: float = 0.0,
+                    grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                    max_workgroups: int = 0):
+    """PPO's critic loss (ppo.py:193-214: the mean squared error of V against the TD target plus l2_reg times the squared norms of the
+    three weight tensors) and its gradients for ONE critic and one minibatch, in one launch plus a small reduction
+    (qr_ppo_critic_grad) — no autograd, no copies of the minibatch's rows.
+    obs: the per-agent observation row tensors [.., D_k] as `critic_values` takes them (contiguous float32; an agent the critic does
+    not read may be None), at least target.numel() rows each, of which the leading ones are used — `storage.obs` passes as it is;
+    target: float32 with ONE element stride, e.g. `storage.td_target[..., k]`; index: int64 [B] rows of the flat target, None = all
+    of them in order.
+    Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b — `grads` given: overwritten
+    in place — and stats float32 [4] = loss, mse, mean error, population variance of the minibatch's targets (explained variance =
+    1 - (stats[1] - stats[2] ** 2) / stats[3])."""
+    dev = target.device
+    if target.dtype != torch.float32:
+        raise ValueError(f"ppo_critic_grad: target must be float32, got {target.dtype}")
+    rows, stride = target.numel(), _element_stride(target, "target")
+    if critic.device != dev:
+        raise ValueError(f"ppo_critic_grad: the critic's tensors are on {critic.device}, the target on {dev}")
+    obs = list(obs) + [None] * (2 - len(obs))
+    widths = []
+    for k, r in enumerate(obs[:2]):
+        if r is None:
+            widths.append(0)
+            continue
+        if r.dtype != torch.float32 or r.device != dev or not r.is_contiguous() or r.dim() < 2 or r[..., 0].numel() < rows:
+            raise ValueError(f"ppo_critic_grad: observation rows {k} must be contiguous float32 [>= {rows} rows, D] on {dev}")
+        widths.append(r.shape[-1])
+    while widths and widths[-1] == 0:
+        widths.pop()
+    q = critic.as_c(widths)
+    if index is not None:
+        if index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous():
+            raise ValueError(f"ppo_critic_grad: index must be a contiguous int64 [B] tensor on {dev}")
+        B = index.numel()
+    else:
+        B = rows
+    if B and rows < 1:
+        raise ValueError("ppo_critic_grad: an index needs a target with at least one element")
+    shapes = {n: tuple(getattr(critic, n).shape) for n in _lib.PPO_CRITIC_GRAD_NAMES}
+    if grads is None:
+        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
+    for n, s in shapes.items():
+        g = grads.get(n)
+        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
+            raise ValueError(f"ppo_critic_grad: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError(f"ppo_critic_grad: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
+        for n in shapes:
+            grads[n].zero_()
+        stats.zero_()
+        return grads, stats
+    need = ppo_critic_workspace_bytes(critic.dims, B, max_workgroups)
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"ppo_critic_grad: workspace must be a contiguous tensor on {dev}")
+    b = _lib.QrCriticBatch()
+    b.obs0, b.obs1 = (_lib.ptr(obs[0]) if q.in0 else None), (_lib.ptr(obs[1]) if q.in1 else None)
+    b.target, b.index = target.data_ptr(), _lib.ptr(index)
+    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    b.batch, b.rows, b.target_stride, b.max_workgroups, b.l2_reg = B, rows, stride, int(max_workgroups), float(l2_reg)
+    g = _lib.QrCriticGrad(*[grads[n].data_ptr() for n in _lib.PPO_CRITIC_GRAD_NAMES], stats.data_ptr())
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_ppo_critic_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ppo_critic_grad")
+    return grads, stats
+
+
+def critic_loss(module, storage, k: int, index: Optional[torch.Tensor] = None, inputs=(0,), **coeffs) -> torch.Tensor:
+    """The critic update of a training loop, as the reference writes it, without autograd — the twin of `actor_loss`: runs
+    `storage.critic_grad` for agent k on the live `module` (attributes fc1, fc2, fc3 — its tensors are read in place; inputs: the
+    agents whose observation rows it reads, `CriticParams.inputs`) and writes the gradients into `module.fc{1,2,3}.{weight,bias}.grad`
+    in place, as `loss.backward()` after `zero_grad()` leaves them.  coeffs: l2_reg, target, stats, max_workgroups.  Returns stats
+    (stats[0] = the loss).  The optimiser step, gradient clipping and the schedule stay torch, on these .grad tensors."""
+    params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.fc3.weight, module.fc3.bias)
+    if "grads" in coeffs:
+        raise ValueError("critic_loss writes into the module's .grad tensors: it takes no grads")
+    grads = {}
+    for n, p in zip(_lib.PPO_CRITIC_GRAD_NAMES, params):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    _, stats = storage.critic_grad(k, CriticParams.from_module(module, inputs), index, grads=grads, **coeffs)
     return stats
 
 

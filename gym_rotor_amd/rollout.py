@@ -7,7 +7,8 @@ Transitions of N envs stay on the GPU as `[T, N, ...]` tensors; `QuadVecEnv.step
 writes observation / reward / done rows straight into them; GAE is one HIP launch
 (`qr_gae`: reverse scan over T per (env, agent) column), and so are the critic's values between the two
 (`qr_critic_values`, `qr_critic_next_values`: `compute_values`), and so is the actor's loss with its gradients per minibatch
-(`qr_ppo_actor_grad`: `actor_grad`).  Normalisation statistics can be
+(`qr_ppo_actor_grad`: `actor_grad`), and so is the critic's loss with its gradients per minibatch (`qr_ppo_critic_grad`:
+`critic_grad`) — a whole PPO update needs torch only for the optimiser step.  Normalisation statistics can be
 all-reduced over the env shards (RCCL when launched under torchrun; gloo in the CPU tests).
 """
 from __future__ import annotations
@@ -70,6 +71,7 @@ class RolloutStorage:
         self.td_target = torch.zeros(T, N, self.n_agents, **f32)
         self._lib = _lib.load()
         self._ppo_workspace = {}   # (agent, B, max_workgroups) -> workspace of actor_grad
+        self._critic_workspace = {}   # (agent, B, max_workgroups) -> workspace of critic_grad
 
     def set_initial_obs(self, obs):
         obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
@@ -155,6 +157,30 @@ class RolloutStorage:
         fin = {} if self.final_obs is None else dict(final_obs=self.final_obs[k], done=self.done, truncated=self.truncated)
         return ppo_actor_grad(actor, self.obs[k], self.act_all, self.logprob_all, adv, index, col_offset=sum(self.action_dims[:k]),
                               workspace=self._ppo_workspace.get(key), **fin, **coeffs)
+
+    def critic_grad(self, k: int, critic, index: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, **coeffs):
+        """PPO's critic loss and its gradients for agent k's critic on the minibatch `index` (int64 rows of the flat [T * N]
+        transitions; None: all of them) in one launch that reads this storage in place (`policy.ppo_critic_grad`): the observation
+        rows `critic.inputs` names (rows past T * N, the bootstrap row among them, are never read) and `target`, by default
+        td_target[..., k] as compute_gae left it; a given target is [T, N, n_agents] (agent k's column is taken) or [T, N].
+        coeffs: l2_reg, grads, stats, max_workgroups.  The workspace is kept per (agent, B, max_workgroups).
+        Returns (grads, stats)."""
+        from .policy import ppo_critic_grad, ppo_critic_workspace_bytes
+        k = int(k)
+        if not 0 <= k < self.n_agents:
+            raise ValueError(f"agent {k} of {self.n_agents}")
+        if target is None:
+            target = self.td_target
+        if tuple(target.shape[:2]) != (self.T, self.N) or target.dim() not in (2, 3):
+            raise ValueError(f"critic_grad: target must be [{self.T}, {self.N}, n_agents] or [{self.T}, {self.N}], got {tuple(target.shape)}")
+        tgt = target[..., k] if target.dim() == 3 else target
+        B = self.T * self.N if index is None else index.numel()
+        mw = int(coeffs.get("max_workgroups", 0))
+        key = (k, B, mw)
+        need = ppo_critic_workspace_bytes(critic.dims, B, mw) // 8 if B else 0
+        if B and (key not in self._critic_workspace or self._critic_workspace[key].numel() < need):   # (a second, wider critic of one agent)
+            self._critic_workspace[key] = torch.empty(need, dtype=torch.float64, device=self.device)
+        return ppo_critic_grad(critic, self.obs, tgt, index, workspace=self._critic_workspace.get(key), **coeffs)
 
     @staticmethod
     def nominal_action(env, k: int, max_action: float = 1.0, device=None) -> torch.Tensor:

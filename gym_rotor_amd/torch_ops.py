@@ -329,6 +329,21 @@ def qr_ppo_actor_grad(actor: List[torch.Tensor], obs: torch.Tensor, final_obs: O
                    max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_ppo_critic_grad", mutates_args=("grads", "stats"))
+def qr_ppo_critic_grad(critic: List[torch.Tensor], inputs: List[int], obs0: Optional[torch.Tensor], obs1: Optional[torch.Tensor],
+                       target: torch.Tensor, index: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor,
+                       l2_reg: float, max_workgroups: int = 0) -> None:
+    """PPO's critic loss and its gradients for one critic and one minibatch (qr_ppo_critic_grad).  Critic and inputs as in
+    qr_critic_values; grads = six float32 tensors of the critic's sizes, overwritten; stats float32 [4].  Everything else as
+    policy.ppo_critic_grad."""
+    from .policy import ppo_critic_grad
+    _gpu(target)
+    if len(grads) != 6:
+        raise ValueError("a critic's gradients are 6 tensors: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b")
+    ppo_critic_grad(_critic_params(critic, inputs), (obs0, obs1), target, index, l2_reg=l2_reg, grads=dict(zip(_lib.PPO_CRITIC_GRAD_NAMES, grads)),
+                    stats=stats, max_workgroups=max_workgroups)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

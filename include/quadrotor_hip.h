@@ -471,6 +471,44 @@ int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpo
 /* Bytes of workspace qr_ppo_actor_grad needs for this actor size, batch and max_workgroups; QR_E_SIZE (< 0) where it would refuse them. */
 int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups);
 
+/* The critic half of one PPO minibatch update (PPO.train, algos/ppo/ppo.py:193-214) for ONE critic (a QrCritic as above: MLP_Critic
+ * or MLP_Critic_CTDE, 1 <= in0 + in1 <= 24, 1 <= hidden_dim <= 64), read from the rollout storage in place: loss and gradients with
+ * respect to the critic's six tensors, without autograd.  A row i of the minibatch is an index into the observation rows:
+ *     v_i   = V(x_i)             x_i = obs0 row index[i] (CTDE: followed by obs1 row index[i])
+ *     e_i   = v_i - y_i          y_i = target[index[i] * target_stride]
+ *     mse   = (1/B) sum_i e_i^2
+ *     loss  = mse + l2_reg (||fc1_w||^2 + ||fc2_w||^2 + ||fc3_w||^2)          (ppo.py:197-204: the weights, not the biases)
+ * The gradients are loss.backward()'s: the data term backwards from dLoss/dv_i = 2 e_i / B, plus 2 l2_reg W on the three weights.
+ *   obs0 / obs1: float32 rows [>= rows][in0 / in1] (NULL where in0 / in1 is 0); target: element i at target[i * target_stride], i <
+ *   rows (the storage's td_target column of this agent); index: int64 [batch] or NULL (rows 0 .. batch - 1; repeats are legal, a
+ *   value outside [0, rows) is clamped into it).
+ * Two launches: one wavefront per workgroup accumulates its share of the 64-row tiles and writes ONE partial vector into
+ * `workspace`; a second kernel sums the partial vectors in float64 in a fixed order and adds the L2 terms.  The same inputs and grid
+ * give the same bits (no atomics).  The grid is min(ceil(batch / 64), max_workgroups), max_workgroups = 0: the library's rule (1024). */
+typedef struct QrCriticBatch {
+  const float* obs0;       const float* obs1;
+  const float* target;
+  const int64_t* index;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_ppo_critic_workspace_bytes(...); 8-byte aligned */
+  int64_t batch, rows;                                /* B >= 1; rows of obs0 / obs1 and elements of target an index may name */
+  int32_t target_stride, max_workgroups;
+  float l2_reg;            int32_t reserved0;
+} QrCriticBatch;
+/* Outputs, overwritten: the gradient tensors in the shapes of the QrCritic's and stats [4] = loss, mse, mean of e_i, population
+ * variance of y_i over the minibatch (explained variance = 1 - (stats[1] - stats[2]^2) / stats[3]: the division is the caller's, so
+ * that a constant target puts no NaN into the output). */
+typedef struct QrCriticGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *fc3_w, *fc3_b, *stats;
+} QrCriticGrad;
+/* QR_E_NULL for a NULL struct, weight, target, output or workspace pointer, or a NULL row pointer whose in0 / in1 is not 0 (index
+ * optional); QR_E_SIZE for widths outside the ranges above, batch < 1, rows < 1, target_stride < 1, max_workgroups < 0 or a workspace
+ * that is too small; QR_E_ALIGN for a float pointer that is not 4-byte aligned or an index / workspace pointer that is not 8-byte
+ * aligned.  Nothing is launched on an error. */
+int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const QrCriticGrad* grad, void* stream);
+/* Bytes of workspace qr_ppo_critic_grad needs for this critic size (in_dim = in0 + in1), batch and max_workgroups; QR_E_SIZE (< 0)
+ * where it would refuse them. */
+int64_t qr_ppo_critic_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -40,6 +40,8 @@ def kernels(lib: str) -> dict:
 
     def flush():
         if name is not None:
+            while body and body[-1] in ("s_nop 0", "s_code_end"):   # the padding behind a kernel (256 s_nop behind the LAST one of the
+                body.pop()                                          # code object) is not its code
             text = "\n".join(body)
             out[name] = (hashlib.sha1(text.encode()).hexdigest(), len(body))
 

@@ -33,7 +33,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
-           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes")
+           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step")
 
 
 class QrCoeffs(C.Structure):
@@ -124,8 +124,32 @@ class QrCriticGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_CRITIC_GRAD_NAMES + ("stats",)]
 
 
+ADAMW_MAX_GROUPS, ADAMW_MAX_TENSORS, ADAMW_MAX_ENTRIES = 8, 8, 65536   # qr_adamw_step: groups per launch, tensors and entries per group
+
+
+class QrAdamWGroup(C.Structure):
+    _fields_ = [("param", C.c_void_p * 8), ("grad", C.c_void_p * 8), ("count", C.c_int32 * 8), ("n_tensors", C.c_int32),
+                ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("stats", C.c_void_p),
+                ("lr", C.c_double), ("eta_min", C.c_double), ("t0", C.c_int64),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("max_norm", C.c_float)]
+
+
 def ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def adamw_group(g: QrAdamWGroup, params, grads, exp_avg, exp_avg_sq, step, stats, *, lr, eta_min, t0, betas, eps, weight_decay, max_norm):
+    """Fill the QrAdamWGroup `g` of one optimiser step: the parameter tensors and their gradients (1..8 of each, in the order of the
+    flat moment buffers), the state tensors, the hyperparameters.  Returns g."""
+    g.n_tensors = len(params)
+    for k, (p, d) in enumerate(zip(params, grads)):
+        g.param[k], g.grad[k], g.count[k] = p.data_ptr(), d.data_ptr(), p.numel()
+    for k in range(len(params), 8):
+        g.param[k], g.grad[k], g.count[k] = None, None, 0
+    g.exp_avg, g.exp_avg_sq, g.step, g.stats = exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(), ptr(stats)
+    g.lr, g.eta_min, g.t0 = float(lr), float(eta_min), int(t0)
+    g.beta1, g.beta2, g.eps, g.weight_decay, g.max_norm = float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_norm)
+    return g
 
 
 def step_out(out, truncated: bool) -> QrStepOut:
@@ -228,6 +252,8 @@ def load():
     lib.qr_ppo_critic_grad.argtypes = [P(QrCritic), P(QrCriticBatch), P(QrCriticGrad), C.c_void_p]
     lib.qr_ppo_critic_workspace_bytes.restype = C.c_int64
     lib.qr_ppo_critic_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_adamw_step.restype = C.c_int
+    lib.qr_adamw_step.argtypes = [P(QrAdamWGroup), C.c_int32, C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

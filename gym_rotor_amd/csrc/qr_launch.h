@@ -467,4 +467,43 @@ static int do_evaluate(const QrEnv* env, const QrPolicyRollout* pol, const QrPop
   return rc;
 }
 
+// qr_adamw_step: every argument check, then ONE launch of n_groups workgroups.  Nothing is launched on an error.
+static int do_adamw(const QrAdamWGroup* groups, int32_t n_groups, void* stream) {
+  if (!groups) return QR_E_NULL;
+  if (n_groups < 1 || n_groups > kAdamWGroups) return QR_E_SIZE;
+  AdamWArgs a{};
+  for (int i = 0; i < n_groups; ++i) {
+    const QrAdamWGroup& g = groups[i];
+    AdamWGroupArgs& d = a.g[i];
+    if (g.n_tensors < 1 || g.n_tensors > kAdamWTensors) return QR_E_SIZE;
+    int64_t total = 0;
+    for (int k = 0; k < g.n_tensors; ++k) {
+      if (g.count[k] < 1) return QR_E_SIZE;
+      total += g.count[k];
+    }
+    if (total > kAdamWMaxEntries) return QR_E_SIZE;
+    const double nonneg[] = {g.lr, g.eta_min, (double)g.eps, (double)g.weight_decay};
+    for (double v : nonneg)
+      if (!(v >= 0.0) || !(v <= 1.79769313486231570e308)) return QR_E_SIZE;
+    if (!(g.beta1 >= 0.0f && g.beta1 < 1.0f) || !(g.beta2 >= 0.0f && g.beta2 < 1.0f) || g.t0 < 0 || g.max_norm != g.max_norm) return QR_E_SIZE;
+    if (!g.exp_avg || !g.exp_avg_sq || !g.step) return QR_E_NULL;
+    for (int k = 0; k < g.n_tensors; ++k)
+      if (!g.param[k] || !g.grad[k]) return QR_E_NULL;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(g.exp_avg) | reinterpret_cast<uintptr_t>(g.exp_avg_sq) | reinterpret_cast<uintptr_t>(g.stats);
+    for (int k = 0; k < g.n_tensors; ++k) bits |= reinterpret_cast<uintptr_t>(g.param[k]) | reinterpret_cast<uintptr_t>(g.grad[k]);
+    if ((bits & 3u) || (reinterpret_cast<uintptr_t>(g.step) & 7u)) return QR_E_ALIGN;
+    for (int k = 0; k < kAdamWTensors; ++k) {
+      const bool used = k < g.n_tensors;
+      d.param[k] = used ? g.param[k] : nullptr;
+      d.grad[k] = used ? g.grad[k] : nullptr;
+      d.off[k + 1] = d.off[k] + (used ? g.count[k] : 0);
+    }
+    d.exp_avg = g.exp_avg; d.exp_avg_sq = g.exp_avg_sq; d.step = g.step; d.stats = g.stats;
+    d.lr = g.lr; d.eta_min = g.eta_min; d.t0 = g.t0;
+    d.beta1 = g.beta1; d.beta2 = g.beta2; d.eps = g.eps; d.weight_decay = g.weight_decay; d.max_norm = g.max_norm;
+  }
+  hipLaunchKernelGGL(adamw_step_kernel, dim3((unsigned)n_groups), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace qr

@@ -45,6 +45,7 @@
 //   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
+//   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -65,6 +66,7 @@
 #include "qr_critic.h"
 #include "qr_ppo.h"
 #include "qr_ppo_critic.h"
+#include "qr_optim.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -204,6 +206,8 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
 }  // namespace qr
 
 extern "C" {
+
+int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream) { return qr::do_adamw(groups, n_groups, stream); }
 
 int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const QrCriticGrad* grad, void* stream) {
   return qr::do_ppo_critic(critic, batch, grad, stream);

@@ -1,0 +1,241 @@
+"""The optimiser half of a PPO update on the device: `DeviceAdamW` — gradient-norm clipping, AdamW and the cosine schedule with warm
+restarts in one launch (`qr_adamw_step`), with the step count and the schedule in device memory — and `PpoUpdater`, the K-epoch,
+shuffle and minibatch loop of the reference's `PPO.train` (algos/ppo/ppo.py:148-214) over `actor_loss`, `critic_loss` and those steps.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+from .policy import actor_loss, critic_loss
+
+
+def _f32(v) -> float:
+    """The float32 the C-ABI holds for `v`."""
+    return C.c_float(float(v)).value
+
+
+class DeviceAdamW:
+    """`clip_grad_norm_(params, max_norm)`, `torch.optim.AdamW(params, lr, betas, eps, weight_decay).step()` and
+    `CosineAnnealingWarmRestarts(T_0=t0, eta_min).step()` — in that order, the reference's (ppo.py:185-190) — as ONE launch per
+    `step()`.  max_norm < 0: no clipping; t0 = 0: a constant rate.  The reference's values: max_norm=100, t0=1_000_000, eta_min=1e-5,
+    lr 3e-4 (actors) / 2e-4 (critics).
+
+    params: 1..8 contiguous float32 tensors on one device, 65 536 entries at the most together; they are updated in place (a live
+    module's parameters: the next launch of the library reads the new weights).  `step()` reads each parameter's `.grad` (contiguous
+    float32, as `actor_loss` / `critic_loss` leave them), synchronises nothing and allocates nothing.
+    Deviations from torch: `.grad` is READ ONLY — it keeps the unclipped gradient, where clip_grad_norm_ scales it in place; betas,
+    eps, weight_decay and max_norm are held as float32 (the attributes show the values in use: beta2 = 0.999 is 0.99900001287...).
+    State: `exp_avg`, `exp_avg_sq` (flat float32, the tensors back to back), `step_count` (int64 [1]) and `stats` (float32 [4] = the
+    last step's gradient norm, clip coefficient, learning rate and step number) on the parameters' device."""
+
+    def __init__(self, params, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_norm: float = -1.0,
+                 t0: int = 0, eta_min: float = 0.0):
+        self.params = list(params)
+        if not 1 <= len(self.params) <= _lib.ADAMW_MAX_TENSORS:
+            raise ValueError(f"DeviceAdamW takes 1..{_lib.ADAMW_MAX_TENSORS} parameter tensors, got {len(self.params)}")
+        self.device = self.params[0].device
+        for k, p in enumerate(self.params):
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
+                raise ValueError(f"DeviceAdamW: parameter {k} must be a contiguous float32 tensor with at least one entry")
+            if p.device != self.device:
+                raise ValueError(f"DeviceAdamW: parameter {k} is on {p.device}, parameter 0 on {self.device}")
+        self.numel = sum(p.numel() for p in self.params)
+        if self.numel > _lib.ADAMW_MAX_ENTRIES:
+            raise ValueError(f"DeviceAdamW: {self.numel} entries, at most {_lib.ADAMW_MAX_ENTRIES} per optimiser")
+        self._set_hyper(dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm, t0=t0, eta_min=eta_min))
+        self.exp_avg = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        self.exp_avg_sq = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.stats = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._group = _lib.QrAdamWGroup()
+
+    def _set_hyper(self, h):
+        lr, eta_min, t0 = float(h["lr"]), float(h["eta_min"]), int(h["t0"])
+        betas = (_f32(h["betas"][0]), _f32(h["betas"][1]))
+        eps, weight_decay, max_norm = _f32(h["eps"]), _f32(h["weight_decay"]), _f32(h["max_norm"])
+        for name, v in (("lr", lr), ("eta_min", eta_min), ("eps", eps), ("weight_decay", weight_decay)):
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError(f"DeviceAdamW: {name} must be finite and >= 0, got {v}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"DeviceAdamW: betas must lie in [0, 1), got {betas}")
+        if t0 < 0 or math.isnan(max_norm):
+            raise ValueError("DeviceAdamW: t0 must be >= 0 and max_norm a number (negative: no clipping)")
+        self.lr, self.eta_min, self.t0, self.betas, self.eps, self.weight_decay, self.max_norm = lr, eta_min, t0, betas, eps, weight_decay, max_norm
+
+    def hyper(self) -> dict:
+        return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm, t0=self.t0,
+                    eta_min=self.eta_min)
+
+    def _fill(self) -> _lib.QrAdamWGroup:
+        """The launch struct of the next step, from the parameters' current .grad tensors."""
+        grads = []
+        for k, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                raise ValueError(f"DeviceAdamW.step: parameter {k} has no .grad")
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device or g.numel() != p.numel():
+                raise ValueError(f"DeviceAdamW.step: the .grad of parameter {k} must be a contiguous float32 tensor of {p.numel()} entries on "
+                                 f"{self.device}")
+            grads.append(g)
+        return _lib.adamw_group(self._group, self.params, grads, self.exp_avg, self.exp_avg_sq, self.step_count, self.stats, **self.hyper())
+
+    def step(self) -> None:
+        """One optimiser step (clip, AdamW, schedule) in one launch on the current stream."""
+        DeviceAdamW.step_all([self])
+
+    @staticmethod
+    def step_all(opts: Sequence["DeviceAdamW"]) -> None:
+        """One step of each of several optimisers on one device in ONE launch (one workgroup each; more than 8: one launch per 8).
+        The result is that of stepping them one by one."""
+        opts = list(opts)
+        if not opts:
+            return
+        dev = opts[0].device
+        if any(o.device != dev for o in opts):
+            raise ValueError("DeviceAdamW.step_all: the optimisers must be on one device")
+        if len({id(o) for o in opts}) != len(opts):
+            raise ValueError("DeviceAdamW.step_all: an optimiser appears twice")
+        groups = [o._fill() for o in opts]
+        if dev.type != "cuda":
+            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for i in range(0, len(groups), _lib.ADAMW_MAX_GROUPS):
+                chunk = groups[i:i + _lib.ADAMW_MAX_GROUPS]
+                _lib.check(lib.qr_adamw_step((_lib.QrAdamWGroup * len(chunk))(*chunk), len(chunk), stream), "qr_adamw_step")
+
+    @property
+    def steps(self) -> int:
+        """Steps taken so far (a host read of the device counter: for logging)."""
+        return int(self.step_count.item())
+
+    def current_lr(self) -> float:
+        """The rate the NEXT step uses — `scheduler.get_last_lr()[0]` after `steps` steps (a host read: for logging)."""
+        if self.t0 == 0:
+            return self.lr
+        return self.eta_min + (self.lr - self.eta_min) * (1.0 + math.cos(math.pi * (self.steps % self.t0) / self.t0)) / 2.0
+
+    def state_dict(self) -> dict:
+        return {"step": self.step_count.clone(), "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone(), "hyper": self.hyper()}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copies into the existing state tensors (their addresses stay: a captured graph keeps working)."""
+        for name, dst in (("step", self.step_count), ("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            src = state[name]
+            if src.dtype != dst.dtype or src.numel() != dst.numel():
+                raise ValueError(f"DeviceAdamW.load_state_dict: {name} must be {dst.dtype} with {dst.numel()} entries")
+        self._set_hyper(state["hyper"])
+        for name, dst in (("step", self.step_count), ("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq)):
+            dst.copy_(state[name].reshape(dst.shape))
+
+
+def adamw_step(params, grads, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor, stats: Optional[torch.Tensor], *, lr: float,
+               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_norm: float = -1.0, t0: int = 0, eta_min: float = 0.0) -> None:
+    """One `qr_adamw_step` launch for ONE group on explicit tensors (what `DeviceAdamW.step` does with its own state and the
+    parameters' .grad): params / grads 1..8 contiguous float32 tensors each, exp_avg / exp_avg_sq float32 with as many entries as the
+    parameters together, step int64 [1], stats float32 [4] or None — all on one device."""
+    params, grads = list(params), list(grads)
+    if not 1 <= len(params) <= _lib.ADAMW_MAX_TENSORS or len(grads) != len(params):
+        raise ValueError(f"adamw_step takes 1..{_lib.ADAMW_MAX_TENSORS} parameter tensors and as many gradients")
+    dev = params[0].device
+    for k, (p, g) in enumerate(zip(params, grads)):
+        for what, t in (("parameter", p), ("gradient", g)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel() or t.numel() < 1:
+                raise ValueError(f"adamw_step: {what} {k} must be a contiguous float32 tensor of {p.numel()} >= 1 entries on {dev}")
+    total = sum(p.numel() for p in params)
+    for what, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != total:
+            raise ValueError(f"adamw_step: {what} must be a contiguous float32 tensor of {total} entries on {dev}")
+    if step.dtype != torch.int64 or step.numel() != 1 or step.device != dev:
+        raise ValueError(f"adamw_step: step must be an int64 tensor of one entry on {dev}")
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 4 or not stats.is_contiguous() or stats.device != dev):
+        raise ValueError(f"adamw_step: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    g = _lib.adamw_group(_lib.QrAdamWGroup(), params, grads, exp_avg, exp_avg_sq, step, stats, lr=lr, eta_min=eta_min, t0=t0, betas=betas,
+                         eps=eps, weight_decay=weight_decay, max_norm=max_norm)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_adamw_step(C.byref(g), 1, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_adamw_step")
+
+
+def minibatch_slices(n_rows: int, batch_size: int):
+    """The contiguous slices of a permutation of n_rows that are its minibatches: ceil(n_rows / batch_size) of them, the last one
+    shorter (ppo.py:152-153, 168, 194)."""
+    n_rows, batch_size = int(n_rows), int(batch_size)
+    if n_rows < 1 or batch_size < 1:
+        raise ValueError("minibatch_slices needs n_rows >= 1 and batch_size >= 1")
+    return [slice(i, min(i + batch_size, n_rows)) for i in range(0, n_rows, batch_size)]
+
+
+class PpoUpdater:
+    """`PPO.train`'s update loop (ppo.py:148-214) for all agents of an env kind, after `compute_gae` / `normalize`: per agent and
+    epoch one shuffle, then the actor's minibatches (`actor_loss`, then a `DeviceAdamW` step), then the critic's (`critic_loss`, then
+    a step).  When actor_batch_size == critic_batch_size the two halves walk the minibatches together — `actor_loss`, `critic_loss`,
+    then ONE `DeviceAdamW.step_all` launch for both networks; the result is the same bits, since neither network reads the other
+    during an update.  Otherwise they are stepped separately, in the reference's order.
+
+    actors / critics: one live module per agent (attributes fc1, fc2, mean_linear, log_std / fc1, fc2, fc3), read and updated in
+    place; actor_opts / critic_opts: their `DeviceAdamW`s; critic_inputs: per agent the observation rows its critic reads ((k,) by
+    default, (0, 1) for CTDE).  noise / nominal: per agent the [D_k] draw of the spatial term and the [A_k] nominal action
+    (`RolloutStorage.nominal_action`), required when lam_S / lam_M != 0; the noise tensor is read at every minibatch, so the caller
+    may refill it in place between updates.  The hyperparameters are the reference's names and defaults (args_parse.py:65-78)."""
+
+    def __init__(self, actors, critics, actor_opts, critic_opts, *, critic_inputs=None, K_epochs: int = 20, actor_batch_size: int = 128,
+                 critic_batch_size: int = 128, clip: float = 0.2, entropy_coef: float = 1e-2, entropy_coef_decay: float = 0.99,
+                 l2_reg: float = 1e-4, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, noise=None, nominal=None,
+                 max_action: float = 1.0):
+        self.actors, self.critics, self.actor_opts, self.critic_opts = list(actors), list(critics), list(actor_opts), list(critic_opts)
+        n = len(self.actors)
+        if n < 1 or not (len(self.critics) == len(self.actor_opts) == len(self.critic_opts) == n):
+            raise ValueError("PpoUpdater needs one actor, critic, actor optimiser and critic optimiser per agent")
+        self.critic_inputs = [tuple(i) for i in critic_inputs] if critic_inputs is not None else [(k,) for k in range(n)]
+        self.noise = list(noise) if noise is not None else [None] * n
+        self.nominal = list(nominal) if nominal is not None else [None] * n
+        if not (len(self.critic_inputs) == len(self.noise) == len(self.nominal) == n):
+            raise ValueError("PpoUpdater: critic_inputs, noise and nominal are per agent")
+        if int(K_epochs) < 1 or int(actor_batch_size) < 1 or int(critic_batch_size) < 1:
+            raise ValueError("PpoUpdater: K_epochs and the batch sizes must be >= 1")
+        self.K_epochs, self.actor_batch_size, self.critic_batch_size = int(K_epochs), int(actor_batch_size), int(critic_batch_size)
+        self.clip, self.entropy_coef, self.entropy_coef_decay, self.l2_reg = float(clip), float(entropy_coef), float(entropy_coef_decay), float(l2_reg)
+        self.lam_T, self.lam_S, self.lam_M, self.max_action = float(lam_T), float(lam_S), float(lam_M), float(max_action)
+        dev = self.actor_opts[0].device
+        self.actor_stats = [torch.zeros(4, dtype=torch.float32, device=dev) for _ in range(n)]
+        self.critic_stats = [torch.zeros(4, dtype=torch.float32, device=dev) for _ in range(n)]
+
+    def update(self, storage, advantage: torch.Tensor, generator: Optional[torch.Generator] = None):
+        """One PPO update from `storage` (after compute_gae: td_target is read from it) and the normalised `advantage`
+        [T, N, n_agents].  Returns (actor_stats, critic_stats): per agent the stats tensors of the last minibatch, on the device,
+        no synchronisation.  From the second call on nothing is allocated but the permutations."""
+        if storage.n_agents != len(self.actors):
+            raise ValueError(f"the storage has {storage.n_agents} agents, the updater {len(self.actors)}")
+        rows = storage.T * storage.N
+        self.entropy_coef *= self.entropy_coef_decay
+        a_slices, c_slices = minibatch_slices(rows, self.actor_batch_size), minibatch_slices(rows, self.critic_batch_size)
+        for k in range(len(self.actors)):
+            a_kw = dict(clip=self.clip, entropy_coef=self.entropy_coef, lam_T=self.lam_T, lam_S=self.lam_S, lam_M=self.lam_M,
+                        noise=self.noise[k], nominal=self.nominal[k], max_action=self.max_action, stats=self.actor_stats[k])
+            c_kw = dict(inputs=self.critic_inputs[k], l2_reg=self.l2_reg, stats=self.critic_stats[k])
+            actor, critic, opt_a, opt_c = self.actors[k], self.critics[k], self.actor_opts[k], self.critic_opts[k]
+            for _ in range(self.K_epochs):
+                perm = torch.randperm(rows, device=storage.device, generator=generator)
+                if self.actor_batch_size == self.critic_batch_size:
+                    both = [opt_a, opt_c]
+                    for sl in a_slices:
+                        actor_loss(actor, storage, k, advantage, perm[sl], **a_kw)
+                        critic_loss(critic, storage, k, perm[sl], **c_kw)
+                        DeviceAdamW.step_all(both)
+                else:
+                    for sl in a_slices:
+                        actor_loss(actor, storage, k, advantage, perm[sl], **a_kw)
+                        opt_a.step()
+                    for sl in c_slices:
+                        critic_loss(critic, storage, k, perm[sl], **c_kw)
+                        opt_c.step()
+        return self.actor_stats, self.critic_stats

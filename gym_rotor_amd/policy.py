@@ -388,7 +388,7 @@ def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional
     """The actor update of a training loop, as the reference writes it, without autograd: runs `storage.actor_grad` for agent k on the
     live `module` (attributes fc1, fc2, mean_linear, log_std — its tensors are read in place) and writes the gradients into
     `module.<param>.grad` in place (log_std in the module's [1, A] shape), as `loss.backward()` after `zero_grad()` leaves them.
-    Returns stats (stats[0] = the loss).  The optimiser step, gradient clipping and the schedule stay torch, on these .grad tensors."""
+    Returns stats (stats[0] = the loss).  Gradient clipping, the optimiser step and the schedule follow on these .grad tensors: `optim.DeviceAdamW` (one launch), or torch's."""
     params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.mean_linear.weight, module.mean_linear.bias,
               module.log_std)
     grads = {}
@@ -489,7 +489,7 @@ def critic_loss(module, storage, k: int, index: Optional[torch.Tensor] = None, i
     `storage.critic_grad` for agent k on the live `module` (attributes fc1, fc2, fc3 — its tensors are read in place; inputs: the
     agents whose observation rows it reads, `CriticParams.inputs`) and writes the gradients into `module.fc{1,2,3}.{weight,bias}.grad`
     in place, as `loss.backward()` after `zero_grad()` leaves them.  coeffs: l2_reg, target, stats, max_workgroups.  Returns stats
-    (stats[0] = the loss).  The optimiser step, gradient clipping and the schedule stay torch, on these .grad tensors."""
+    (stats[0] = the loss).  Gradient clipping, the optimiser step and the schedule follow on these .grad tensors: `optim.DeviceAdamW` (one launch), or torch's."""
     params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.fc3.weight, module.fc3.bias)
     if "grads" in coeffs:
         raise ValueError("critic_loss writes into the module's .grad tensors: it takes no grads")

@@ -8,7 +8,7 @@ writes observation / reward / done rows straight into them; GAE is one HIP launc
 (`qr_gae`: reverse scan over T per (env, agent) column), and so are the critic's values between the two
 (`qr_critic_values`, `qr_critic_next_values`: `compute_values`), and so is the actor's loss with its gradients per minibatch
 (`qr_ppo_actor_grad`: `actor_grad`), and so is the critic's loss with its gradients per minibatch (`qr_ppo_critic_grad`:
-`critic_grad`) — a whole PPO update needs torch only for the optimiser step.  Normalisation statistics can be
+`critic_grad`); the optimiser step that follows is `optim.DeviceAdamW` (`qr_adamw_step`).  Normalisation statistics can be
 all-reduced over the env shards (RCCL when launched under torchrun; gloo in the CPU tests).
 """
 from __future__ import annotations

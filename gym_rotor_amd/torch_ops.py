@@ -344,6 +344,19 @@ def qr_ppo_critic_grad(critic: List[torch.Tensor], inputs: List[int], obs0: Opti
                     stats=stats, max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_adamw_step", mutates_args=("params", "exp_avg", "exp_avg_sq", "step", "stats"))
+def qr_adamw_step(params: List[torch.Tensor], grads: List[torch.Tensor], exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor,
+                  stats: Optional[torch.Tensor], lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, max_norm: float,
+                  t0: int, eta_min: float) -> None:
+    """Gradient-norm clipping, one AdamW step and the cosine schedule for one parameter group (qr_adamw_step): params updated in place
+    from grads (read only), the moments and the int64 step counter in place, stats float32 [4] or None.  Everything else as
+    optim.adamw_step."""
+    from .optim import adamw_step
+    _gpu(exp_avg)
+    adamw_step(params, grads, exp_avg, exp_avg_sq, step, stats, lr=lr, betas=(beta1, beta2), eps=eps, weight_decay=weight_decay,
+               max_norm=max_norm, t0=t0, eta_min=eta_min)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

@@ -509,6 +509,34 @@ int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const
  * where it would refuse them. */
 int64_t qr_ppo_critic_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
 
+/* What follows each gradient launch in PPO.train (algos/ppo/ppo.py:185-190, 209-214) — torch.nn.utils.clip_grad_norm_,
+ * torch.optim.AdamW.step() (amsgrad = False, maximize = False) and CosineAnnealingWarmRestarts(T_0, eta_min).step() — for up to 8
+ * independent parameter groups in ONE launch, one workgroup per group.  A group is what one AdamW instance holds: an actor's seven
+ * tensors, a critic's six.  With t = *step + 1:
+ *     total_norm = the 2-norm over all of the group's gradient entries (float64 sums in a fixed order)
+ *     lr_t       = eta_min + (lr - eta_min) (1 + cos(pi ((t - 1) mod t0) / t0)) / 2     (t0 = 0: lr_t = lr) — the scheduler is stepped
+ *                  AFTER the optimiser, so the t-th optimiser step sees eta(t - 1)
+ *     clip_coef  = min(1, max_norm / (total_norm + 1e-6))                               (max_norm < 0: 1, clipping is off)
+ *     g = clip_coef grad;  p *= 1 - lr_t weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *     p -= (lr_t / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * the scalars in float64, the per-entry arithmetic in float32.  Parameters, exp_avg, exp_avg_sq and *step are updated in place;
+ * stats [4] = total_norm, clip_coef, lr_t, t.  The GRADIENT tensors are read only: unlike clip_grad_norm_, which scales .grad in
+ * place, they keep the unclipped gradient.  Non-finite gradients propagate (error_if_nonfinite = False).  No atomics: equal inputs
+ * give equal bits.  Groups must not share memory. */
+typedef struct QrAdamWGroup {
+  float* param[8];  const float* grad[8];  int32_t count[8];  int32_t n_tensors;   /* 1..8 tensors, count >= 1 each */
+  float* exp_avg;   float* exp_avg_sq;     /* [sum of count] each, the tensors back to back; zero before the first step */
+  int64_t* step;                            /* device: steps taken so far */
+  float* stats;                             /* device [4] or NULL */
+  double lr, eta_min;  int64_t t0;          /* base rate; schedule (t0 = 0: constant) */
+  float beta1, beta2, eps, weight_decay, max_norm;   /* max_norm < 0: no clipping */
+} QrAdamWGroup;
+/* QR_E_NULL for a NULL struct, param, grad, state or step pointer (stats optional); QR_E_SIZE for n_groups outside 1..8, n_tensors
+ * outside 1..8, a count < 1, a group of more than 65 536 entries, lr / eta_min / eps / weight_decay negative or not finite, a beta
+ * outside [0, 1), t0 < 0 or a NaN max_norm; QR_E_ALIGN for a float pointer that is not 4-byte aligned or a step pointer that is not
+ * 8-byte aligned.  Nothing is launched on an error. */
+int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -33,7 +33,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
-           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step")
+           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
+           "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -122,6 +123,53 @@ PPO_CRITIC_GRAD_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")  
 
 class QrCriticGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_CRITIC_GRAD_NAMES + ("stats",)]
+
+
+QCRITIC_MAX_IN, QCRITIC_MAX_HIDDEN = 28, 64   # qr_twinq_target / qr_twinq_grad: widest obs_dim + action_dim, widest hidden layer
+TWINQ_GRAD_NAMES = tuple(f"fc{k}_{x}" for k in range(1, 7) for x in "wb")   # qr_twinq_grad: the gradient tensors, in order
+
+
+class QrQCritic(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TWINQ_GRAD_NAMES] + [("obs_dim", C.c_int32), ("action_dim", C.c_int32), ("hidden_dim", C.c_int32),
+                                                              ("reserved0", C.c_int32)]
+
+
+class QrTransitions(C.Structure):
+    _fields_ = [("obs", C.c_void_p), ("obs_next", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("index", C.c_void_p), ("batch", C.c_int64), ("rows", C.c_int64), ("row_stride", C.c_int32), ("col_offset", C.c_int32),
+                ("reward_stride", C.c_int32), ("done_stride", C.c_int32)]
+
+
+class QrTd3Target(C.Structure):
+    _fields_ = [("eps", C.c_void_p), ("action_next", C.c_void_p), ("y", C.c_void_p), ("discount", C.c_float), ("target_noise", C.c_float),
+                ("noise_clip", C.c_float), ("max_action", C.c_float)]
+
+
+class QrTwinQGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TWINQ_GRAD_NAMES + ("stats", "y", "workspace")] + [("workspace_bytes", C.c_int64),
+                                                                                           ("max_workgroups", C.c_int32), ("reserved0", C.c_int32)]
+
+
+def transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None, index=None, batch, rows, row_stride=1, col_offset=0,
+                reward_stride=1, done_stride=1) -> QrTransitions:
+    """QrTransitions of one minibatch of a flat transition buffer; a tensor the entry point does not read stays None."""
+    b = QrTransitions()
+    b.obs, b.obs_next, b.action, b.reward, b.done, b.index = ptr(obs), ptr(obs_next), ptr(action), ptr(reward), ptr(done), ptr(index)
+    b.batch, b.rows = int(batch), int(rows)
+    b.row_stride, b.col_offset, b.reward_stride, b.done_stride = int(row_stride), int(col_offset), int(reward_stride), int(done_stride)
+    return b
+
+
+def td3_target_args(*, eps, action_next, y, discount, target_noise, noise_clip, max_action) -> QrTd3Target:
+    """QrTd3Target of one qr_twinq_target launch."""
+    return QrTd3Target(ptr(eps), ptr(action_next), ptr(y), float(discount), float(target_noise), float(noise_clip), float(max_action))
+
+
+def twinq_grad_args(grads, stats, y, workspace, max_workgroups) -> QrTwinQGrad:
+    """QrTwinQGrad of one qr_twinq_grad launch: grads = {name: tensor} over TWINQ_GRAD_NAMES."""
+    g = QrTwinQGrad(*[grads[n].data_ptr() for n in TWINQ_GRAD_NAMES], stats.data_ptr(), y.data_ptr(), workspace.data_ptr())
+    g.workspace_bytes, g.max_workgroups, g.reserved0 = workspace.numel() * workspace.element_size(), int(max_workgroups), 0
+    return g
 
 
 ADAMW_MAX_GROUPS, ADAMW_MAX_TENSORS, ADAMW_MAX_ENTRIES = 8, 8, 65536   # qr_adamw_step: groups per launch, tensors and entries per group
@@ -254,6 +302,12 @@ def load():
     lib.qr_ppo_critic_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_adamw_step.restype = C.c_int
     lib.qr_adamw_step.argtypes = [P(QrAdamWGroup), C.c_int32, C.c_void_p]
+    lib.qr_twinq_target.restype = C.c_int
+    lib.qr_twinq_target.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrTd3Target), C.c_void_p]
+    lib.qr_twinq_grad.restype = C.c_int
+    lib.qr_twinq_grad.argtypes = [P(QrQCritic), P(QrTransitions), P(QrTwinQGrad), C.c_void_p]
+    lib.qr_twinq_workspace_bytes.restype = C.c_int64
+    lib.qr_twinq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -46,6 +46,7 @@
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
+//   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -67,6 +68,7 @@
 #include "qr_ppo.h"
 #include "qr_ppo_critic.h"
 #include "qr_optim.h"
+#include "qr_td3.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -203,9 +205,124 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
   hipLaunchKernelGGL(ppo_critic_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1)), dim3(256), 0, s, r);
   return (int)hipGetLastError();
 }
+
+// The grid of qr_twinq_grad along x, per network (the launch has two such rows): a function of the batch and max_workgroups only
+// (0: 512, so that both rows together are the waves resident at once, one per SIMD at the kernel's register count: 256 CUs x 4).
+static int64_t twinq_grid(int64_t batch, int32_t max_workgroups) {
+  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : 512;
+  return tiles < cap ? tiles : cap;
+}
+
+static bool twinq_sizes_ok(int64_t obs_dim, int64_t action_dim, int64_t hidden) {
+  return obs_dim >= 1 && action_dim >= 1 && obs_dim + action_dim <= kTqIn && hidden >= 1 && hidden <= 64;
+}
+
+static int twinq_critic_check(const QrQCritic* c) {  // sizes, then pointers, as every entry point orders them
+  if (!twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) || c->reserved0 != 0) return QR_E_SIZE;
+  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b) return QR_E_NULL;
+  if (!c->fc4_w || !c->fc4_b || !c->fc5_w || !c->fc5_b || !c->fc6_w || !c->fc6_b) return QR_E_NULL;
+  return 0;
+}
+
+static void twinq_nets(TwinQNetW (&n)[2], const QrQCritic* c) {
+  n[0] = TwinQNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
+  n[1] = TwinQNetW{c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b};
+}
+
+static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrTd3Target* t, void* stream) {
+  if (!c || !b || !t) return QR_E_NULL;
+  if (p && (p->squash != QR_ACTOR_TANH_MEAN || p->log_std_w || p->log_std_b)) return QR_E_KIND;
+  if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
+  if (p && (!ppo_np(p->obs_dim, p->hidden_dim, p->action_dim) || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
+  if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
+  if (!(t->noise_clip >= 0.0f) || !(t->max_action >= 0.0f) || !(t->noise_clip <= 3.0e38f) || !(t->max_action <= 3.0e38f)) return QR_E_SIZE;
+  if (int rc = twinq_critic_check(c)) return rc;
+  if (p && (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b)) return QR_E_NULL;
+  if (!b->obs_next || !b->reward || !b->done || !t->y || (!p && !t->action_next)) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
+                                c->fc6_b, b->obs_next, b->reward, b->done, t->eps, t->action_next, t->y, p ? p->fc1_w : nullptr,
+                                p ? p->fc1_b : nullptr, p ? p->fc2_w : nullptr, p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr,
+                                p ? p->mean_b : nullptr};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if (reinterpret_cast<uintptr_t>(b->index) & 7u) return QR_E_ALIGN;
+
+  Td3TargetArgs a{};
+  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
+  twinq_nets(a.net, c);
+  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next;
+  a.index = b->index; a.y = t->y; a.B = b->batch; a.rows = b->rows;
+  a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.rwd_stride = b->reward_stride; a.done_stride = b->done_stride;
+  a.discount = t->discount; a.target_noise = t->target_noise; a.noise_clip = t->noise_clip; a.max_action = t->max_action;
+  // grid-stride over the tiles: at most the waves resident at once, one per SIMD at the kernel's register count
+  const int64_t tiles = (b->batch + 63) / 64;
+  const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ad = p ? p->obs_dim : 0;
+  if (ad == 23) hipLaunchKernelGGL(td3_target_kernel<23>, grid, dim3(64), 0, s, a);
+  else if (ad == 15) hipLaunchKernelGGL(td3_target_kernel<15>, grid, dim3(64), 0, s, a);
+  else if (ad == 3) hipLaunchKernelGGL(td3_target_kernel<3>, grid, dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(td3_target_kernel<0>, grid, dim3(64), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGrad* g, void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
+  if (b->batch < 1 || b->rows < 1 || b->row_stride < 1 || g->max_workgroups < 0 || g->reserved0 != 0) return QR_E_SIZE;
+  if (b->col_offset < 0 || b->col_offset + c->action_dim > b->row_stride) return QR_E_SIZE;
+  if (int rc = twinq_critic_check(c)) return rc;
+  float* const grads[12] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b, g->fc4_w, g->fc4_b, g->fc5_w, g->fc5_b, g->fc6_w, g->fc6_b};
+  for (const float* q : grads)
+    if (!q) return QR_E_NULL;
+  if (!g->stats || !g->y || !g->workspace || !b->obs || !b->action) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
+                                c->fc6_b, g->stats, g->y, b->obs, b->action};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (const float* q : grads)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
+  const int D = c->obs_dim + c->action_dim, H = c->hidden_dim;
+  const TwinQLayout Y(D, H);
+  const int64_t grid = twinq_grid(b->batch, g->max_workgroups);
+  if (g->workspace_bytes < 2 * grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  TwinQArgs a{};
+  twinq_nets(a.net, c);
+  a.obs = b->obs; a.action = b->action + b->col_offset; a.y = g->y; a.index = b->index; a.partials = static_cast<double*>(g->workspace);
+  a.B = b->batch; a.rows = b->rows; a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = H; a.act_stride = b->row_stride;
+  a.g_scale = (float)(2.0 / (double)b->batch);
+  TwinQReduceArgs r{};
+  r.partials = a.partials;
+  const int starts[7] = {Y.w1, Y.b1, Y.w2, Y.b2, Y.w3, Y.b3, Y.st};
+  for (int k = 0; k < 12; ++k) r.grad[k / 6][k % 6] = grads[k];
+  for (int k = 0; k < 7; ++k) r.off[k] = starts[k];
+  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(twinq_kernel, dim3((unsigned)grid, 2), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(twinq_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1), 2), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,
+                  void* stream) {
+  return qr::do_td3_target(actor_target, critic_target, batch, target, stream);
+}
+
+int qr_twinq_grad(const QrQCritic* critic, const QrTransitions* batch, const QrTwinQGrad* grad, void* stream) {
+  return qr::do_twinq(critic, batch, grad, stream);
+}
+
+int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {
+  if (in_dim < 2 || !qr::twinq_sizes_ok(in_dim - 1, 1, hidden_dim) || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return 2 * qr::twinq_grid(batch, max_workgroups) * qr::TwinQLayout(in_dim, hidden_dim).np * (int64_t)sizeof(double);
+}
 
 int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream) { return qr::do_adamw(groups, n_groups, stream); }
 

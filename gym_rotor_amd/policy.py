@@ -173,6 +173,74 @@ class CriticParams:
         return q
 
 
+@dataclass
+class QCriticParams:
+    """One agent's twin critic for the TD3 critic half (`td3.td3_target`, `td3.twinq_grad`): the reference's TD3 / SAC `MLP_Critic`
+    (algos/td3/td3_mlp.py:36-99: Q1 = fc3(relu(fc2(relu(fc1(sa))))), Q2 = fc6(relu(fc5(relu(fc4(sa))))), sa = the observation row
+    followed by the action row), obs_dim + action_dim up to 28 and hidden width up to 64.  The twelve tensors are the module's own
+    (contiguous float32, torch.nn.Linear layout), used by the kernels in place.  action_dim: how many of fc1's input columns are
+    the action's (the trailing ones)."""
+    fc1_w: torch.Tensor
+    fc1_b: torch.Tensor
+    fc2_w: torch.Tensor
+    fc2_b: torch.Tensor
+    fc3_w: torch.Tensor
+    fc3_b: torch.Tensor
+    fc4_w: torch.Tensor
+    fc4_b: torch.Tensor
+    fc5_w: torch.Tensor
+    fc5_b: torch.Tensor
+    fc6_w: torch.Tensor
+    fc6_b: torch.Tensor
+    action_dim: int = 4
+
+    NAMES = _lib.TWINQ_GRAD_NAMES
+
+    def __post_init__(self):
+        self.action_dim = int(self.action_dim)
+        if self.fc1_w.dim() != 2:
+            raise ValueError("critic tensor fc1_w must be [hidden, obs_dim + action_dim]")
+        hidden, din = self.fc1_w.shape
+        if not 2 <= din <= _lib.QCRITIC_MAX_IN or not 1 <= hidden <= _lib.QCRITIC_MAX_HIDDEN:
+            raise ValueError(f"twin critic sizes in = {din}, hidden = {hidden} are outside 2..{_lib.QCRITIC_MAX_IN} / 1..{_lib.QCRITIC_MAX_HIDDEN}")
+        if not 1 <= self.action_dim < din:
+            raise ValueError(f"twin critic: action_dim = {self.action_dim} must leave at least one observation column of the {din} inputs")
+        for n, s in self.shapes.items():
+            t = getattr(self, n)
+            if tuple(t.shape) != s or t.dtype != torch.float32 or t.device != self.fc1_w.device or not t.is_contiguous():
+                raise ValueError(f"critic tensor {n} must be a contiguous float32 {s} tensor on {self.fc1_w.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    @property
+    def shapes(self) -> dict:
+        hidden, din = self.fc1_w.shape
+        one = {"1_w": (hidden, din), "1_b": (hidden,), "2_w": (hidden, hidden), "2_b": (hidden,), "3_w": (1, hidden), "3_b": (1,)}
+        return {n: one[f"{(int(n[2]) - 1) % 3 + 1}{n[3:]}"] for n in self.NAMES}
+
+    @property
+    def dims(self):
+        """(obs_dim, action_dim, hidden width)"""
+        return (self.fc1_w.shape[1] - self.action_dim, self.action_dim, self.fc1_w.shape[0])
+
+    @property
+    def device(self):
+        return self.fc1_w.device
+
+    @classmethod
+    def from_module(cls, critic, action_dim: int) -> "QCriticParams":
+        """From a module shaped like the reference's twin critic (attributes fc1 .. fc6)."""
+        layers = [getattr(critic, f"fc{k}") for k in range(1, 7)]
+        return cls(*[t for l in layers for t in (l.weight.data, l.bias.data)], action_dim)
+
+    def as_c(self) -> _lib.QrQCritic:
+        q = _lib.QrQCritic()
+        for n in self.NAMES:
+            setattr(q, n, getattr(self, n).data_ptr())
+        q.obs_dim, q.action_dim, q.hidden_dim = self.dims
+        q.reserved0 = 0
+        return q
+
+
 def _element_stride(t: torch.Tensor, what: str) -> int:
     """The one stride between consecutive elements of `t` in row-major order (a column of a contiguous [.., n_agents] tensor)."""
     dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]

@@ -1,0 +1,264 @@
+"""The critic half of a TD3 update on the device: the replay buffer as flat device tensors (`ReplayBuffer`), the target values of a
+minibatch in one launch (`td3_target`: qr_twinq_target), the twin-Q loss and its twelve gradients in two (`twinq_grad`:
+qr_twinq_grad), and both on live modules (`td3_critic_loss`).
+
+Replaces, per minibatch of `TD3.train` (algos/td3/td3.py:111-171): five index clones, the actor-target forward pass, randn_like's
+two clamps, two twin-critic forward passes, min, the Bellman line, two mse_loss and the autograd backward pass.  The actor half
+(every policy_update_freq-th iteration), the soft target update and the optimiser group of twelve tensors are not here:
+`optim.DeviceAdamW` takes eight tensors, so a twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import _lib
+from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams
+
+
+class ReplayBuffer:
+    """The reference's `ReplayBuffer` (algos/replay_buffer.py) for TD3 / SAC as flat device tensors per agent k:
+        obs[k], obs_next[k] [capacity, D_k]   act[k] [capacity, A_k]   rwd[k], done[k] [capacity] float32 (done: 0.0 / 1.0)
+    `count` (the next row to write) and `current_size` follow the reference's ring rule, one transition at a time:
+    count = (count + 1) % capacity, current_size = min(current_size + 1, capacity)."""
+
+    def __init__(self, capacity: int, obs_dims: Sequence[int], action_dims: Sequence[int], device):
+        self.capacity = int(capacity)
+        self.obs_dims, self.action_dims = [int(d) for d in obs_dims], [int(a) for a in action_dims]
+        if self.capacity < 1 or len(self.obs_dims) != len(self.action_dims) or not self.obs_dims:
+            raise ValueError("ReplayBuffer needs capacity >= 1 and one obs_dim and one action_dim per agent")
+        self.device = torch.device(device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        n = self.capacity
+        self.obs = [torch.zeros(n, d, **f32) for d in self.obs_dims]
+        self.obs_next = [torch.zeros(n, d, **f32) for d in self.obs_dims]
+        self.act = [torch.zeros(n, a, **f32) for a in self.action_dims]
+        self.rwd = [torch.zeros(n, **f32) for _ in self.obs_dims]
+        self.done = [torch.zeros(n, **f32) for _ in self.obs_dims]
+        self.count, self.current_size = 0, 0
+        self._cache = {}   # (agent, B, max_workgroups) -> y, workspace, stats of td3_critic_loss
+
+    @property
+    def n_agents(self) -> int:
+        return len(self.obs_dims)
+
+    def add(self, storage) -> None:
+        """Append one collected `RolloutStorage` horizon: its T * N transitions in (t, n) order — what T * N calls of the reference's
+        store_transition leave, wrapping at capacity.  obs_next is the reference's: final_obs where the env was re-sampled in the
+        step (any agent's done, or truncated: qr_critic_next_values' rule), obs[t + 1] elsewhere; done is agent k's own flag.
+        Plain torch copies, once per horizon."""
+        T, N = storage.T, storage.N
+        n = T * N
+        if n > self.capacity:
+            raise ValueError(f"a horizon of {T} x {N} = {n} transitions does not fit a buffer of {self.capacity}")
+        if storage.n_agents != self.n_agents or [o.shape[-1] for o in storage.obs] != self.obs_dims or list(storage.action_dims) != self.action_dims:
+            raise ValueError("the storage's agents, observation widths or action widths differ from the buffer's")
+        reset = storage.reset_mask().reshape(n, 1) if storage.final_obs is not None else None
+        first = min(n, self.capacity - self.count)   # rows [count, count + first), then rows [0, n - first)
+        for k in range(self.n_agents):
+            nxt = storage.obs[k][1:].reshape(n, -1)
+            if reset is not None:
+                nxt = torch.where(reset, storage.final_obs[k].reshape(n, -1), nxt)
+            cols = ((self.obs[k], storage.obs[k][:-1].reshape(n, -1)), (self.obs_next[k], nxt), (self.act[k], storage.act[k].reshape(n, -1)),
+                    (self.rwd[k], storage.reward[..., k].reshape(n)), (self.done[k], storage.done[..., k].reshape(n).to(torch.float32)))
+            for dst, src in cols:
+                dst[self.count:self.count + first].copy_(src[:first])
+                if n > first:
+                    dst[:n - first].copy_(src[first:])
+        self.count = (self.count + n) % self.capacity
+        self.current_size = min(self.current_size + n, self.capacity)
+
+    def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """int64 [batch_size] rows below current_size, without replacement (np.random.choice(current_size, batch_size, replace=False))."""
+        batch_size = int(batch_size)
+        if not 1 <= batch_size <= self.current_size:
+            raise ValueError(f"cannot sample {batch_size} of {self.current_size} transitions without replacement")
+        return torch.randperm(self.current_size, device=self.device, generator=generator)[:batch_size]
+
+    def tensors(self, k: int) -> dict:
+        """Agent k's five tensors, as `td3_target` / `twinq_grad` take them."""
+        return {"obs": self.obs[k], "act": self.act[k], "rwd": self.rwd[k], "obs_next": self.obs_next[k], "done": self.done[k]}
+
+
+def _agent_tensors(buffer_or_tensors, k: int) -> dict:
+    return buffer_or_tensors.tensors(k) if isinstance(buffer_or_tensors, ReplayBuffer) else dict(buffer_or_tensors)
+
+
+def _check_index(index, dev, what: str):
+    if index is not None and (index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous()):
+        raise ValueError(f"{what}: index must be a contiguous int64 [B] tensor on {dev}")
+
+
+def _rows(t, width: int, dev, what: str, name: str) -> int:
+    if t is None or t.dtype != torch.float32 or t.device != dev or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous float32 [rows, {width}] tensor on {dev}")
+    return t.shape[0]
+
+
+def _column(t, rows: int, dev, what: str, name: str) -> int:
+    """Element stride of a float32 tensor of `rows` elements with one stride ([rows], [rows, 1] or a column of a wider tensor)."""
+    if t is None or t.dtype != torch.float32 or t.device != dev or t.numel() != rows:
+        raise ValueError(f"{what}: {name} must be float32 with {rows} elements on {dev}")
+    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]
+    if len(dims) > 1 or (dims and dims[0][1] < 1):
+        raise ValueError(f"{what}: {name} must have one positive element stride, got shape {tuple(t.shape)} strides {t.stride()}")
+    return dims[0][1] if dims else 1
+
+
+def td3_target(actor_target: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
+               index: Optional[torch.Tensor] = None, *, discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5,
+               max_action: float = 1.0, noise: Optional[torch.Tensor] = None, action_next: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TD3's target values of one minibatch in one launch (qr_twinq_target; td3.py:139-154), j the minibatch position, i = index[j]:
+        a'_j = clamp(actor_target(obs_next[i]) + clamp(target_noise * noise[j], +-noise_clip), +-max_action)
+        y[j] = rwd[i] + discount * (1 - done[i]) * min(Q1, Q2)(obs_next[i], a'_j)
+    actor_target: `ActorParams.from_td3_module(module, 0.0)` (the tanh-of-mean form in one of the three sizes of the rollout; its
+    log_std is not read), or None with action_next [B, A] float32: a'_j = action_next[j] as it is.  buffer_or_tensors: a
+    `ReplayBuffer` (agent k's tensors) or a dict with obs_next [rows, D], rwd, done (float32, `rows` elements, one stride).
+    noise: float32 [B, A] standard-normal draws by minibatch position, None: no smoothing noise.  index: int64 [B], None: all rows
+    in order.  Returns y float32 [B] (`out` given: written in place)."""
+    what = "td3_target"
+    t = _agent_tensors(buffer_or_tensors, k)
+    dev = critic_target.device
+    D, A, H = critic_target.dims
+    rows = _rows(t.get("obs_next"), D, dev, what, "obs_next")
+    rs, ds = _column(t.get("rwd"), rows, dev, what, "rwd"), _column(t.get("done"), rows, dev, what, "done")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    if actor_target is not None:
+        if actor_target.dims not in PPO_ACTOR_DIMS:
+            raise ValueError(f"{what}: actor sizes {actor_target.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
+        if actor_target.squash != _lib.ACTOR_TANH_MEAN or actor_target.log_std_w is not None:
+            raise ValueError(f"{what}: the target actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
+        if (actor_target.dims[0], actor_target.dims[2]) != (D, A):
+            raise ValueError(f"{what}: the actor maps {actor_target.dims[0]} -> {actor_target.dims[2]}, the critic reads {D} + {A}")
+        Da, Ha, Aa = actor_target.dims
+        ashapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
+        for n, shp in ashapes.items():   # (log_std is not read: whatever it holds is not checked)
+            w = getattr(actor_target, n)
+            if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
+                raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
+    elif action_next is None:
+        raise ValueError(f"{what}: without a target actor, action_next [B, {A}] is required")
+    for name, x in (("noise", noise), ("action_next", action_next)):
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:
+        return out
+    b = _lib.transitions(obs_next=t["obs_next"], reward=t["rwd"], done=t["done"], index=index, batch=B, rows=rows, reward_stride=rs, done_stride=ds)
+    g = _lib.td3_target_args(eps=noise, action_next=action_next, y=out, discount=discount, target_noise=target_noise, noise_clip=noise_clip,
+                             max_action=max_action)
+    q = critic_target.as_c()
+    if actor_target is not None:
+        p = actor_target.as_c()
+        p.log_std = None
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_twinq_target(C.byref(p) if actor_target is not None else None, C.byref(q), C.byref(b), C.byref(g),
+                                       torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_twinq_target")
+    return out
+
+
+def twinq_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `twinq_grad` call needs (qr_twinq_workspace_bytes); dims = (obs_dim, action_dim, hidden width)."""
+    n = _lib.load().qr_twinq_workspace_bytes(int(dims[0]) + int(dims[1]), int(dims[2]), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_twinq_workspace_bytes")
+    return int(n)
+
+
+def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None, *,
+               grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+               max_workgroups: int = 0):
+    """The twin-Q regression against a given target and its gradients (qr_twinq_grad; td3.py:157-167 without the equivariant term,
+    and SAC's critic loss): loss = mean_j (Q1(obs[i], action[i]) - y[j])^2 + mean_j (Q2(obs[i], action[i]) - y[j])^2, i = index[j] —
+    no autograd, no copies of the minibatch's rows.  obs [rows, D] contiguous float32; action float32 [rows, >= A] whose rows lie one
+    row stride apart (the critic reads the leading A columns: pass a per-agent view of wider rows as it is); y float32 [B] by
+    minibatch position; index int64 [B], None: all rows in order.
+    Returns (grads, stats): grads = {name: float32 tensor} for fc1_w .. fc6_b — `grads` given: overwritten in place — and stats
+    float32 [4] = loss, the Q1 mse, the Q2 mse, the mean of y."""
+    what = "twinq_grad"
+    dev = critic.device
+    D, A, H = critic.dims
+    rows = _rows(obs, D, dev, what, "obs")
+    if (action is None or action.dtype != torch.float32 or action.device != dev or action.dim() != 2 or action.shape[0] != rows or action.shape[1] < A
+            or (action.shape[1] > 1 and action.stride(1) != 1) or action.stride(0) < action.shape[1]):
+        raise ValueError(f"{what}: action must be float32 [{rows}, >= {A}] rows with unit column stride on {dev}")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    if y is None or y.dtype != torch.float32 or y.device != dev or y.numel() != B or not y.is_contiguous():
+        raise ValueError(f"{what}: y must be a contiguous float32 [{B}] tensor on {dev}")
+    shapes = critic.shapes
+    if grads is None:
+        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
+    for n, s in shapes.items():
+        g = grads.get(n)
+        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
+            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
+        for n in shapes:
+            grads[n].zero_()
+        stats.zero_()
+        return grads, stats
+    need = twinq_workspace_bytes(critic.dims, B, max_workgroups)
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
+    b = _lib.transitions(obs=obs, action=action, index=index, batch=B, rows=rows, row_stride=action.stride(0) if rows > 1 else max(action.shape[1], 1))
+    g = _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups)
+    q = critic.as_c()
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_twinq_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_twinq_grad")
+    return grads, stats
+
+
+def td3_critic_loss(critic_module, critic_target_module, actor_target_module, buffer: ReplayBuffer, k: int = 0,
+                    index: Optional[torch.Tensor] = None, *, discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5,
+                    max_action: float = 1.0, noise: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                    max_workgroups: int = 0) -> torch.Tensor:
+    """The critic update of TD3.train, as the reference writes it, without autograd: `td3_target` on the target modules, then
+    `twinq_grad` on the live `critic_module` (attributes fc1 .. fc6 — its tensors are read in place) for agent k of `buffer`; writes
+    the gradients into `critic_module.fc{1..6}.{weight,bias}.grad` in place, as `loss.backward()` after `zero_grad()` leaves them.
+    The defaults are the reference's (args_parse.py:44-58).  noise: the [B, A] standard-normal draws of the target policy smoothing
+    (torch.randn_like in the reference), None: none.  Returns stats (stats[0] = the loss).  From the second call on with an unchanged
+    B nothing is allocated: y, the workspace and stats are cached on the buffer.  The optimiser step follows on these .grad tensors:
+    two `optim.DeviceAdamW` groups of six tensors, or torch's."""
+    A = buffer.action_dims[k]
+    layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
+    grads = {}
+    for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    critic = QCriticParams.from_module(critic_module, A)
+    B = buffer.capacity if index is None else index.numel()
+    key = (k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = twinq_workspace_bytes(critic.dims, B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
+                                    torch.empty(4, dtype=torch.float32, device=dev))
+    y, workspace, own_stats = hit
+    m = actor_target_module
+    actor = ActorParams(m.fc1.weight.data, m.fc1.bias.data, m.fc2.weight.data, m.fc2.bias.data, m.fc3.weight.data, m.fc3.bias.data, None)
+    td3_target(actor, QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
+               noise_clip=noise_clip, max_action=max_action, noise=noise, out=y)
+    _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
+                          workspace=workspace, max_workgroups=max_workgroups)
+    return stats

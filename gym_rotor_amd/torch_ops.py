@@ -357,6 +357,42 @@ def qr_adamw_step(params: List[torch.Tensor], grads: List[torch.Tensor], exp_avg
                max_norm=max_norm, t0=t0, eta_min=eta_min)
 
 
+def _qcritic_params(critic: Sequence[torch.Tensor], action_dim: int):
+    from .policy import QCriticParams
+    if len(critic) != 12:
+        raise ValueError("a twin critic is 12 tensors: fc1_w, fc1_b, ..., fc6_w, fc6_b")
+    return QCriticParams(*critic, int(action_dim))
+
+
+@torch.library.custom_op(f"{_NS}::qr_twinq_target", mutates_args=("y",))
+def qr_twinq_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
+                  done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],
+                  y: torch.Tensor, discount: float, target_noise: float, noise_clip: float, max_action: float) -> None:
+    """TD3's target values of one minibatch (qr_twinq_target).  actor: the target actor's six tensors fc1_w, fc1_b, fc2_w, fc2_b, fc3_w,
+    fc3_b, or an empty list with action_next; critic: the target critic's twelve tensors.  Everything else as td3.td3_target."""
+    from .policy import ActorParams
+    from .td3 import td3_target
+    _gpu(y)
+    if len(actor) not in (0, 6):
+        raise ValueError("a TD3 actor is 6 tensors: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b")
+    td3_target(ActorParams(*actor, None) if actor else None, _qcritic_params(critic, action_dim),
+               {"obs_next": obs_next, "rwd": reward, "done": done}, 0, index, discount=discount, target_noise=target_noise,
+               noise_clip=noise_clip, max_action=max_action, noise=noise, action_next=action_next, out=y)
+
+
+@torch.library.custom_op(f"{_NS}::qr_twinq_grad", mutates_args=("grads", "stats"))
+def qr_twinq_grad(critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor, action: torch.Tensor, y: torch.Tensor,
+                  index: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor, max_workgroups: int = 0) -> None:
+    """The twin-Q loss against y and its twelve gradients for one minibatch (qr_twinq_grad).  critic and grads: twelve tensors each, fc1_w,
+    fc1_b, ..., fc6_w, fc6_b; stats float32 [4].  Everything else as td3.twinq_grad."""
+    from .td3 import twinq_grad
+    _gpu(stats)
+    if len(grads) != 12:
+        raise ValueError("grads is 12 tensors: fc1_w, fc1_b, ..., fc6_w, fc6_b")
+    twinq_grad(_qcritic_params(critic, action_dim), obs, action, y, index, grads=dict(zip(_lib.TWINQ_GRAD_NAMES, grads)), stats=stats,
+               max_workgroups=max_workgroups)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

@@ -537,6 +537,81 @@ typedef struct QrAdamWGroup {
  * 8-byte aligned.  Nothing is launched on an error. */
 int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream);
 
+/* The critic half of one TD3 minibatch update (TD3.train, algos/td3/td3.py:123-167, the non-CTDE branch) for ONE agent, read from a
+ * flat transition buffer in place, without autograd.  The reference's twin critic MLP_Critic (algos/td3/td3_mlp.py:36-99), twelve
+ * float32 tensors in torch.nn.Linear layout, used in place:
+ *     Q1 = fc3(relu(fc2(relu(fc1(sa)))))     Q2 = fc6(relu(fc5(relu(fc4(sa)))))     sa = the observation row followed by the action row
+ * obs_dim >= 1, action_dim >= 1, obs_dim + action_dim <= 28, 1 <= hidden_dim <= 64.  reserved0 must be 0 (a later CTDE form, rows
+ * from four sources, takes it). */
+typedef struct QrQCritic {
+  const float *fc1_w, *fc1_b;       /* [hidden][obs_dim+action_dim], [hidden]     Q1 */
+  const float *fc2_w, *fc2_b;       /* [hidden][hidden], [hidden]                    */
+  const float *fc3_w, *fc3_b;       /* [1][hidden], [1]                              */
+  const float *fc4_w, *fc4_b;       /* as fc1                                     Q2 */
+  const float *fc5_w, *fc5_b;       /* as fc2                                        */
+  const float *fc6_w, *fc6_b;       /* as fc3                                        */
+  int32_t obs_dim, action_dim;
+  int32_t hidden_dim, reserved0;
+} QrQCritic;
+/* What the reference's ReplayBuffer (algos/replay_buffer.py) holds for one agent, as flat float32 tensors, and one minibatch of it:
+ *   obs, obs_next [>= rows][obs_dim]; action: row i at action + i * row_stride + col_offset (as in QrPpoBatch); reward, done: element
+ *   i at reward[i * reward_stride], done[i * done_stride] (done is 0.0 or 1.0); index: int64 [batch] or NULL (rows 0 .. batch - 1;
+ *   repeats are legal, a value outside [0, rows) is clamped into it).  A pointer the entry point does not read may be NULL:
+ *   qr_twinq_target reads obs_next, reward, done and index; qr_twinq_grad reads obs, action and index. */
+typedef struct QrTransitions {
+  const float* obs;        const float* obs_next;
+  const float* action;
+  const float* reward;     const float* done;
+  const int64_t* index;
+  int64_t batch, rows;                                /* B >= 1; rows an index may name */
+  int32_t row_stride, col_offset;                     /* of the action rows */
+  int32_t reward_stride, done_stride;
+} QrTransitions;
+/* The TD3 target of a minibatch in ONE launch (td3.py:139-154), j the minibatch position and i = index[j]:
+ *     a'_j = clamp(pi_targ(obs_next[i]) + clamp(target_noise * eps[j], +-noise_clip), +-max_action)
+ *     y[j] = reward[i] + discount * (1 - done[i]) * min(Q1_targ, Q2_targ)(obs_next[i], a'_j)
+ * pi_targ: a QrActor of the QR_ACTOR_TANH_MEAN form (MLP_Actor_TD3: tanh(fc3(relu(fc2(relu(fc1(x))))))) in one of
+ * qr_ppo_actor_grad's three sizes, its obs_dim and action_dim equal to the critic's; its log_std is not read.  eps: [batch][action_dim]
+ * float32 standard-normal draws, row j for minibatch position j (not for index[j]); NULL: no smoothing noise, the same bits as
+ * zeros.  actor_target NULL: a'_j = action_next[j] ([batch][action_dim], used as it is: eps and the clamps do not apply) — the
+ * next action of another policy form (SAC's sample), or a critic wider than any actor this library holds.  A row with done = 1 gets
+ * y = reward exactly (for finite Q).  Only the rows the index names are read.  y: [batch] float32, plain stores. */
+typedef struct QrTd3Target {
+  const float* eps;
+  const float* action_next;
+  float* y;
+  float discount, target_noise, noise_clip, max_action;
+} QrTd3Target;
+/* QR_E_NULL for a NULL critic, batch or target struct, weight, obs_next, reward, done or y pointer, or actor_target and action_next
+ * both NULL; QR_E_KIND for an actor with squash != QR_ACTOR_TANH_MEAN or a log_std head; QR_E_SIZE for widths outside the ranges
+ * above, reserved0 != 0, an actor size other than (23,16,4), (15,16,4), (3,4,1), an actor whose obs_dim or action_dim differs from
+ * the critic's, batch < 1, rows < 1, a stride < 1 or a negative or non-finite noise_clip / max_action; QR_E_ALIGN for a float pointer
+ * that is not 4-byte aligned or an index pointer that is not 8-byte aligned.  Nothing is launched on an error. */
+int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,
+                  void* stream);
+/* The twin-Q regression against a given target (td3.py:157-167 without the equivariant term; SAC's critic update has the same form):
+ *     loss = (1/B) sum_j (Q1(obs[i], action[i]) - y[j])^2 + (1/B) sum_j (Q2(obs[i], action[i]) - y[j])^2,      i = index[j]
+ * and loss.backward()'s gradients for the twelve tensors.  y: [batch] float32 by minibatch position (qr_twinq_target's output).
+ * Outputs, overwritten: the gradient tensors in the shapes of the QrQCritic's and stats [4] = loss, the Q1 mse, the Q2 mse, the
+ * mean of y.  Two launches: one wavefront per workgroup owns ONE of the two networks, accumulates its share of the 64-row tiles and
+ * writes ONE partial vector into `workspace`; a second kernel sums the partial vectors in float64 in a fixed order.  The same inputs
+ * and grid give the same bits (no atomics).  The grid is 2 x min(ceil(batch / 64), max_workgroups), max_workgroups = 0: the
+ * library's rule (512 per network). */
+typedef struct QrTwinQGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *fc3_w, *fc3_b, *fc4_w, *fc4_b, *fc5_w, *fc5_b, *fc6_w, *fc6_b, *stats;
+  const float* y;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_twinq_workspace_bytes(...); 8-byte aligned */
+  int32_t max_workgroups, reserved0;
+} QrTwinQGrad;
+/* QR_E_NULL for a NULL struct, weight, obs, action, y, output or workspace pointer (index optional); QR_E_SIZE for widths outside
+ * the ranges above, reserved0 != 0, batch < 1, rows < 1, row_stride < 1, a column offset outside the row, max_workgroups < 0 or a
+ * workspace that is too small; QR_E_ALIGN for a float pointer that is not 4-byte aligned or an index / workspace pointer that is not
+ * 8-byte aligned.  Nothing is launched on an error. */
+int qr_twinq_grad(const QrQCritic* critic, const QrTransitions* batch, const QrTwinQGrad* grad, void* stream);
+/* Bytes of workspace qr_twinq_grad needs for this critic size (in_dim = obs_dim + action_dim), batch and max_workgroups; QR_E_SIZE
+ * (< 0) where it would refuse them. */
+int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

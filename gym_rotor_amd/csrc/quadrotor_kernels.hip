@@ -44,6 +44,7 @@
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
 //   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
+//   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): the half-tile gradient body, the partial vector, the reduction's sums
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel
@@ -156,12 +157,15 @@ static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* 
   return (int)hipGetLastError();
 }
 
-// The grid of qr_ppo_critic_grad: a function of the batch and max_workgroups only (0: the waves resident at once, one per SIMD at
-// the kernel's register count: 256 CUs x 4; its 29 KB of LDS admit five workgroups per CU).
-static int64_t ppo_critic_grid(int64_t batch, int32_t max_workgroups) {
-  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : 1024;
+// The grid of an MLP-critic gradient launch (along x): a function of the batch and max_workgroups only.  0: default_cap, the waves
+// resident at once, one per SIMD at the kernels' register count — 256 CUs x 4 = 1024 for qr_ppo_critic_grad (its 29 KB of LDS
+// would admit five workgroups per CU), 512 for each of qr_twinq_grad's two rows.
+static int64_t mlp_grad_grid(int64_t batch, int32_t max_workgroups, int64_t default_cap) {
+  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : default_cap;
   return tiles < cap ? tiles : cap;
 }
+static int64_t ppo_critic_grid(int64_t batch, int32_t max_workgroups) { return mlp_grad_grid(batch, max_workgroups, 1024); }
+static int64_t twinq_grid(int64_t batch, int32_t max_workgroups) { return mlp_grad_grid(batch, max_workgroups, 512); }
 
 static bool ppo_critic_sizes_ok(int64_t in0, int64_t in1, int64_t hidden) {
   return in0 >= 0 && in1 >= 0 && in0 <= kCriticIn && in1 <= kCriticIn && in0 + in1 >= 1 && in0 + in1 <= kCriticIn && hidden >= 1 && hidden <= 64;
@@ -180,12 +184,12 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
     if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
   if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(b->workspace)) & 7u) return QR_E_ALIGN;
   const int D = c->in0 + c->in1, H = c->hidden_dim;
-  const PpoCriticLayout Y(D, H);
+  const MlpGradLayout Y(D, H, kPcSums);
   const int64_t grid = ppo_critic_grid(b->batch, b->max_workgroups);
   if (b->workspace_bytes < grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
 
   PpoCriticArgs a{};
-  a.fc1_w = c->fc1_w; a.fc1_b = c->fc1_b; a.fc2_w = c->fc2_w; a.fc2_b = c->fc2_b; a.fc3_w = c->fc3_w; a.fc3_b = c->fc3_b;
+  a.w = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
   a.rows0 = c->in0 ? b->obs0 : nullptr; a.rows1 = c->in1 ? b->obs1 : nullptr;
   a.target = b->target; a.index = b->index; a.partials = static_cast<double*>(b->workspace);
   a.B = b->batch; a.rows = b->rows; a.in0 = c->in0; a.in1 = c->in1; a.hidden = H; a.tgt_stride = b->target_stride;
@@ -194,9 +198,8 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
   r.partials = a.partials;
   r.weight[0] = c->fc1_w; r.weight[1] = c->fc2_w; r.weight[2] = c->fc3_w;
   float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b};
-  const int starts[7] = {Y.w1, Y.b1, Y.w2, Y.b2, Y.w3, Y.b3, Y.st};
   for (int k = 0; k < 6; ++k) r.grad[k] = grads[k];
-  for (int k = 0; k < 7; ++k) r.off[k] = starts[k];
+  Y.starts(r.off);
   r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch; r.l2_reg = b->l2_reg;
 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -206,15 +209,8 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
   return (int)hipGetLastError();
 }
 
-// The grid of qr_twinq_grad along x, per network (the launch has two such rows): a function of the batch and max_workgroups only
-// (0: 512, so that both rows together are the waves resident at once, one per SIMD at the kernel's register count: 256 CUs x 4).
-static int64_t twinq_grid(int64_t batch, int32_t max_workgroups) {
-  const int64_t tiles = (batch + 63) / 64, cap = max_workgroups > 0 ? max_workgroups : 512;
-  return tiles < cap ? tiles : cap;
-}
-
 static bool twinq_sizes_ok(int64_t obs_dim, int64_t action_dim, int64_t hidden) {
-  return obs_dim >= 1 && action_dim >= 1 && obs_dim + action_dim <= kTqIn && hidden >= 1 && hidden <= 64;
+  return obs_dim >= 1 && action_dim >= 1 && obs_dim + action_dim <= TwinQL1::XS && hidden >= 1 && hidden <= 64;
 }
 
 static int twinq_critic_check(const QrQCritic* c) {  // sizes, then pointers, as every entry point orders them
@@ -224,9 +220,9 @@ static int twinq_critic_check(const QrQCritic* c) {  // sizes, then pointers, as
   return 0;
 }
 
-static void twinq_nets(TwinQNetW (&n)[2], const QrQCritic* c) {
-  n[0] = TwinQNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
-  n[1] = TwinQNetW{c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b};
+static void twinq_nets(MlpNetW (&n)[2], const QrQCritic* c) {
+  n[0] = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
+  n[1] = MlpNetW{c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b};
 }
 
 static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrTd3Target* t, void* stream) {
@@ -284,7 +280,7 @@ static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGra
     if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
   if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
   const int D = c->obs_dim + c->action_dim, H = c->hidden_dim;
-  const TwinQLayout Y(D, H);
+  const MlpGradLayout Y(D, H, kTqSums);
   const int64_t grid = twinq_grid(b->batch, g->max_workgroups);
   if (g->workspace_bytes < 2 * grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
 
@@ -295,9 +291,8 @@ static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGra
   a.g_scale = (float)(2.0 / (double)b->batch);
   TwinQReduceArgs r{};
   r.partials = a.partials;
-  const int starts[7] = {Y.w1, Y.b1, Y.w2, Y.b2, Y.w3, Y.b3, Y.st};
   for (int k = 0; k < 12; ++k) r.grad[k / 6][k % 6] = grads[k];
-  for (int k = 0; k < 7; ++k) r.off[k] = starts[k];
+  Y.starts(r.off);
   r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch;
 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -321,7 +316,7 @@ int qr_twinq_grad(const QrQCritic* critic, const QrTransitions* batch, const QrT
 
 int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {
   if (in_dim < 2 || !qr::twinq_sizes_ok(in_dim - 1, 1, hidden_dim) || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
-  return 2 * qr::twinq_grid(batch, max_workgroups) * qr::TwinQLayout(in_dim, hidden_dim).np * (int64_t)sizeof(double);
+  return 2 * qr::twinq_grid(batch, max_workgroups) * qr::MlpGradLayout(in_dim, hidden_dim, qr::kTqSums).np * (int64_t)sizeof(double);
 }
 
 int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream) { return qr::do_adamw(groups, n_groups, stream); }
@@ -332,7 +327,7 @@ int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const
 
 int64_t qr_ppo_critic_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {
   if (!qr::ppo_critic_sizes_ok(in_dim, 0, hidden_dim) || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
-  return qr::ppo_critic_grid(batch, max_workgroups) * qr::PpoCriticLayout(in_dim, hidden_dim).np * (int64_t)sizeof(double);
+  return qr::ppo_critic_grid(batch, max_workgroups) * qr::MlpGradLayout(in_dim, hidden_dim, qr::kPcSums).np * (int64_t)sizeof(double);
 }
 
 int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream) {

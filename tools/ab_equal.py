@@ -2,6 +2,10 @@
 """Do two builds of the library compute the same bits?  Each build (QR_LIB) steps the same batch (QR_AB_KIND, default quad; QR_AB_ENVS, default 65 536
 envs) with in-launch resets in its own subprocess and prints a digest of state, integrators, parameters, observation rows, rewards,
 dones, terminal observations, episode and tile counters — then the same for qr_rollout and (wrappers) qr_rollout_actor with a PPO and an SAC actor.
+A third digest covers the update launches: ppo_critic_grad on every case of tests/golden/ppo_critic_grad.npz (gradients, stats), td3_target
+and twinq_grad on every case of tests/golden/td3_critic.npz (y, the twelve gradients, stats), each at the default grid, at
+max_workgroups 1 and 3, and once with a permuted index.
+A build whose child does not exit 0 within QR_AB_TIMEOUT seconds (default 900) ends the run: nothing more is started on the card.
 
     [QR_AB_KIND=coupled] python tools/ab_equal.py build/ab/A.so build/ab/B.so        (GPU box)
 """
@@ -52,11 +56,52 @@ if kind != "quad":
         env.get_norm_error_state()
         upd(env.rollout_actor(actors, 8))
     h.update(env.get_current_state().cpu().numpy().tobytes()); h.update(env._integ.cpu().numpy().tobytes())
-print(step_digest, h.hexdigest(), int(env._episode.sum()))
-''' % ROOT
+rollout_digest = h.hexdigest()
+# the update launches on the fixtures of their tests
+import numpy as np
+sys.path.insert(0, os.path.join(%r, "tests"))
+import td3_ref, test_ppo_critic_host as pch, test_td3_critic_host as tch
+from gym_rotor_amd import ActorParams, CriticParams, QCriticParams, ppo_critic_grad, td3_target, twinq_grad
+h = hashlib.sha256()
+cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+perm = cuda(np.random.default_rng(0).permutation(130).astype(np.int64))
+def put(*ts):
+    for x in ts:
+        h.update(x.cpu().numpy().tobytes())
+g = dict(np.load(os.path.join(%r, "tests", "golden", "ppo_critic_grad.npz"), allow_pickle=False))
+for name in pch.CASES:
+    c = pch.case(g, name)
+    critic, obs, tgt = CriticParams(*[cuda(t) for t in c["w"]], c["inputs"]), [cuda(o) for o in c["obs"]], cuda(c["target"])
+    for index, mw in ((None, 0), (None, 1), (None, 3), (perm, 0)):
+        grads, stats = ppo_critic_grad(critic, obs, tgt, index, l2_reg=c["l2_reg"], max_workgroups=mw)
+        put(*[grads[n] for n in pch.NAMES], stats)
+g = td3_ref.load()
+for name in tch.CASES:
+    c = td3_ref.case(g, name)
+    critic, critic_t = (QCriticParams(*[cuda(c[p + n]) for n in td3_ref.NAMES], int(c["action_dim"])) for p in ("c_", "t_"))
+    actor_t = ActorParams(*[cuda(c["a_" + n]) for n in td3_ref.ACTOR_NAMES], None) if "a_fc1_w" in c else None
+    tens = {"obs": cuda(c["obs"]), "act": cuda(c["action"]), "rwd": cuda(c["reward"]), "obs_next": cuda(c["obs_next"]), "done": cuda(c["done"])}
+    kw = {k: float(c[k]) for k in ("discount", "target_noise", "noise_clip", "max_action")}
+    kw["noise"] = None if c.get("eps") is None else cuda(c["eps"])
+    if actor_t is None:
+        kw["action_next"] = cuda(c["a_next_in"])
+    for index, mw in ((None, 0), (None, 1), (None, 3), (perm, 0)):
+        y = td3_target(actor_t, critic_t, tens, 0, index, **kw)
+        grads, stats = twinq_grad(critic, tens["obs"], tens["act"], y, index, max_workgroups=mw)
+        put(y, *[grads[n] for n in td3_ref.NAMES], stats)
+torch.cuda.synchronize()
+print(step_digest, rollout_digest, h.hexdigest(), int(env._episode.sum()))
+''' % (ROOT, ROOT, ROOT)
 out = []
 for lib in sys.argv[1:3]:
-    r = subprocess.run([sys.executable, "-c", CHILD], env=dict(os.environ, QR_LIB=os.path.abspath(lib)), capture_output=True, text=True)
-    out.append(r.stdout.strip().splitlines()[-1] if r.returncode == 0 else "FAILED " + r.stderr[-300:])
+    try:
+        r = subprocess.run([sys.executable, "-c", CHILD], env=dict(os.environ, QR_LIB=os.path.abspath(lib)), capture_output=True, text=True,
+                           timeout=float(os.environ.get("QR_AB_TIMEOUT", "900")))
+    except subprocess.TimeoutExpired:
+        sys.exit(f"{os.path.basename(lib)} FAILED: time limit; nothing more is started")
+    if r.returncode != 0:
+        sys.exit(f"{os.path.basename(lib)} FAILED (exit {r.returncode}); nothing more is started\n{r.stderr[-600:]}")
+    out.append(r.stdout.strip().splitlines()[-1])
     print(os.path.basename(lib), out[-1])
-print("IDENTICAL" if out[0] == out[1] and not out[0].startswith("FAILED") else "DIFFERENT")
+print("IDENTICAL" if out[0] == out[1] else "DIFFERENT")
+sys.exit(0 if out[0] == out[1] else 1)

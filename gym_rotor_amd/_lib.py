@@ -34,7 +34,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
            "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
-           "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes")
+           "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
+           "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update")
 
 
 class QrCoeffs(C.Structure):
@@ -150,6 +151,21 @@ class QrTwinQGrad(C.Structure):
                                                                                            ("max_workgroups", C.c_int32), ("reserved0", C.c_int32)]
 
 
+DPG_GRAD_NAMES = PPO_GRAD_NAMES[:6]   # qr_dpg_actor_grad: the gradient tensors, in order
+SOFT_UPDATE_MAX = 24                  # qr_soft_update: tensors per launch
+
+
+class QrDpgGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in DPG_GRAD_NAMES + ("stats", "noise", "nominal", "workspace")] + [
+        ("workspace_bytes", C.c_int64), ("lam_T", C.c_float), ("lam_S", C.c_float), ("lam_M", C.c_float), ("max_action", C.c_float),
+        ("max_workgroups", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class QrSoftUpdate(C.Structure):
+    _fields_ = [("target", C.c_void_p * 24), ("param", C.c_void_p * 24), ("count", C.c_int64 * 24), ("n_tensors", C.c_int32),
+                ("reserved0", C.c_int32), ("tau", C.c_double)]
+
+
 def transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None, index=None, batch, rows, row_stride=1, col_offset=0,
                 reward_stride=1, done_stride=1) -> QrTransitions:
     """QrTransitions of one minibatch of a flat transition buffer; a tensor the entry point does not read stays None."""
@@ -170,6 +186,24 @@ def twinq_grad_args(grads, stats, y, workspace, max_workgroups) -> QrTwinQGrad:
     g = QrTwinQGrad(*[grads[n].data_ptr() for n in TWINQ_GRAD_NAMES], stats.data_ptr(), y.data_ptr(), workspace.data_ptr())
     g.workspace_bytes, g.max_workgroups, g.reserved0 = workspace.numel() * workspace.element_size(), int(max_workgroups), 0
     return g
+
+
+def dpg_grad_args(grads, stats, noise, nominal, workspace, *, lam_T, lam_S, lam_M, max_action, max_workgroups) -> QrDpgGrad:
+    """QrDpgGrad of one qr_dpg_actor_grad launch: grads = {name: tensor} over DPG_GRAD_NAMES."""
+    g = QrDpgGrad(*[grads[n].data_ptr() for n in DPG_GRAD_NAMES], stats.data_ptr(), ptr(noise), ptr(nominal), workspace.data_ptr())
+    g.workspace_bytes = workspace.numel() * workspace.element_size()
+    g.lam_T, g.lam_S, g.lam_M, g.max_action = float(lam_T), float(lam_S), float(lam_M), float(max_action)
+    g.max_workgroups, g.reserved0 = int(max_workgroups), 0
+    return g
+
+
+def soft_update_args(params, targets, tau) -> QrSoftUpdate:
+    """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
+    u = QrSoftUpdate()
+    u.n_tensors, u.reserved0, u.tau = len(params), 0, float(tau)
+    for k, (p, t) in enumerate(zip(params, targets)):
+        u.param[k], u.target[k], u.count[k] = p.data_ptr(), t.data_ptr(), t.numel()
+    return u
 
 
 ADAMW_MAX_GROUPS, ADAMW_MAX_TENSORS, ADAMW_MAX_ENTRIES = 8, 8, 65536   # qr_adamw_step: groups per launch, tensors and entries per group
@@ -308,6 +342,12 @@ def load():
     lib.qr_twinq_grad.argtypes = [P(QrQCritic), P(QrTransitions), P(QrTwinQGrad), C.c_void_p]
     lib.qr_twinq_workspace_bytes.restype = C.c_int64
     lib.qr_twinq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_dpg_actor_grad.restype = C.c_int
+    lib.qr_dpg_actor_grad.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrDpgGrad), C.c_void_p]
+    lib.qr_dpg_actor_workspace_bytes.restype = C.c_int64
+    lib.qr_dpg_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_soft_update.restype = C.c_int
+    lib.qr_soft_update.argtypes = [P(QrSoftUpdate), C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

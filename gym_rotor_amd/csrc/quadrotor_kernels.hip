@@ -48,6 +48,7 @@
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel
+//   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -70,6 +71,7 @@
 #include "qr_ppo_critic.h"
 #include "qr_optim.h"
 #include "qr_td3.h"
+#include "qr_td3_actor.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -301,9 +303,105 @@ static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGra
   hipLaunchKernelGGL(twinq_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1), 2), dim3(256), 0, s, r);
   return (int)hipGetLastError();
 }
+
+// The grid of qr_dpg_actor_grad: ppo_grid's rule (0: one wave per SIMD at the kernel's register count, 256 CUs x 4).
+static int dpg_np(int32_t d, int32_t h, int32_t a) {  // length of a partial vector; 0: not one of the rollout's actor sizes
+  if (d == 23 && h == 16 && a == 4) return DpgLayout<23, 16, 4>::NP;
+  if (d == 15 && h == 16 && a == 4) return DpgLayout<15, 16, 4>::NP;
+  if (d == 3 && h == 4 && a == 1) return DpgLayout<3, 4, 1>::NP;
+  return 0;
+}
+
+static bool nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
+
+static int do_dpg_actor(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrDpgGrad* g, void* stream) {
+  if (!p || !c || !b || !g) return QR_E_NULL;
+  if (p->squash != QR_ACTOR_TANH_MEAN || p->log_std_w || p->log_std_b) return QR_E_KIND;
+  const int np = dpg_np(p->obs_dim, p->hidden_dim, p->action_dim);
+  if (!np || !twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) || c->reserved0 != 0) return QR_E_SIZE;
+  if (p->obs_dim != c->obs_dim || p->action_dim != c->action_dim) return QR_E_SIZE;
+  if (b->batch < 1 || b->rows < 1 || g->max_workgroups < 0 || g->reserved0 != 0) return QR_E_SIZE;
+  if (!nonneg_finite(g->max_action) || !nonneg_finite(g->lam_T) || !nonneg_finite(g->lam_S) || !nonneg_finite(g->lam_M)) return QR_E_SIZE;
+  if (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b) return QR_E_NULL;
+  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b) return QR_E_NULL;  // (Q2 is not read)
+  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->mean_w || !g->mean_b || !g->stats || !g->workspace) return QR_E_NULL;
+  if (!b->obs || (g->lam_T != 0.0f && !b->obs_next) || (g->lam_S != 0.0f && !g->noise) || (g->lam_M != 0.0f && !g->nominal)) return QR_E_NULL;
+  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w,
+                                c->fc3_b, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->stats, g->noise, g->nominal, b->obs,
+                                b->obs_next};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
+  const int64_t grid = ppo_grid(b->batch, g->max_workgroups);
+  if (g->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
+  const double B = (double)b->batch, ba = B * A;
+  DpgArgs a{};
+  // log_std: PpoNet::fill copies action_dim floats from it into a slot this kernel never reads; mean_b is such an array
+  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->mean_b, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
+  a.q = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
+  a.obs = b->obs; a.obs_next = g->lam_T != 0.0f ? b->obs_next : nullptr; a.index = b->index;
+  a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
+  a.partials = static_cast<double*>(g->workspace);
+  a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim; a.max_action = g->max_action;
+  a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
+  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * g->lam_T / ba); a.c_S = (float)(2.0 * g->lam_S / ba); a.c_M = (float)(2.0 * g->lam_M / ba);
+  DpgReduceArgs r{};
+  r.partials = a.partials;
+  float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b};
+  const int sizes[6] = {H * D, H, H * H, H, A * H, A};
+  for (int k = 0; k < 6; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
+  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = np; r.B = B; r.BA = ba; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (D == 23) hipLaunchKernelGGL((dpg_actor_kernel<23, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  else if (D == 15) hipLaunchKernelGGL((dpg_actor_kernel<15, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((dpg_actor_kernel<3, 4, 1>), dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(dpg_reduce_kernel, dim3((unsigned)((r.off[6] + 15) / 16 + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
+
+static int do_soft_update(const QrSoftUpdate* u, void* stream) {
+  if (!u) return QR_E_NULL;
+  if (u->n_tensors < 1 || u->n_tensors > kSoftMax || u->reserved0 != 0 || !(u->tau >= 0.0 && u->tau <= 1.0)) return QR_E_SIZE;
+  for (int k = 0; k < u->n_tensors; ++k)
+    if (u->count[k] < 1) return QR_E_SIZE;
+  for (int k = 0; k < u->n_tensors; ++k)
+    if (!u->target[k] || !u->param[k]) return QR_E_NULL;
+  for (int k = 0; k < u->n_tensors; ++k)
+    if (u->target[k] == u->param[k]) return QR_E_SIZE;
+  for (int k = 0; k < u->n_tensors; ++k)
+    if ((reinterpret_cast<uintptr_t>(u->target[k]) | reinterpret_cast<uintptr_t>(u->param[k])) & 3u) return QR_E_ALIGN;
+  SoftUpdateArgs a{};
+  int64_t widest = 0;
+  for (int k = 0; k < u->n_tensors; ++k) {
+    a.target[k] = u->target[k]; a.param[k] = u->param[k]; a.count[k] = u->count[k];
+    widest = u->count[k] > widest ? u->count[k] : widest;
+  }
+  a.tau = (float)u->tau; a.omt = (float)(1.0 - u->tau);
+  const int64_t cols = (widest + 255) / 256;
+  hipLaunchKernelGGL(soft_update_kernel, dim3((unsigned)(cols < kSoftCols ? cols : kSoftCols), (unsigned)u->n_tensors), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_dpg_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTransitions* batch, const QrDpgGrad* grad, void* stream) {
+  return qr::do_dpg_actor(actor, critic, batch, grad, stream);
+}
+
+int64_t qr_dpg_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
+                                     int32_t max_workgroups) {
+  const int np = qr::dpg_np(obs_dim, hidden_dim, action_dim);
+  if (!np || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * np * (int64_t)sizeof(double);
+}
+
+int qr_soft_update(const QrSoftUpdate* update, void* stream) { return qr::do_soft_update(update, stream); }
 
 int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,
                   void* stream) {

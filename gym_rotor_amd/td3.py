@@ -1,16 +1,19 @@
-"""The critic half of a TD3 update on the device: the replay buffer as flat device tensors (`ReplayBuffer`), the target values of a
-minibatch in one launch (`td3_target`: qr_twinq_target), the twin-Q loss and its twelve gradients in two (`twinq_grad`:
-qr_twinq_grad), and both on live modules (`td3_critic_loss`).
+"""A TD3 update on the device: the replay buffer as flat device tensors (`ReplayBuffer`), the target values of a minibatch in one
+launch (`td3_target`: qr_twinq_target), the twin-Q loss and its twelve gradients in two (`twinq_grad`: qr_twinq_grad), both on live
+modules (`td3_critic_loss`); the actor's loss -mean Q1(s, pi(s)) with its smoothness terms and its six gradients in two launches
+(`dpg_actor_grad`: qr_dpg_actor_grad; on live modules `td3_actor_loss`), and the soft target update of all tensors in one
+(`soft_update`: qr_soft_update).
 
-Replaces, per minibatch of `TD3.train` (algos/td3/td3.py:111-171): five index clones, the actor-target forward pass, randn_like's
-two clamps, two twin-critic forward passes, min, the Bellman line, two mse_loss and the autograd backward pass.  The actor half
-(every policy_update_freq-th iteration), the soft target update and the optimiser group of twelve tensors are not here:
-`optim.DeviceAdamW` takes eight tensors, so a twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
+Replaces, per minibatch of `TD3.train` (algos/td3/td3.py:111-211): the index clones, the actor-target forward pass, randn_like's two
+clamps, two twin-critic forward passes, min, the Bellman line, two mse_loss and the autograd backward pass; and every
+policy_update_freq-th iteration three actor passes, the Q1 pass, the backward pass through the critic and three times through the
+actor, and eighteen copy_ lines.  The optimiser group of twelve tensors is not here: `optim.DeviceAdamW` takes eight tensors, so a
+twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -38,7 +41,7 @@ class ReplayBuffer:
         self.rwd = [torch.zeros(n, **f32) for _ in self.obs_dims]
         self.done = [torch.zeros(n, **f32) for _ in self.obs_dims]
         self.count, self.current_size = 0, 0
-        self._cache = {}   # (agent, B, max_workgroups) -> y, workspace, stats of td3_critic_loss
+        self._cache = {}   # (agent, B, max_workgroups) -> y, workspace, stats of td3_critic_loss; ("actor", ...) -> td3_actor_loss's
 
     @property
     def n_agents(self) -> int:
@@ -262,3 +265,160 @@ def td3_critic_loss(critic_module, critic_target_module, actor_target_module, bu
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
                           workspace=workspace, max_workgroups=max_workgroups)
     return stats
+
+
+def dpg_actor_workspace_bytes(actor_dims, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `dpg_actor_grad` call needs (qr_dpg_actor_workspace_bytes); actor_dims = (obs_dim, hidden, action_dim)."""
+    n = _lib.load().qr_dpg_actor_workspace_bytes(*(int(d) for d in actor_dims), int(critic_hidden), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_dpg_actor_workspace_bytes")
+    return int(n)
+
+
+def _vector(t, width: int, dev, what: str, name: str):
+    if t is not None and (t.dtype != torch.float32 or t.device != dev or t.numel() != width or not t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {width} elements on {dev}")
+
+
+def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor, obs_next: Optional[torch.Tensor] = None,
+                   index: Optional[torch.Tensor] = None, *, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0,
+                   noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None, grads: Optional[dict] = None,
+                   stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, max_workgroups: int = 0):
+    """TD3's actor loss and its gradients (qr_dpg_actor_grad; td3.py:183-196 without the equivariant term, with
+    algos/policy_regularization.py), c = clamp to +-max_action, i = index[j]:
+        loss = -mean_j Q1(obs[i], c(pi(obs[i]))) + lam_T mse(c(pi(obs[i])), c(pi(obs_next[i])))
+               + lam_S mse(c(pi(obs[i])), c(pi(obs[i] + noise))) + lam_M mse(c(pi(obs[i])), nominal)
+    — no autograd, no copies of the minibatch's rows.  actor: MLP_Actor_TD3's six tensors as `ActorParams` (the tanh-of-mean form in
+    one of the three sizes of the rollout; its log_std is not read); critic: the twin critic, of which Q1 is read.  obs, obs_next
+    [rows, D] contiguous float32 (obs_next: needed when lam_T != 0); noise [D]: ONE row, needed when lam_S != 0; nominal [A]: needed
+    when lam_M != 0; index int64 [B], None: all rows in order.
+    Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b — `grads` given: overwritten
+    in place — and stats float32 [4] = loss, the mean of Q1, the share of pi(obs)'s components outside +-max_action, the weighted sum
+    of the three smoothness terms."""
+    what = "dpg_actor_grad"
+    dev = critic.device
+    D, A, H = critic.dims
+    if actor.dims not in PPO_ACTOR_DIMS:
+        raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
+    if actor.squash != _lib.ACTOR_TANH_MEAN or actor.log_std_w is not None:
+        raise ValueError(f"{what}: the actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
+    if (actor.dims[0], actor.dims[2]) != (D, A):
+        raise ValueError(f"{what}: the actor maps {actor.dims[0]} -> {actor.dims[2]}, the critic reads {D} + {A}")
+    Da, Ha, Aa = actor.dims
+    shapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
+    for n, shp in shapes.items():   # (log_std is not read: whatever it holds is not checked)
+        w = getattr(actor, n)
+        if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
+            raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
+    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
+        if not 0.0 <= float(v) < float("inf"):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    rows = _rows(obs, D, dev, what, "obs")
+    if lam_T != 0 and _rows(obs_next, D, dev, what, "obs_next") != rows:
+        raise ValueError(f"{what}: obs_next must have obs's {rows} rows")
+    if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
+        raise ValueError(f"{what}: noise [{D}] is required when lam_S != 0, nominal [{A}] when lam_M != 0")
+    _vector(noise, D, dev, what, "noise")
+    _vector(nominal, A, dev, what, "nominal")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    if grads is None:
+        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
+    for n, s in shapes.items():
+        g = grads.get(n)
+        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
+            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
+        for n in shapes:
+            grads[n].zero_()
+        stats.zero_()
+        return grads, stats
+    if workspace is None:
+        workspace = torch.empty(dpg_actor_workspace_bytes(actor.dims, H, B, max_workgroups) // 8, dtype=torch.float64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
+    b = _lib.transitions(obs=obs, obs_next=obs_next if lam_T != 0 else None, index=index, batch=B, rows=rows)
+    g = _lib.dpg_grad_args(grads, stats, noise if lam_S != 0 else None, nominal if lam_M != 0 else None, workspace, lam_T=lam_T, lam_S=lam_S,
+                           lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
+    p, q = actor.as_c(), critic.as_c()
+    p.log_std = None
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_dpg_actor_grad(C.byref(p), C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_dpg_actor_grad")
+    return grads, stats
+
+
+def td3_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                   lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, noise: Optional[torch.Tensor] = None,
+                   nominal: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """The actor update of TD3.train, as the reference writes it, without autograd: `dpg_actor_grad` on the live `actor_module`
+    (attributes fc1, fc2, fc3) and `critic_module` (fc1 .. fc6, of which Q1 is read) for agent k of `buffer`; writes the gradients into
+    `actor_module.fc{1,2,3}.{weight,bias}.grad` in place, as `loss.backward()` after `zero_grad()` leaves them.  The defaults are the
+    reference's (args_parse.py); noise: policy_regularization's ONE [D] row of N(0, 0.05) draws; nominal: its [A] hover action.
+    Returns stats (stats[0] = the loss).  From the second call on with an unchanged B nothing is allocated: the workspace and stats
+    are cached on the buffer.  The optimiser step follows on these .grad tensors (`optim.DeviceAdamW`, or torch's), then
+    `soft_update`."""
+    layers = [actor_module.fc1, actor_module.fc2, actor_module.fc3]
+    grads = {}
+    for n, p in zip(_lib.DPG_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    actor = ActorParams(*(t.data for l in layers for t in (l.weight, l.bias)), None)
+    critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
+    B = buffer.capacity if index is None else index.numel()
+    key = ("actor", k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = dpg_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.float32, device=dev))
+    workspace, own_stats = hit
+    _, stats = dpg_actor_grad(actor, critic, buffer.obs[k], buffer.obs_next[k], index, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                              max_action=max_action, noise=noise, nominal=nominal, grads=grads, stats=own_stats if stats is None else stats,
+                              workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def _tensors_of(x):
+    """The tensors of a module (its parameters, in order), of a sequence of modules, or a sequence of tensors as it is."""
+    if isinstance(x, torch.nn.Module):
+        return [p.data for p in x.parameters()]
+    out = []
+    for e in x:
+        out += [p.data for p in e.parameters()] if isinstance(e, torch.nn.Module) else [e]
+    return out
+
+
+def soft_update(params, targets, tau: float = 0.005) -> None:
+    """TD3's soft target update (td3.py:207-211) of up to 24 tensors in ONE launch (qr_soft_update), in place on the targets:
+        target = tau * param + (1 - tau) * target
+    with the bits of the reference's `target_param.data.copy_(tau * param.data + (1 - tau) * target_param.data)`.  params, targets: a
+    module, a sequence of modules (their parameters in order: `soft_update([critic, actor], [critic_t, actor_t])`) or a sequence of
+    tensors, pairwise of equal element counts; contiguous float32 on one GPU."""
+    what = "soft_update"
+    ps, ts = _tensors_of(params), _tensors_of(targets)
+    if len(ps) != len(ts) or not 1 <= len(ps) <= _lib.SOFT_UPDATE_MAX:
+        raise ValueError(f"{what}: needs 1..{_lib.SOFT_UPDATE_MAX} (param, target) pairs, got {len(ps)} params and {len(ts)} targets")
+    if not 0.0 <= float(tau) <= 1.0:
+        raise ValueError(f"{what}: tau must lie in [0, 1], got {tau}")
+    dev = ts[0].device
+    for k, (p, t) in enumerate(zip(ps, ts)):
+        for name, x in (("param", p), ("target", t)):
+            if x.dtype != torch.float32 or x.device != dev or not x.is_contiguous() or x.numel() < 1:
+                raise ValueError(f"{what}: {name} {k} must be a non-empty contiguous float32 tensor on {dev}")
+        if p.numel() != t.numel():
+            raise ValueError(f"{what}: pair {k} has {p.numel()} and {t.numel()} elements")
+        if p.data_ptr() == t.data_ptr():
+            raise ValueError(f"{what}: pair {k}: the target is its own param")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    u = _lib.soft_update_args(ps, ts, tau)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_soft_update(C.byref(u), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_soft_update")

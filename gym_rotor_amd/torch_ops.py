@@ -393,6 +393,30 @@ def qr_twinq_grad(critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor
                max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_dpg_actor_grad", mutates_args=("grads", "stats"))
+def qr_dpg_actor_grad(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor, obs_next: Optional[torch.Tensor],
+                      index: Optional[torch.Tensor], noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor], grads: List[torch.Tensor],
+                      stats: torch.Tensor, lam_T: float, lam_S: float, lam_M: float, max_action: float, max_workgroups: int = 0) -> None:
+    """TD3's actor loss and its six gradients for one minibatch (qr_dpg_actor_grad).  actor and grads: six tensors each, fc1_w, fc1_b,
+    fc2_w, fc2_b, fc3_w, fc3_b; critic: the twin critic's twelve; stats float32 [4].  Everything else as td3.dpg_actor_grad."""
+    from .policy import ActorParams
+    from .td3 import dpg_actor_grad
+    _gpu(stats)
+    if len(actor) != 6 or len(grads) != 6:
+        raise ValueError("a TD3 actor and its gradients are 6 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b")
+    dpg_actor_grad(ActorParams(*actor, None), _qcritic_params(critic, action_dim), obs, obs_next, index, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                   max_action=max_action, noise=noise, nominal=nominal, grads=dict(zip(_lib.DPG_GRAD_NAMES, grads)), stats=stats,
+                   max_workgroups=max_workgroups)
+
+
+@torch.library.custom_op(f"{_NS}::qr_soft_update", mutates_args=("targets",))
+def qr_soft_update(params: List[torch.Tensor], targets: List[torch.Tensor], tau: float) -> None:
+    """target = tau * param + (1 - tau) * target for up to 24 tensor pairs in one launch (qr_soft_update), as td3.soft_update."""
+    from .td3 import soft_update
+    _gpu(targets[0])
+    soft_update(list(params), list(targets), tau)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

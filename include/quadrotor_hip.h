@@ -612,6 +612,61 @@ int qr_twinq_grad(const QrQCritic* critic, const QrTransitions* batch, const QrT
  * (< 0) where it would refuse them. */
 int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
 
+/* The actor half of one TD3 minibatch update (TD3.train, algos/td3/td3.py:177-196, the non-CTDE branch without the equivariant
+ * term, with algos/policy_regularization.py) for ONE agent, read from the transition buffer in place: the loss and loss.backward()'s
+ * gradients with respect to the actor's six tensors, without autograd.  With j the minibatch position and i = index[j]:
+ *     a_j     = clamp(pi(obs[i]), +-max_action)              pi = tanh(fc3(relu(fc2(relu(fc1 x)))))     (MLP_Actor_TD3)
+ *     a_next  = clamp(pi(obs_next[i]), +-max_action)
+ *     a_pert  = clamp(pi(obs[i] + noise), +-max_action)      noise: ONE [obs_dim] row, broadcast
+ *     loss    = -(1/B) sum_j Q1(obs[i], a_j) + lam_T mse(a, a_next) + lam_S mse(a, a_pert) + lam_M mse(a, nominal)
+ * mse: the mean over the B x action_dim elements.  The gradients flow through all three evaluations of pi (neither a_next nor a_pert
+ * is detached) and through Q1 into a; the critic's own gradients are not produced.  clamp routes a gradient where |pi| <= max_action,
+ * as torch.clamp does.  A coefficient lam_* equal to 0 skips that term's passes.
+ *   actor: a QrActor of the QR_ACTOR_TANH_MEAN form in one of the sizes (23,16,4), (15,16,4), (3,4,1); its log_std is not read.
+ *   critic: a QrQCritic as above whose obs_dim and action_dim equal the actor's; only fc1 .. fc3 (Q1) are read, fc4 .. fc6 may be NULL.
+ *   batch: obs, obs_next (read only with lam_T != 0) and index of a QrTransitions (index: int64 [batch] or NULL; repeats are legal, a
+ *   value outside [0, rows) is clamped into it).  noise [obs_dim]: required when lam_S != 0; nominal [action_dim]: when lam_M != 0.
+ * Outputs, overwritten: the six gradient tensors in the shapes of the QrActor's and stats [4] = loss, the mean of Q1(obs, a), the share
+ * of the B x action_dim components of pi(obs) with |pi| > max_action (an exact count over B x action_dim), and
+ * lam_T L_T + lam_S L_S + lam_M L_M.
+ * Two launches: one wavefront per workgroup accumulates its share of the 64-row tiles and writes ONE partial vector into `workspace`;
+ * a second kernel sums the partial vectors in float64 in a fixed order.  The same inputs and grid give the same bits (no atomics).
+ * The grid is min(ceil(batch / 64), max_workgroups), max_workgroups = 0: the library's rule (1024). */
+typedef struct QrDpgGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *mean_w, *mean_b, *stats;
+  const float* noise;      const float* nominal;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_dpg_actor_workspace_bytes(...); 8-byte aligned */
+  float lam_T, lam_S, lam_M, max_action;
+  int32_t max_workgroups, reserved0;
+} QrDpgGrad;
+/* QR_E_NULL for a NULL struct, actor weight, Q1 weight, obs, output or workspace pointer (index optional; obs_next, noise, nominal as
+ * above); QR_E_KIND for squash != QR_ACTOR_TANH_MEAN or an actor with a log_std head; QR_E_SIZE for an actor size other than the
+ * three above, critic widths outside their ranges, an actor whose obs_dim or action_dim differs from the critic's, reserved0 != 0
+ * (either struct), batch < 1, rows < 1, max_workgroups < 0, a negative or non-finite max_action or lam_*, or a workspace that is too
+ * small; QR_E_ALIGN for a float pointer that is not 4-byte aligned or an index / workspace pointer that is not 8-byte aligned.
+ * Nothing is launched on an error. */
+int qr_dpg_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTransitions* batch, const QrDpgGrad* grad, void* stream);
+/* Bytes of workspace qr_dpg_actor_grad needs for this actor size, critic width, batch and max_workgroups; QR_E_SIZE (< 0) where it
+ * would refuse them. */
+int64_t qr_dpg_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
+                                     int32_t max_workgroups);
+
+/* The soft (Polyak) target update of TD3.train (td3.py:207-211) for up to 24 tensors in ONE launch — a twin critic's twelve and an
+ * actor's six with room to spare:
+ *     target[k][i] = fl(fl(tau32 * param[k][i]) + fl(omt32 * target[k][i])),   tau32 = float32(tau), omt32 = float32(1.0 - tau)
+ * float32 in torch's order, every operation rounded on its own (no fused multiply-add), the subtraction 1.0 - tau in double: the bits
+ * of `target_param.data.copy_(tau * param.data + (1 - tau) * target_param.data)`.  In place on `target`; `param` is read only.
+ * Tensors must not overlap. */
+typedef struct QrSoftUpdate {
+  float* target[24];  const float* param[24];  int64_t count[24];   /* entries of each tensor, >= 1 */
+  int32_t n_tensors, reserved0;                                     /* 1..24; 0 */
+  double tau;                                                       /* in [0, 1] */
+} QrSoftUpdate;
+/* QR_E_NULL for a NULL struct, target or param pointer; QR_E_SIZE for n_tensors outside 1..24, reserved0 != 0, a count < 1, tau
+ * outside [0, 1] or not finite, or a target pointer equal to its param pointer; QR_E_ALIGN for a pointer that is not 4-byte aligned.
+ * Nothing is launched on an error. */
+int qr_soft_update(const QrSoftUpdate* update, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

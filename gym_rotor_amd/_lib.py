@@ -35,7 +35,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
            "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
            "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
-           "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update")
+           "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target")
 
 
 class QrCoeffs(C.Structure):
@@ -166,6 +166,11 @@ class QrSoftUpdate(C.Structure):
                 ("reserved0", C.c_int32), ("tau", C.c_double)]
 
 
+class QrSacTarget(C.Structure):
+    _fields_ = [("eps", C.c_void_p), ("action_next", C.c_void_p), ("logp_next", C.c_void_p), ("alpha_dev", C.c_void_p), ("y", C.c_void_p),
+                ("action_out", C.c_void_p), ("logp_out", C.c_void_p), ("discount", C.c_float), ("alpha", C.c_float)]
+
+
 def transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None, index=None, batch, rows, row_stride=1, col_offset=0,
                 reward_stride=1, done_stride=1) -> QrTransitions:
     """QrTransitions of one minibatch of a flat transition buffer; a tensor the entry point does not read stays None."""
@@ -179,6 +184,12 @@ def transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None,
 def td3_target_args(*, eps, action_next, y, discount, target_noise, noise_clip, max_action) -> QrTd3Target:
     """QrTd3Target of one qr_twinq_target launch."""
     return QrTd3Target(ptr(eps), ptr(action_next), ptr(y), float(discount), float(target_noise), float(noise_clip), float(max_action))
+
+
+def sac_target_args(*, eps, action_next, logp_next, alpha_dev, y, action_out, logp_out, discount, alpha) -> QrSacTarget:
+    """QrSacTarget of one qr_sac_target launch; alpha_dev: the device scalar that wins over `alpha`, or None."""
+    return QrSacTarget(ptr(eps), ptr(action_next), ptr(logp_next), ptr(alpha_dev), ptr(y), ptr(action_out), ptr(logp_out), float(discount),
+                       float(alpha))
 
 
 def twinq_grad_args(grads, stats, y, workspace, max_workgroups) -> QrTwinQGrad:
@@ -348,6 +359,8 @@ def load():
     lib.qr_dpg_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_soft_update.restype = C.c_int
     lib.qr_soft_update.argtypes = [P(QrSoftUpdate), C.c_void_p]
+    lib.qr_sac_target.restype = C.c_int
+    lib.qr_sac_target.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrSacTarget), C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -49,6 +49,7 @@
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
+//   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_target_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
@@ -72,6 +73,7 @@
 #include "qr_optim.h"
 #include "qr_td3.h"
 #include "qr_td3_actor.h"
+#include "qr_sac.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -264,6 +266,45 @@ static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitio
   return (int)hipGetLastError();
 }
 
+static int do_sac_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrSacTarget* t, void* stream) {
+  if (!c || !b || !t) return QR_E_NULL;
+  if (p && (p->squash != QR_ACTOR_TANH_SAMPLE || !p->log_std_w || !p->log_std_b)) return QR_E_KIND;
+  if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
+  if (p && (!ppo_np(p->obs_dim, p->hidden_dim, p->action_dim) || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
+  if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
+  if (!(t->discount >= 0.0f) || !(t->alpha >= 0.0f) || !(t->discount <= 3.0e38f) || !(t->alpha <= 3.0e38f)) return QR_E_SIZE;
+  if (int rc = twinq_critic_check(c)) return rc;
+  if (p && (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b)) return QR_E_NULL;
+  if (!b->obs_next || !b->reward || !b->done || !t->y || (!p && (!t->action_next || !t->logp_next))) return QR_E_NULL;
+  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
+                                c->fc6_b, b->obs_next, b->reward, b->done, t->eps, t->action_next, t->logp_next, t->alpha_dev, t->y,
+                                t->action_out, t->logp_out, p ? p->fc1_w : nullptr, p ? p->fc1_b : nullptr, p ? p->fc2_w : nullptr,
+                                p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr, p ? p->mean_b : nullptr, p ? p->log_std_w : nullptr,
+                                p ? p->log_std_b : nullptr};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if (reinterpret_cast<uintptr_t>(b->index) & 7u) return QR_E_ALIGN;
+
+  SacTargetArgs a{};
+  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, p->log_std_w, p->log_std_b, QR_ACTOR_TANH_SAMPLE};
+  twinq_nets(a.net, c);
+  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.eps = p ? t->eps : nullptr;
+  a.action_next = p ? nullptr : t->action_next; a.logp_next = p ? nullptr : t->logp_next; a.alpha_dev = t->alpha_dev;
+  a.index = b->index; a.y = t->y; a.action_out = t->action_out; a.logp_out = t->logp_out; a.B = b->batch; a.rows = b->rows;
+  a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.rwd_stride = b->reward_stride; a.done_stride = b->done_stride;
+  a.discount = t->discount; a.alpha = t->alpha;
+  // qr_twinq_target's grid: grid-stride over the tiles, at most the waves resident at once, one per SIMD at the kernel's register count
+  const int64_t tiles = (b->batch + 63) / 64;
+  const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int ad = p ? p->obs_dim : 0;
+  if (ad == 23) hipLaunchKernelGGL(sac_target_kernel<23>, grid, dim3(64), 0, s, a);
+  else if (ad == 15) hipLaunchKernelGGL(sac_target_kernel<15>, grid, dim3(64), 0, s, a);
+  else if (ad == 3) hipLaunchKernelGGL(sac_target_kernel<3>, grid, dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(sac_target_kernel<0>, grid, dim3(64), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGrad* g, void* stream) {
   if (!c || !b || !g) return QR_E_NULL;
   if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
@@ -402,6 +443,10 @@ int64_t qr_dpg_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_
 }
 
 int qr_soft_update(const QrSoftUpdate* update, void* stream) { return qr::do_soft_update(update, stream); }
+
+int qr_sac_target(const QrActor* actor, const QrQCritic* critic_target, const QrTransitions* batch, const QrSacTarget* target, void* stream) {
+  return qr::do_sac_target(actor, critic_target, batch, target, stream);
+}
 
 int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,
                   void* stream) {

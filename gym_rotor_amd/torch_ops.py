@@ -417,6 +417,24 @@ def qr_soft_update(params: List[torch.Tensor], targets: List[torch.Tensor], tau:
     soft_update(list(params), list(targets), tau)
 
 
+@torch.library.custom_op(f"{_NS}::qr_sac_target", mutates_args=("y", "action_out", "logp_out"))
+def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
+                  done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],
+                  logp_next: Optional[torch.Tensor], y: torch.Tensor, action_out: Optional[torch.Tensor], logp_out: Optional[torch.Tensor],
+                  discount: float, alpha: float, alpha_dev: Optional[torch.Tensor] = None) -> None:
+    """SAC's target values of one minibatch (qr_sac_target).  actor: the live actor's eight tensors fc1_w, fc1_b, fc2_w, fc2_b, mean_w,
+    mean_b, log_std_w, log_std_b, or an empty list with action_next and logp_next; critic: the target critic's twelve tensors; alpha_dev:
+    the temperature as a device tensor of one element, which wins over alpha.  Everything else as sac.sac_target."""
+    from .policy import ActorParams
+    from .sac import sac_target
+    _gpu(y)
+    if len(actor) not in (0, 8):
+        raise ValueError("a SAC actor is 8 tensors: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b")
+    sac_target(ActorParams(*actor[:6], None, actor[6], actor[7], _lib.ACTOR_TANH_SAMPLE) if actor else None, _qcritic_params(critic, action_dim),
+               {"obs_next": obs_next, "rwd": reward, "done": done}, 0, index, discount=discount, alpha=alpha if alpha_dev is None else alpha_dev,
+               noise=noise, action_next=action_next, logp_next=logp_next, out=y, action_out=action_out, logp_out=logp_out)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

@@ -667,6 +667,40 @@ typedef struct QrSoftUpdate {
  * Nothing is launched on an error. */
 int qr_soft_update(const QrSoftUpdate* update, void* stream);
 
+/* SAC's soft target values of a minibatch in ONE launch (SAC.train, algos/sac/sac.py:135-153, the non-CTDE branch, with
+ * MLP_Actor_SAC.sample, algos/sac/sac_mlp.py:55-79), j the minibatch position and i = index[j]:
+ *     mean, ls = pi(obs_next[i]);   ls = clamp(ls, -20, 2)                     pi: the LIVE actor (SAC has no target actor)
+ *     u = mean + exp(ls) * eps[j];  a'_j = tanh(u)
+ *     logp_j = sum_f [ -eps[j][f]^2 / 2 - ls_f - log sqrt(2 pi) - log(1 - a'_f^2 + 1e-6) ]
+ *     y[j] = reward[i] + discount * (1 - done[i]) * ( min(Q1_targ, Q2_targ)(obs_next[i], a'_j) - alpha * logp_j )
+ * 1 - a'^2 is formed as 4 t / (1 + t)^2 and a' as copysign((1 - t) / (1 + t), u) with t = exp(-2 |u|), not from the rounded a': the
+ * same function without the cancellation, good to a relative 1e-6 at every |u|.  -eps^2 / 2 is formed from eps directly, not as
+ * -(u - mean)^2 / (2 var).
+ * actor: a QrActor of the QR_ACTOR_TANH_SAMPLE form with the log_std head (MLP_Actor_SAC: fc1, fc2, mean_linear, log_std_linear) in one
+ * of qr_twinq_target's three sizes, its obs_dim and action_dim equal to the critic's; its log_std member is not read.  eps:
+ * [batch][action_dim] float32 standard-normal draws (rsample's), row j for minibatch position j (not for index[j]); NULL: zeros, the
+ * same bits as zeros.  alpha: the entropy temperature; alpha_dev, where not NULL, is a device float that is read in the kernel and
+ * wins (the reference's sac_alpha is a device tensor under automatic entropy tuning: the host never synchronises for it).
+ * actor NULL: a'_j = action_next[j] ([batch][action_dim]) and logp_j = logp_next[j] ([batch]) are used as they are — another policy
+ * form, or a critic wider than any actor this library holds; eps is not read.  action_out [batch][action_dim] and logp_out [batch]:
+ * optional, a'_j and logp_j as used; giving them or not changes no bit of y.  A row with done = 1 gets y = reward exactly (for finite
+ * Q and logp).  Only the rows the index names are read.  y: [batch] float32.  Plain stores, no atomics: equal inputs give equal bits.
+ * The grid is qr_twinq_target's. */
+typedef struct QrSacTarget {
+  const float* eps;
+  const float* action_next;  const float* logp_next;
+  const float* alpha_dev;
+  float* y;
+  float* action_out;         float* logp_out;
+  float discount, alpha;
+} QrSacTarget;
+/* QR_E_NULL for a NULL critic, batch or target struct, weight, obs_next, reward, done or y pointer, or an actor of NULL with
+ * action_next or logp_next NULL; QR_E_KIND for an actor with squash != QR_ACTOR_TANH_SAMPLE or without the log_std head; QR_E_SIZE for
+ * widths outside QrQCritic's ranges, reserved0 != 0, an actor size other than (23,16,4), (15,16,4), (3,4,1), an actor whose obs_dim or
+ * action_dim differs from the critic's, batch < 1, rows < 1, a stride < 1 or a negative or non-finite discount or alpha; QR_E_ALIGN
+ * for a float pointer that is not 4-byte aligned or an index pointer that is not 8-byte aligned.  Nothing is launched on an error. */
+int qr_sac_target(const QrActor* actor, const QrQCritic* critic_target, const QrTransitions* batch, const QrSacTarget* target, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -1,7 +1,8 @@
-// qr_td3.h — part of the gfx950 quadrotor step library (included by quadrotor_kernels.hip, after qr_optim.h).
+// qr_td3.h — part of the gfx950 quadrotor step library (included by quadrotor_kernels.hip after qr_optim.h, and by qr_td3_actor.h and qr_sac.h).
 // The critic half of one TD3 minibatch update (TD3.train, algos/td3/td3.py:123-167, the non-CTDE branch) for the reference's twin
 // critic MLP_Critic (algos/td3/td3_mlp.py:36-99; Q = fc3(relu(fc2(relu(fc1(sa))))), twice):
-//   td3_target_kernel  (qr_twinq_target)   y = reward + discount (1 - done) min(Q1_targ, Q2_targ)(obs_next, a'), forward only
+//   td3_target_kernel  (qr_twinq_target)   y = reward + discount (1 - done) min(Q1_targ, Q2_targ)(obs_next, a'), forward only:
+//                                           target_walk with Td3Rule; the walk is sac_target_kernel's too (qr_sac.h)
 //   twinq_kernel + twinq_reduce_kernel (qr_twinq_grad)   mse(Q1, y) + mse(Q2, y) and its gradients for the twelve tensors
 // The half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's, shared with ppo_critic_kernel; here: ReLU,
 // 28 inputs with fc1_w's operands in LDS, rows from obs + action, y by minibatch position, two statistics, two networks.
@@ -209,12 +210,18 @@ __device__ __forceinline__ float twinq_forward(const float (&a2)[4][4][4], const
   return sv[kMgB3] + (__uint_as_float(t[0]) + __uint_as_float(t[1]));
 }
 
-// AD = the target actor's obs_dim: 23 or 15 (ActorMfma, hidden 16, 4 actions), 3 (ActorLds<3, 4, 1>), or 0: no actor, a' is
-// supplied.  One wavefront per workgroup walks 64-row tiles grid-stride: gather obs_next rows (index, clamped) into the critic's
-// input tile and the actor's tile, the actor's mean for the lane's own row, the smoothing noise and both clamps, a' into the
-// columns behind the observation, then both target networks over the tile, min, and the Bellman line.  Lane l owns row l.
-template <int AD>
-__global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) {
+// What td3_target_kernel and sac_target_kernel (qr_sac.h) share: the tile walk.  AD = the actor's obs_dim: 23 or 15 (ActorMfma,
+// hidden 16, 4 actions), 3 (ActorLds<3, 4, 1>), or 0: no actor, a' is supplied.  One wavefront per workgroup walks 64-row tiles
+// grid-stride: gather obs_next rows (index, clamped) into the critic's input tile and the actor's tile, the actor's heads for the
+// lane's own row, a' into the columns behind the observation, then both target networks over the tile and min.  Lane l owns row l.
+// A Rule supplies what is the algorithm's own: Args (the fields read here carry the same names in both), LOG_STD (has the actor a
+// log_std head), and for minibatch position j, with `sum` what the rule adds up over a row (zero at the row's start):
+//   component(pre, ls, k, active, sum)  a' of one component from the heads' outputs; k = j * action_dim + f
+//   keep(k, act, active)                a' of one component is settled, computed or supplied
+//   supplied(j, active)                 `sum` of a row whose a' is supplied
+//   bellman(j, rwd, dn, qmin, sum)      y[j], for active rows only
+template <int AD, class Rule>
+__device__ __forceinline__ void target_walk(const typename Rule::Args& a) {
   constexpr int AA = AD == 3 ? 1 : 4;  // the actor's action_dim
   using Actor1 = ActorLds<3, 4, 1>;
   __shared__ float xs[64 * kMgX];
@@ -229,9 +236,10 @@ __global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) {
   load_fc2(q2, a.net[1].fc2_w, H, lane);
   twinq_fill_small(w1s[0], svec[0], a.net[0], D, H, lane);
   twinq_fill_small(w1s[1], svec[1], a.net[1], D, H, lane);
-  ActorMfma<(AD == 23 || AD == 15) ? AD : 23, false> actor;
+  ActorMfma<(AD == 23 || AD == 15) ? AD : 23, Rule::LOG_STD> actor;
   if constexpr (AD == 23 || AD == 15) actor.load(a.actor, lane);
   if constexpr (AD == 3) Actor1::fill(wsm, a.actor, lane);
+  const Rule rule(a);
   for (int i = lane; i < 64 * kMgX; i += 64) xs[i] = 0.0f;  // the padding columns stay zero: nothing below writes them
   __syncthreads();
 
@@ -248,31 +256,58 @@ __global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) {
     stage_rows(xs, kMgX, src0, a.obs_dim, 0, lane);
     if constexpr (AD > 0) stage_rows(as, AD, src0, AD, 0, lane);
     __syncthreads();
+    float sum = 0.0f;
     if constexpr (AD > 0) {
       float pre[AA], ls[AA];
       if constexpr (AD == 3) {
         float x[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[k] = as[lane * 3 + k];
-        Actor1::heads(wsm, false, x, pre, ls);
+        Actor1::heads(wsm, Rule::LOG_STD, x, pre, ls);
       } else {
         actor.heads(as, lane, pre, ls);
       }
 #pragma unroll
       for (int f = 0; f < AA; ++f) {
-        float n = 0.0f;
-        if (a.eps && active) n = fminf(fmaxf(a.target_noise * a.eps[j * AA + f], -a.noise_clip), a.noise_clip);
-        xs[lane * kMgX + AD + f] = fminf(fmaxf(tanh_fast(pre[f]) + n, -a.max_action), a.max_action);
+        const float act = rule.component(pre[f], ls[f], j * AA + f, active, sum);
+        xs[lane * kMgX + AD + f] = act;
+        rule.keep(j * AA + f, act, active);
       }
     } else {
-      for (int f = 0; f < a.action_dim; ++f) xs[lane * kMgX + a.obs_dim + f] = active ? a.action_next[j * a.action_dim + f] : 0.0f;
+      for (int f = 0; f < a.action_dim; ++f) {
+        const float act = active ? a.action_next[j * a.action_dim + f] : 0.0f;
+        xs[lane * kMgX + a.obs_dim + f] = act;
+        rule.keep(j * a.action_dim + f, act, active);
+      }
+      sum = rule.supplied(j, active);
     }
     __syncthreads();
     const float v1 = twinq_forward(q1, xs, lds_here(w1s[0]), lds_here(svec[0]), lane);
     const float v2 = twinq_forward(q2, xs, lds_here(w1s[1]), lds_here(svec[1]), lane);
     __syncthreads();  // the tile is read: the next one may be staged
-    if (active) a.y[j] = fmaf(a.discount * (1.0f - dn), fminf(v1, v2), rwd);
+    if (active) rule.bellman(j, rwd, dn, fminf(v1, v2), sum);
   }
 }
+
+// TD3's rule: the target actor's mean, the smoothing noise and both clamps; the Bellman line on min.
+struct Td3Rule {
+  using Args = Td3TargetArgs;
+  static constexpr bool LOG_STD = false;
+  const Args& a;
+  __device__ __forceinline__ explicit Td3Rule(const Args& args) : a(args) {}
+  __device__ __forceinline__ float component(float pre, float, int64_t k, bool active, float&) const {
+    float n = 0.0f;
+    if (a.eps && active) n = fminf(fmaxf(a.target_noise * a.eps[k], -a.noise_clip), a.noise_clip);
+    return fminf(fmaxf(tanh_fast(pre) + n, -a.max_action), a.max_action);
+  }
+  __device__ __forceinline__ void keep(int64_t, float, bool) const {}
+  __device__ __forceinline__ float supplied(int64_t, bool) const { return 0.0f; }
+  __device__ __forceinline__ void bellman(int64_t j, float rwd, float dn, float qmin, float) const {
+    a.y[j] = fmaf(a.discount * (1.0f - dn), qmin, rwd);
+  }
+};
+
+template <int AD>
+__global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) { target_walk<AD, Td3Rule>(a); }
 
 }  // namespace qr

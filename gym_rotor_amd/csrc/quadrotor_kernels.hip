@@ -47,14 +47,15 @@
 //   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): the half-tile gradient body, the partial vector, the reduction's sums
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
-//   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel
+//   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
-//   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_target_kernel
+//   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdio.h>
 #include <string.h>
 #include "quadrotor_hip.h"
@@ -229,80 +230,62 @@ static void twinq_nets(MlpNetW (&n)[2], const QrQCritic* c) {
   n[1] = MlpNetW{c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b};
 }
 
-static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrTd3Target* t, void* stream) {
-  if (!c || !b || !t) return QR_E_NULL;
-  if (p && (p->squash != QR_ACTOR_TANH_MEAN || p->log_std_w || p->log_std_b)) return QR_E_KIND;
+// What qr_twinq_target and qr_sac_target check, fill and launch alike; c, b and the caller's own struct are not NULL.  The caller has
+// filled its own fields of `a` and says: the actor form it takes (squash, log_std: with the log_std head), whether its scalars are
+// in range, whether what the no-actor form reads is there, its own float pointers, and its kernels for AD = 23, 15, 3, 0.
+template <class Args>
+static int target_launch(const QrActor* p, const QrQCritic* c, const QrTransitions* b, Args& a, int32_t squash, bool log_std, bool scalars_ok,
+                         bool supplied_ok, std::initializer_list<const void*> own, void (*const kernel[4])(Args), void* stream) {
+  if (p && (p->squash != squash || (log_std ? !p->log_std_w || !p->log_std_b : p->log_std_w || p->log_std_b))) return QR_E_KIND;
   if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
   if (p && (!ppo_np(p->obs_dim, p->hidden_dim, p->action_dim) || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
   if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
-  if (!(t->noise_clip >= 0.0f) || !(t->max_action >= 0.0f) || !(t->noise_clip <= 3.0e38f) || !(t->max_action <= 3.0e38f)) return QR_E_SIZE;
+  if (!scalars_ok) return QR_E_SIZE;
   if (int rc = twinq_critic_check(c)) return rc;
   if (p && (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b)) return QR_E_NULL;
-  if (!b->obs_next || !b->reward || !b->done || !t->y || (!p && !t->action_next)) return QR_E_NULL;
+  if (!b->obs_next || !b->reward || !b->done || !a.y || (!p && !supplied_ok)) return QR_E_NULL;
   const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
-                                c->fc6_b, b->obs_next, b->reward, b->done, t->eps, t->action_next, t->y, p ? p->fc1_w : nullptr,
-                                p ? p->fc1_b : nullptr, p ? p->fc2_w : nullptr, p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr,
-                                p ? p->mean_b : nullptr};
+                                c->fc6_b, b->obs_next, b->reward, b->done, p ? p->fc1_w : nullptr, p ? p->fc1_b : nullptr,
+                                p ? p->fc2_w : nullptr, p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr, p ? p->mean_b : nullptr,
+                                p ? p->log_std_w : nullptr, p ? p->log_std_b : nullptr};
   for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (const void* q : own)
     if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
   if (reinterpret_cast<uintptr_t>(b->index) & 7u) return QR_E_ALIGN;
 
-  Td3TargetArgs a{};
-  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
+  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, p->log_std_w, p->log_std_b, squash};
   twinq_nets(a.net, c);
-  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next;
-  a.index = b->index; a.y = t->y; a.B = b->batch; a.rows = b->rows;
+  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.index = b->index; a.B = b->batch; a.rows = b->rows;
   a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.rwd_stride = b->reward_stride; a.done_stride = b->done_stride;
-  a.discount = t->discount; a.target_noise = t->target_noise; a.noise_clip = t->noise_clip; a.max_action = t->max_action;
-  // grid-stride over the tiles: at most the waves resident at once, one per SIMD at the kernel's register count
+  // grid-stride over the tiles: at most the waves resident at once, one per SIMD at the kernels' register count
   const int64_t tiles = (b->batch + 63) / 64;
   const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int ad = p ? p->obs_dim : 0;
-  if (ad == 23) hipLaunchKernelGGL(td3_target_kernel<23>, grid, dim3(64), 0, s, a);
-  else if (ad == 15) hipLaunchKernelGGL(td3_target_kernel<15>, grid, dim3(64), 0, s, a);
-  else if (ad == 3) hipLaunchKernelGGL(td3_target_kernel<3>, grid, dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(td3_target_kernel<0>, grid, dim3(64), 0, s, a);
+  hipLaunchKernelGGL(kernel[ad == 23 ? 0 : ad == 15 ? 1 : ad == 3 ? 2 : 3], grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
+}
+
+static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrTd3Target* t, void* stream) {
+  if (!c || !b || !t) return QR_E_NULL;
+  Td3TargetArgs a{};
+  a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next; a.y = t->y;
+  a.discount = t->discount; a.target_noise = t->target_noise; a.noise_clip = t->noise_clip; a.max_action = t->max_action;
+  const bool scalars_ok = t->noise_clip >= 0.0f && t->max_action >= 0.0f && t->noise_clip <= 3.0e38f && t->max_action <= 3.0e38f;
+  static void (*const kernel[4])(Td3TargetArgs) = {td3_target_kernel<23>, td3_target_kernel<15>, td3_target_kernel<3>, td3_target_kernel<0>};
+  return target_launch(p, c, b, a, QR_ACTOR_TANH_MEAN, false, scalars_ok, t->action_next != nullptr, {t->eps, t->action_next, t->y}, kernel, stream);
 }
 
 static int do_sac_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrSacTarget* t, void* stream) {
   if (!c || !b || !t) return QR_E_NULL;
-  if (p && (p->squash != QR_ACTOR_TANH_SAMPLE || !p->log_std_w || !p->log_std_b)) return QR_E_KIND;
-  if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
-  if (p && (!ppo_np(p->obs_dim, p->hidden_dim, p->action_dim) || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
-  if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
-  if (!(t->discount >= 0.0f) || !(t->alpha >= 0.0f) || !(t->discount <= 3.0e38f) || !(t->alpha <= 3.0e38f)) return QR_E_SIZE;
-  if (int rc = twinq_critic_check(c)) return rc;
-  if (p && (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b)) return QR_E_NULL;
-  if (!b->obs_next || !b->reward || !b->done || !t->y || (!p && (!t->action_next || !t->logp_next))) return QR_E_NULL;
-  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
-                                c->fc6_b, b->obs_next, b->reward, b->done, t->eps, t->action_next, t->logp_next, t->alpha_dev, t->y,
-                                t->action_out, t->logp_out, p ? p->fc1_w : nullptr, p ? p->fc1_b : nullptr, p ? p->fc2_w : nullptr,
-                                p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr, p ? p->mean_b : nullptr, p ? p->log_std_w : nullptr,
-                                p ? p->log_std_b : nullptr};
-  for (const void* q : floats)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  if (reinterpret_cast<uintptr_t>(b->index) & 7u) return QR_E_ALIGN;
-
   SacTargetArgs a{};
-  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, p->log_std_w, p->log_std_b, QR_ACTOR_TANH_SAMPLE};
-  twinq_nets(a.net, c);
-  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.eps = p ? t->eps : nullptr;
-  a.action_next = p ? nullptr : t->action_next; a.logp_next = p ? nullptr : t->logp_next; a.alpha_dev = t->alpha_dev;
-  a.index = b->index; a.y = t->y; a.action_out = t->action_out; a.logp_out = t->logp_out; a.B = b->batch; a.rows = b->rows;
-  a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.rwd_stride = b->reward_stride; a.done_stride = b->done_stride;
+  a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next; a.logp_next = p ? nullptr : t->logp_next;
+  a.alpha_dev = t->alpha_dev; a.y = t->y; a.action_out = t->action_out; a.logp_out = t->logp_out;
   a.discount = t->discount; a.alpha = t->alpha;
-  // qr_twinq_target's grid: grid-stride over the tiles, at most the waves resident at once, one per SIMD at the kernel's register count
-  const int64_t tiles = (b->batch + 63) / 64;
-  const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int ad = p ? p->obs_dim : 0;
-  if (ad == 23) hipLaunchKernelGGL(sac_target_kernel<23>, grid, dim3(64), 0, s, a);
-  else if (ad == 15) hipLaunchKernelGGL(sac_target_kernel<15>, grid, dim3(64), 0, s, a);
-  else if (ad == 3) hipLaunchKernelGGL(sac_target_kernel<3>, grid, dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(sac_target_kernel<0>, grid, dim3(64), 0, s, a);
-  return (int)hipGetLastError();
+  const bool scalars_ok = t->discount >= 0.0f && t->alpha >= 0.0f && t->discount <= 3.0e38f && t->alpha <= 3.0e38f;
+  static void (*const kernel[4])(SacTargetArgs) = {sac_target_kernel<23>, sac_target_kernel<15>, sac_target_kernel<3>, sac_target_kernel<0>};
+  return target_launch(p, c, b, a, QR_ACTOR_TANH_SAMPLE, true, scalars_ok, t->action_next && t->logp_next,
+                       {t->eps, t->action_next, t->logp_next, t->alpha_dev, t->y, t->action_out, t->logp_out}, kernel, stream);
 }
 
 static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGrad* g, void* stream) {

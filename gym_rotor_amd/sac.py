@@ -9,14 +9,13 @@ own update and the optimiser group of twelve tensors are not here (twelve tensor
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Union
 
 import torch
 
 from . import _lib
-from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams
-from .td3 import ReplayBuffer, _agent_tensors, _check_index, _column, _rows, twinq_grad, twinq_workspace_bytes
+from .policy import ActorParams, QCriticParams
+from .td3 import ReplayBuffer, _critic_update_state, _target, twinq_grad
 
 
 def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
@@ -35,64 +34,30 @@ def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffe
     on the device that the kernel reads (no host synchronisation).  index: int64 [B], None: all rows in order.  action_out [B, A],
     logp_out [B]: optional outputs a' and logp.  Returns y float32 [B] (`out` given: written in place)."""
     what = "sac_target"
-    t = _agent_tensors(buffer_or_tensors, k)
-    dev = critic_target.device
-    D, A, H = critic_target.dims
-    rows = _rows(t.get("obs_next"), D, dev, what, "obs_next")
-    rs, ds = _column(t.get("rwd"), rows, dev, what, "rwd"), _column(t.get("done"), rows, dev, what, "done")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
-    if actor is not None:
-        if actor.dims not in PPO_ACTOR_DIMS:
-            raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
-        if actor.squash != _lib.ACTOR_TANH_SAMPLE or actor.log_std_w is None or actor.log_std_b is None:
-            raise ValueError(f"{what}: the actor must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
-        if (actor.dims[0], actor.dims[2]) != (D, A):
-            raise ValueError(f"{what}: the actor maps {actor.dims[0]} -> {actor.dims[2]}, the critic reads {D} + {A}")
-        Da, Ha, Aa = actor.dims
-        ashapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,),
-                   "log_std_w": (Aa, Ha), "log_std_b": (Aa,)}
-        for n, shp in ashapes.items():   # (log_std is not read: whatever it holds is not checked)
-            w = getattr(actor, n)
-            if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
-                raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
-    elif action_next is None or logp_next is None:
-        raise ValueError(f"{what}: without an actor, action_next [B, {A}] and logp_next [B] are required")
-    for name, x in (("noise", noise), ("action_next", action_next), ("action_out", action_out)):
+
+    def own(B, A, dev):   # what follows _target's check of noise and action_next; the keywords of sac_target_args that are SAC's
+        x = action_out
         if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
-    for name, x in (("logp_next", logp_next), ("logp_out", logp_out)):
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or x.numel() != B or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}] tensor on {dev}")
-    alpha_dev = None
-    if isinstance(alpha, torch.Tensor):
-        if alpha.dtype != torch.float32 or alpha.device != dev or alpha.numel() != 1:
-            raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
-        alpha_dev, alpha = alpha, 0.0
-    elif not 0.0 <= float(alpha) < float("inf"):
-        raise ValueError(f"{what}: alpha must be finite and >= 0, got {alpha}")
-    if not 0.0 <= float(discount) < float("inf"):
-        raise ValueError(f"{what}: discount must be finite and >= 0, got {discount}")
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:
-        return out
-    b = _lib.transitions(obs_next=t["obs_next"], reward=t["rwd"], done=t["done"], index=index, batch=B, rows=rows, reward_stride=rs, done_stride=ds)
-    g = _lib.sac_target_args(eps=noise, action_next=action_next, logp_next=logp_next, alpha_dev=alpha_dev, y=out, action_out=action_out,
-                             logp_out=logp_out, discount=discount, alpha=alpha)
-    q = critic_target.as_c()
-    if actor is not None:
-        p = actor.as_c()
-        p.log_std = None
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_sac_target(C.byref(p) if actor is not None else None, C.byref(q), C.byref(b), C.byref(g),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_sac_target")
-    return out
+            raise ValueError(f"{what}: action_out must be a contiguous float32 [{B}, {A}] tensor on {dev}")
+        for name, x in (("logp_next", logp_next), ("logp_out", logp_out)):
+            if x is not None and (x.dtype != torch.float32 or x.device != dev or x.numel() != B or not x.is_contiguous()):
+                raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}] tensor on {dev}")
+        a, alpha_dev = alpha, None
+        if isinstance(a, torch.Tensor):
+            if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
+                raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
+            alpha_dev, a = a, 0.0
+        elif not 0.0 <= float(a) < float("inf"):
+            raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
+        if not 0.0 <= float(discount) < float("inf"):
+            raise ValueError(f"{what}: discount must be finite and >= 0, got {discount}")
+        return dict(logp_next=logp_next, alpha_dev=alpha_dev, action_out=action_out, logp_out=logp_out, discount=discount, alpha=a)
+
+    A = critic_target.dims[1]
+    return _target(what, "qr_sac_target", _lib.sac_target_args, actor,
+                   (_lib.ACTOR_TANH_SAMPLE, True, "the actor must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head"),
+                   f"without an actor, action_next [B, {A}] and logp_next [B] are required" if action_next is None or logp_next is None else None,
+                   critic_target, buffer_or_tensors, k, index, noise, action_next, out, own)
 
 
 def sac_critic_loss(critic_module, critic_target_module, actor_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
@@ -109,22 +74,7 @@ def sac_critic_loss(critic_module, critic_target_module, actor_module, buffer: R
     if not isinstance(buffer, ReplayBuffer):
         raise ValueError("sac_critic_loss: buffer must be a ReplayBuffer")
     A = buffer.action_dims[k]
-    layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
-    grads = {}
-    for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
-    critic = QCriticParams.from_module(critic_module, A)
-    B = buffer.capacity if index is None else index.numel()
-    key = ("sac", k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = twinq_workspace_bytes(critic.dims, B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
-                                    torch.empty(4, dtype=torch.float32, device=dev))
-    y, workspace, own_stats = hit
+    grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups, ("sac",))
     sac_target(ActorParams.from_sac_module(actor_module), QCriticParams.from_module(critic_target_module, A), buffer, k, index,
                discount=discount, alpha=alpha, noise=noise, out=y)
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,

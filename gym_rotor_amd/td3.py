@@ -110,6 +110,67 @@ def _column(t, rows: int, dev, what: str, name: str) -> int:
     return dims[0][1] if dims else 1
 
 
+def _check_actor(actor: ActorParams, D: int, A: int, dev, what: str, squash: int, log_std_head: bool, form: str) -> dict:
+    """An actor beside a twin critic that reads D + A: one of the rollout's sizes, of the form the launch takes (`form`: the message
+    otherwise), its tensors of their shapes on `dev`.  Returns {name: shape} of the tensors the launch reads."""
+    if actor.dims not in PPO_ACTOR_DIMS:
+        raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
+    if actor.squash != squash or ((actor.log_std_w is None or actor.log_std_b is None) if log_std_head else actor.log_std_w is not None):
+        raise ValueError(f"{what}: {form}")
+    if (actor.dims[0], actor.dims[2]) != (D, A):
+        raise ValueError(f"{what}: the actor maps {actor.dims[0]} -> {actor.dims[2]}, the critic reads {D} + {A}")
+    Da, Ha, Aa = actor.dims
+    shapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
+    if log_std_head:
+        shapes.update(log_std_w=(Aa, Ha), log_std_b=(Aa,))
+    for n, shp in shapes.items():   # (log_std is not read: whatever it holds is not checked)
+        w = getattr(actor, n)
+        if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
+            raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
+    return shapes
+
+
+def _target(what: str, entry: str, make_args, actor: Optional[ActorParams], form: tuple, missing: Optional[str], critic_target: QCriticParams,
+            buffer_or_tensors, k: int, index, noise, action_next, out, own) -> torch.Tensor:
+    """What `td3_target` and `sac.sac_target` do alike: the transitions, the actor (`form`: _check_actor's last three arguments) or,
+    without one, `missing` (the message when a supplied tensor is), noise, action_next, the caller's `own(B, A, dev)` checks —
+    which return its own keywords of `make_args` — out, and the launch of `entry`."""
+    t = _agent_tensors(buffer_or_tensors, k)
+    dev = critic_target.device
+    D, A, H = critic_target.dims
+    rows = _rows(t.get("obs_next"), D, dev, what, "obs_next")
+    rs, ds = _column(t.get("rwd"), rows, dev, what, "rwd"), _column(t.get("done"), rows, dev, what, "done")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    if actor is not None:
+        _check_actor(actor, D, A, dev, what, *form)
+    elif missing is not None:
+        raise ValueError(f"{what}: {missing}")
+    for name, x in (("noise", noise), ("action_next", action_next)):
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
+    kw = own(B, A, dev)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:
+        return out
+    b = _lib.transitions(obs_next=t["obs_next"], reward=t["rwd"], done=t["done"], index=index, batch=B, rows=rows, reward_stride=rs, done_stride=ds)
+    g = make_args(eps=noise, action_next=action_next, y=out, **kw)
+    q = critic_target.as_c()
+    if actor is not None:
+        p = actor.as_c()
+        p.log_std = None
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), entry)(C.byref(p) if actor is not None else None, C.byref(q), C.byref(b), C.byref(g),
+                                         torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, entry)
+    return out
+
+
 def td3_target(actor_target: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
                index: Optional[torch.Tensor] = None, *, discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5,
                max_action: float = 1.0, noise: Optional[torch.Tensor] = None, action_next: Optional[torch.Tensor] = None,
@@ -122,52 +183,12 @@ def td3_target(actor_target: Optional[ActorParams], critic_target: QCriticParams
     `ReplayBuffer` (agent k's tensors) or a dict with obs_next [rows, D], rwd, done (float32, `rows` elements, one stride).
     noise: float32 [B, A] standard-normal draws by minibatch position, None: no smoothing noise.  index: int64 [B], None: all rows
     in order.  Returns y float32 [B] (`out` given: written in place)."""
-    what = "td3_target"
-    t = _agent_tensors(buffer_or_tensors, k)
-    dev = critic_target.device
-    D, A, H = critic_target.dims
-    rows = _rows(t.get("obs_next"), D, dev, what, "obs_next")
-    rs, ds = _column(t.get("rwd"), rows, dev, what, "rwd"), _column(t.get("done"), rows, dev, what, "done")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
-    if actor_target is not None:
-        if actor_target.dims not in PPO_ACTOR_DIMS:
-            raise ValueError(f"{what}: actor sizes {actor_target.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
-        if actor_target.squash != _lib.ACTOR_TANH_MEAN or actor_target.log_std_w is not None:
-            raise ValueError(f"{what}: the target actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
-        if (actor_target.dims[0], actor_target.dims[2]) != (D, A):
-            raise ValueError(f"{what}: the actor maps {actor_target.dims[0]} -> {actor_target.dims[2]}, the critic reads {D} + {A}")
-        Da, Ha, Aa = actor_target.dims
-        ashapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
-        for n, shp in ashapes.items():   # (log_std is not read: whatever it holds is not checked)
-            w = getattr(actor_target, n)
-            if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
-                raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
-    elif action_next is None:
-        raise ValueError(f"{what}: without a target actor, action_next [B, {A}] is required")
-    for name, x in (("noise", noise), ("action_next", action_next)):
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:
-        return out
-    b = _lib.transitions(obs_next=t["obs_next"], reward=t["rwd"], done=t["done"], index=index, batch=B, rows=rows, reward_stride=rs, done_stride=ds)
-    g = _lib.td3_target_args(eps=noise, action_next=action_next, y=out, discount=discount, target_noise=target_noise, noise_clip=noise_clip,
-                             max_action=max_action)
-    q = critic_target.as_c()
-    if actor_target is not None:
-        p = actor_target.as_c()
-        p.log_std = None
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_twinq_target(C.byref(p) if actor_target is not None else None, C.byref(q), C.byref(b), C.byref(g),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_twinq_target")
-    return out
+    A = critic_target.dims[1]
+    return _target("td3_target", "qr_twinq_target", _lib.td3_target_args, actor_target,
+                   (_lib.ACTOR_TANH_MEAN, False, "the target actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head"),
+                   f"without a target actor, action_next [B, {A}] is required" if action_next is None else None, critic_target, buffer_or_tensors,
+                   k, index, noise, action_next, out,
+                   lambda B, A, dev: dict(discount=discount, target_noise=target_noise, noise_clip=noise_clip, max_action=max_action))
 
 
 def twinq_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
@@ -230,6 +251,27 @@ def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y
     return grads, stats
 
 
+def _critic_update_state(critic_module, buffer: ReplayBuffer, k: int, index, max_workgroups: int, tag: tuple = ()):
+    """For `td3_critic_loss` and `sac.sac_critic_loss`: the live twin critic's twelve .grad tensors by name (made where there is none),
+    its `QCriticParams`, and (y, workspace, stats) from the buffer's cache under tag + (k, B, max_workgroups)."""
+    layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
+    grads = {}
+    for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
+    B = buffer.capacity if index is None else index.numel()
+    key = tag + (k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = twinq_workspace_bytes(critic.dims, B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
+                                    torch.empty(4, dtype=torch.float32, device=dev))
+    return grads, critic, hit
+
+
 def td3_critic_loss(critic_module, critic_target_module, actor_target_module, buffer: ReplayBuffer, k: int = 0,
                     index: Optional[torch.Tensor] = None, *, discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5,
                     max_action: float = 1.0, noise: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
@@ -242,22 +284,7 @@ def td3_critic_loss(critic_module, critic_target_module, actor_target_module, bu
     B nothing is allocated: y, the workspace and stats are cached on the buffer.  The optimiser step follows on these .grad tensors:
     two `optim.DeviceAdamW` groups of six tensors, or torch's."""
     A = buffer.action_dims[k]
-    layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
-    grads = {}
-    for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
-    critic = QCriticParams.from_module(critic_module, A)
-    B = buffer.capacity if index is None else index.numel()
-    key = (k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = twinq_workspace_bytes(critic.dims, B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
-                                    torch.empty(4, dtype=torch.float32, device=dev))
-    y, workspace, own_stats = hit
+    grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups)
     m = actor_target_module
     actor = ActorParams(m.fc1.weight.data, m.fc1.bias.data, m.fc2.weight.data, m.fc2.bias.data, m.fc3.weight.data, m.fc3.bias.data, None)
     td3_target(actor, QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
@@ -297,18 +324,7 @@ def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
     what = "dpg_actor_grad"
     dev = critic.device
     D, A, H = critic.dims
-    if actor.dims not in PPO_ACTOR_DIMS:
-        raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
-    if actor.squash != _lib.ACTOR_TANH_MEAN or actor.log_std_w is not None:
-        raise ValueError(f"{what}: the actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
-    if (actor.dims[0], actor.dims[2]) != (D, A):
-        raise ValueError(f"{what}: the actor maps {actor.dims[0]} -> {actor.dims[2]}, the critic reads {D} + {A}")
-    Da, Ha, Aa = actor.dims
-    shapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
-    for n, shp in shapes.items():   # (log_std is not read: whatever it holds is not checked)
-        w = getattr(actor, n)
-        if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
-            raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
+    shapes = _check_actor(actor, D, A, dev, what, _lib.ACTOR_TANH_MEAN, False, "the actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
     for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
         if not 0.0 <= float(v) < float("inf"):
             raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")

@@ -15,7 +15,8 @@ import sac_ref  # noqa: E402
 import td3_ref  # noqa: E402
 from sac_ref import ACTOR_NAMES  # noqa: E402
 from td3_ref import NAMES  # noqa: E402
-from test_sac_critic_host import CASES, LIVE, _SacActor, _Twin  # noqa: E402
+from test_sac_critic_host import CASES, LIVE, _SacActor  # noqa: E402
+from twinq_gpu_util import _cuda, _idx, _np, _q, _twin_module, bar, torch_twinq  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -7.25
@@ -26,15 +27,6 @@ STATS = ("loss", "mse1", "mse2", "mean_y")
 def cases():
     g = sac_ref.load()
     return {n: sac_ref.case(g, n) for n in CASES}
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _cuda(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
 
 
 def _critic(c, prefix="t_"):
@@ -53,10 +45,6 @@ def _actor(c):
 
 def _tensors(c):
     return {"obs": _cuda(c["obs"]), "act": _cuda(c["action"]), "rwd": _cuda(c["reward"]), "obs_next": _cuda(c["obs_next"]), "done": _cuda(c["done"])}
-
-
-def _idx(index):
-    return None if index is None else _cuda(np.asarray(index, dtype=np.int64))
 
 
 def run_target(c, index=None, eps="own", outputs=True, tensors=None, **over):
@@ -82,20 +70,6 @@ def run_target(c, index=None, eps="own", outputs=True, tensors=None, **over):
 # ------------------------------------------------------------------------------------------------------------------------
 # eager torch on the device, in a given dtype: what e32 is measured with (sac_mlp.py:65-76 with rsample's draw supplied, sac.py:146-153)
 # ------------------------------------------------------------------------------------------------------------------------
-def _twin_module(c, prefix, dtype):
-    D, A, H = c["obs"].shape[1], c["action"].shape[1], c[prefix + "fc1_w"].shape[0]
-    m = _Twin(D + A, H)
-    with torch.no_grad():
-        for n in NAMES:
-            getattr(getattr(m, n[:3]), "weight" if n.endswith("w") else "bias").copy_(torch.from_numpy(c[prefix + n]))
-    return m.to(dtype).cuda()
-
-
-def _q(m, sa, k):
-    f = [getattr(m, f"fc{j}") for j in range(3 * k + 1, 3 * k + 4)]
-    return f[2](torch.relu(f[1](torch.relu(f[0](sa)))))
-
-
 def torch_target(c, dtype, index=None, eps=None):
     """(a', logp, y) as float64 NumPy arrays, computed by eager torch in `dtype` on the device."""
     idx = np.arange(130) if index is None else np.asarray(index)
@@ -120,22 +94,6 @@ def torch_target(c, dtype, index=None, eps=None):
         q = torch.min(_q(m, sa, 0), _q(m, sa, 1)) - float(c["alpha"]) * logp
         y = r[:, None] + float(c["discount"]) * (1 - d[:, None]) * q
     return tuple(_np(t).astype(np.float64) for t in (a, logp[:, 0], y[:, 0]))
-
-
-def torch_twinq(c, dtype, y, index=None):
-    idx = np.arange(130) if index is None else np.asarray(index)
-    m = _twin_module(c, "c_", dtype)
-    sa = torch.cat([_cuda(c["obs"][idx], dtype), _cuda(c["action"][idx], dtype)], 1)
-    yt = _cuda(np.asarray(y), dtype)[:, None]
-    m1, m2 = torch.nn.functional.mse_loss(_q(m, sa, 0), yt), torch.nn.functional.mse_loss(_q(m, sa, 1), yt)
-    m.zero_grad()
-    (m1 + m2).backward()
-    grads = {n: _np(getattr(getattr(m, n[:3]), "weight" if n.endswith("w") else "bias").grad).astype(np.float64) for n in NAMES}
-    return grads, np.array([(m1 + m2).item(), m1.item(), m2.item(), yt.mean().item()], dtype=np.float64)
-
-
-def bar(v64, e32):
-    return max(2e-6 * max(1.0, float(np.abs(v64).max())), float(e32))
 
 
 def check(label, what, got, x64, x32):

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import td3_actor_ref as R  # noqa: E402
 from td3_actor_ref import ACTOR_NAMES, CASES, Q1_NAMES  # noqa: E402
 from test_td3_critic_host import _Actor, _Twin  # noqa: E402
+from twinq_gpu_util import _cuda, _idx, _np, bar  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -7.25
@@ -26,19 +27,6 @@ LIB_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mean_w", "mean_b")
 def cases():
     g = R.load()
     return {n: R.case(g, n) for n in CASES}
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _cuda(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def _idx(index):
-    return None if index is None else _cuda(np.asarray(index, dtype=np.int64))
 
 
 def _actor(c):
@@ -84,10 +72,6 @@ def torch_dpg(c, dtype, index=None, lam=None):
     loss.backward()
     grads = {n: _np(t.grad).astype(np.float64) for n, t in zip(ACTOR_NAMES, w)}
     return grads, np.array([loss.item(), q1.mean().item(), (mu.abs() > ma).double().mean().item(), float(reg.detach())], dtype=np.float64)
-
-
-def bar(v64, e32):
-    return max(2e-6 * max(1.0, float(np.abs(v64).max())), float(e32))
 
 
 def check(label, c, grads, stats, index=None, lam=None, g64=None, s64=None):

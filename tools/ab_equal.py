@@ -4,7 +4,8 @@ envs) with in-launch resets in its own subprocess and prints a digest of state, 
 dones, terminal observations, episode and tile counters — then the same for qr_rollout and (wrappers) qr_rollout_actor with a PPO and an SAC actor.
 A third digest covers the update launches: ppo_critic_grad on every case of tests/golden/ppo_critic_grad.npz (gradients, stats), td3_target
 and twinq_grad on every case of tests/golden/td3_critic.npz (y, the twelve gradients, stats), each at the default grid, at
-max_workgroups 1 and 3, and once with a permuted index.
+max_workgroups 1 and 3, and once with a permuted index; sac_target on every case of tests/golden/sac_critic.npz (y, action_out,
+logp_out), in order and with the permuted index.
 A build whose child does not exit 0 within QR_AB_TIMEOUT seconds (default 900) ends the run: nothing more is started on the card.
 
     [QR_AB_KIND=coupled] python tools/ab_equal.py build/ab/A.so build/ab/B.so        (GPU box)
@@ -60,8 +61,8 @@ rollout_digest = h.hexdigest()
 # the update launches on the fixtures of their tests
 import numpy as np
 sys.path.insert(0, os.path.join(%r, "tests"))
-import td3_ref, test_ppo_critic_host as pch, test_td3_critic_host as tch
-from gym_rotor_amd import ActorParams, CriticParams, QCriticParams, ppo_critic_grad, td3_target, twinq_grad
+import sac_ref, td3_ref, test_ppo_critic_host as pch, test_sac_critic_host as sch, test_td3_critic_host as tch
+from gym_rotor_amd import ActorParams, CriticParams, QCriticParams, _lib, ppo_critic_grad, sac_target, td3_target, twinq_grad
 h = hashlib.sha256()
 cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 perm = cuda(np.random.default_rng(0).permutation(130).astype(np.int64))
@@ -89,6 +90,19 @@ for name in tch.CASES:
         y = td3_target(actor_t, critic_t, tens, 0, index, **kw)
         grads, stats = twinq_grad(critic, tens["obs"], tens["act"], y, index, max_workgroups=mw)
         put(y, *[grads[n] for n in td3_ref.NAMES], stats)
+g = sac_ref.load()
+for name in sch.CASES:
+    c = sac_ref.case(g, name)
+    critic_t = QCriticParams(*[cuda(c["t_" + n]) for n in td3_ref.NAMES], int(c["action_dim"]))
+    w = [cuda(c["a_" + n]) for n in sac_ref.ACTOR_NAMES] if "a_fc1_w" in c else None
+    actor = ActorParams(*w[:6], None, w[6], w[7], _lib.ACTOR_TANH_SAMPLE) if w else None
+    tens = {"rwd": cuda(c["reward"]), "obs_next": cuda(c["obs_next"]), "done": cuda(c["done"])}
+    kw = dict(discount=float(c["discount"]), alpha=float(c["alpha"]), noise=None if c.get("eps") is None else cuda(c["eps"]))
+    if actor is None:
+        kw.update(action_next=cuda(c["a_next_in"]), logp_next=cuda(c["logp_next_in"]))
+    for index in (None, perm):
+        a_out, logp_out = torch.zeros(130, int(c["action_dim"]), device="cuda"), torch.zeros(130, device="cuda")
+        put(sac_target(actor, critic_t, tens, 0, index, action_out=a_out, logp_out=logp_out, **kw), a_out, logp_out)
 torch.cuda.synchronize()
 print(step_digest, rollout_digest, h.hexdigest(), int(env._episode.sum()))
 ''' % (ROOT, ROOT, ROOT)

@@ -4,9 +4,12 @@
 //   dpg_actor_kernel + dpg_reduce_kernel (qr_dpg_actor_grad)   -mean Q1(s, pi(s)) with the three smoothness terms, and its gradients
 //                                                               for MLP_Actor_TD3's six tensors
 //   soft_update_kernel (qr_soft_update)                         target = tau param + (1 - tau) target for up to 24 tensors
-// Nothing here is a second copy: the actor's passes are PpoNet's (qr_ppo.h: forward, backward, the MFMA weight gradients, emit),
-// Q1's forward pass and the product W2^T dz2 are qr_mlp_grad.h's pieces with qr_td3.h's TwinQL1, and the reduction is
-// reduce16_entries / block_sum_column.  New: the contraction dQ/da = fc1_w[:, D..D+A)^T dz1, and the glue.
+// The pieces are shared: the actor's passes are PpoNet's (qr_ppo.h: forward, backward, the MFMA weight gradients, emit), Q1's forward
+// pass and the product W2^T dz2 are qr_mlp_grad.h's pieces with qr_td3.h's TwinQL1, the reduction is reduce16_entries /
+// block_sum_column, and the host launcher is ppo_actor_kernel's (actor_grad_launch).  New: the contraction
+// dQ/da = fc1_w[:, D..D+A)^T dz1, and the glue.  The tile walk — prologue, gather, smoothness block, epilogue — IS a second copy of
+// ppo_actor_kernel's: with the loss phase below as a hook of a shared walk this kernel takes 8 more AGPRs, so a fix
+// to either walk has to be made in both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -51,7 +51,8 @@
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
-//   this file      the C-ABI
+//   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad) and
+//                  target_launch (qr_twinq_target and qr_sac_target)
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -107,59 +108,85 @@ static int64_t ppo_grid(int64_t batch, int32_t max_workgroups) {
   return tiles < cap ? tiles : cap;
 }
 
-static int ppo_np(int32_t d, int32_t h, int32_t a) {  // length of a partial vector; 0: not one of the rollout's actor sizes
-  if (d == 23 && h == 16 && a == 4) return PpoLayout<23, 16, 4>::NP;
-  if (d == 15 && h == 16 && a == 4) return PpoLayout<15, 16, 4>::NP;
-  if (d == 3 && h == 4 && a == 1) return PpoLayout<3, 4, 1>::NP;
-  return 0;
+// Which of the rollout's three actor sizes (the index of every table over them); -1: none.
+static int actor_size(int32_t d, int32_t h, int32_t a) {
+  if (d == 23 && h == 16 && a == 4) return 0;
+  if (d == 15 && h == 16 && a == 4) return 1;
+  if (d == 3 && h == 4 && a == 1) return 2;
+  return -1;
+}
+// length of a partial vector per actor size
+constexpr int kPpoNP[3] = {PpoLayout<23, 16, 4>::NP, PpoLayout<15, 16, 4>::NP, PpoLayout<3, 4, 1>::NP};
+constexpr int kDpgNP[3] = {DpgLayout<23, 16, 4>::NP, DpgLayout<15, 16, 4>::NP, DpgLayout<3, 4, 1>::NP};
+
+// What qr_ppo_actor_grad and qr_dpg_actor_grad check, fill and launch alike; p and the caller's own structs are not NULL.  The caller
+// has filled its own fields of `a` and `r` (among them a.index, a.partials = the workspace, a.B and a.lam_*) and says: whether the
+// actor's log_std parameter is read, whether its own sizes and scalars are in range, whether its own pointers are there, its own
+// float pointers, the gradient tensors in PpoLayout's order (7 or 6), the partial vector's length per actor size, its kernels for
+// D = 23, 15, 3, and its reduce kernel with the entries one workgroup of it sums.
+template <class Args, class RArgs>
+static int actor_grad_launch(const QrActor* p, Args& a, RArgs& r, bool log_std, bool sizes_ok, bool supplied_ok, std::initializer_list<const void*> own,
+                             float* const* grads, int n_grads, int64_t workspace_bytes, int32_t max_workgroups, const int (&np_of)[3],
+                             void (*const kernel[3])(Args), void (*reduce)(RArgs), int per_workgroup, void* stream) {
+  if (p->squash != QR_ACTOR_TANH_MEAN || p->log_std_w || p->log_std_b) return QR_E_KIND;
+  const int size = actor_size(p->obs_dim, p->hidden_dim, p->action_dim);
+  if (size < 0 || !sizes_ok || a.B < 1 || max_workgroups < 0) return QR_E_SIZE;
+  if (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b || (log_std && !p->log_std)) return QR_E_NULL;
+  for (int k = 0; k < n_grads; ++k)
+    if (!grads[k]) return QR_E_NULL;
+  if (!a.partials || !supplied_ok) return QR_E_NULL;
+  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, log_std ? p->log_std : nullptr};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (int k = 0; k < n_grads; ++k)
+    if (reinterpret_cast<uintptr_t>(grads[k]) & 3u) return QR_E_ALIGN;
+  for (const void* q : own)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(a.index) | reinterpret_cast<uintptr_t>(a.partials)) & 7u) return QR_E_ALIGN;
+  const int64_t grid = ppo_grid(a.B, max_workgroups);
+  const int np = np_of[size];
+  if (workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
+  const double B = (double)a.B, ba = B * A;
+  // without log_std: PpoNet::fill copies action_dim floats from it into a slot the kernel never reads; mean_b is such an array
+  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, log_std ? p->log_std : p->mean_b, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
+  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * a.lam_T / ba); a.c_S = (float)(2.0 * a.lam_S / ba); a.c_M = (float)(2.0 * a.lam_M / ba);
+  const int sizes[7] = {H * D, H, H * H, H, A * H, A, A};
+  r.partials = a.partials;
+  for (int k = 0; k < n_grads; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
+  r.n_parts = (int32_t)grid; r.np = np;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel[size], dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(reduce, dim3((unsigned)((r.off[n_grads] + per_workgroup - 1) / per_workgroup + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
 }
 
 static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* g, void* stream) {
   if (!c || !b || !g) return QR_E_NULL;
-  if (c->squash != QR_ACTOR_TANH_MEAN || c->log_std_w || c->log_std_b) return QR_E_KIND;
-  const int np = ppo_np(c->obs_dim, c->hidden_dim, c->action_dim);
-  if (!np || b->batch < 1 || b->n_steps < 1 || b->n_envs < 1 || b->row_stride < 1 || b->adv_stride < 1 || b->max_workgroups < 0) return QR_E_SIZE;
-  if (b->col_offset < 0 || b->col_offset + c->action_dim > b->row_stride || (b->final_obs && b->n_agents < 1)) return QR_E_SIZE;
-  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->mean_w || !c->mean_b || !c->log_std) return QR_E_NULL;
-  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->mean_w || !g->mean_b || !g->log_std || !g->stats) return QR_E_NULL;
-  if (!b->obs || !b->action || !b->logp_old || !b->advantage || !b->workspace || (b->final_obs && !b->done)) return QR_E_NULL;
-  if ((b->lam_S != 0.0f && !b->noise) || (b->lam_M != 0.0f && !b->nominal)) return QR_E_NULL;
-  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->mean_w, c->mean_b, c->log_std, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b,
-                                g->mean_w, g->mean_b, g->log_std, g->stats, b->obs, b->final_obs, b->action, b->logp_old, b->advantage, b->noise,
-                                b->nominal};
-  for (const void* p : floats)
-    if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(b->workspace)) & 7u) return QR_E_ALIGN;
-  const int64_t grid = ppo_grid(b->batch, b->max_workgroups);
-  if (b->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
-
-  const int D = c->obs_dim, H = c->hidden_dim, A = c->action_dim;
-  const double B = (double)b->batch, ba = B * A;
+  const bool sizes_ok = b->n_steps >= 1 && b->n_envs >= 1 && b->row_stride >= 1 && b->adv_stride >= 1 && b->col_offset >= 0 &&
+                        b->col_offset + c->action_dim <= b->row_stride && !(b->final_obs && b->n_agents < 1);
+  const bool supplied_ok = g->stats && b->obs && b->action && b->logp_old && b->advantage && !(b->final_obs && !b->done) &&
+                           !(b->lam_S != 0.0f && !b->noise) && !(b->lam_M != 0.0f && !b->nominal);
   PpoArgs a{};
-  a.w = ActorW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->mean_w, c->mean_b, c->log_std, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
   a.obs = b->obs; a.final_obs = b->final_obs; a.done = b->done; a.truncated = b->truncated;
-  a.action = b->action + b->col_offset; a.logp_old = b->logp_old + b->col_offset; a.advantage = b->advantage; a.index = b->index;
+  const int64_t col = sizes_ok && supplied_ok ? b->col_offset : 0;  // (no arithmetic on what the checks refuse)
+  a.action = b->action + col; a.logp_old = b->logp_old + col; a.advantage = b->advantage; a.index = b->index;
   a.noise = b->lam_S != 0.0f ? b->noise : nullptr; a.nominal = b->lam_M != 0.0f ? b->nominal : nullptr;
   a.partials = static_cast<double*>(b->workspace);
   a.B = b->batch; a.N = b->n_envs; a.rows = (int64_t)b->n_steps * b->n_envs;
   a.act_stride = b->row_stride; a.adv_stride = b->adv_stride; a.n_agents = b->n_agents;
   a.clip = b->clip; a.max_action = b->max_action; a.lam_T = b->lam_T; a.lam_S = b->lam_S; a.lam_M = b->lam_M;
-  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * b->lam_T / ba); a.c_S = (float)(2.0 * b->lam_S / ba); a.c_M = (float)(2.0 * b->lam_M / ba);
   PpoReduceArgs r{};
-  r.partials = a.partials;
-  float* const grads[7] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std};
-  const int sizes[7] = {H * D, H, H * H, H, A * H, A, A};
-  for (int k = 0; k < 7; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
-  r.stats = g->stats; r.log_std = c->log_std; r.n_parts = (int32_t)grid; r.np = np; r.action_dim = A; r.B = B;
+  r.stats = g->stats; r.log_std = c->log_std; r.action_dim = c->action_dim; r.B = (double)b->batch;
   r.entropy_coef = b->entropy_coef; r.lam_T = b->lam_T; r.lam_S = b->lam_S; r.lam_M = b->lam_M;
-
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (D == 23) hipLaunchKernelGGL((ppo_actor_kernel<23, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  else if (D == 15) hipLaunchKernelGGL((ppo_actor_kernel<15, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((ppo_actor_kernel<3, 4, 1>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(ppo_reduce_kernel, dim3((unsigned)((r.off[7] + 3) / 4 + 1)), dim3(256), 0, s, r);
-  return (int)hipGetLastError();
+  float* const grads[7] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std};
+  static void (*const kernel[3])(PpoArgs) = {ppo_actor_kernel<23, 16, 4>, ppo_actor_kernel<15, 16, 4>, ppo_actor_kernel<3, 4, 1>};
+  return actor_grad_launch(c, a, r, true, sizes_ok, supplied_ok,
+                           {g->stats, b->obs, b->final_obs, b->action, b->logp_old, b->advantage, b->noise, b->nominal}, grads, 7,
+                           b->workspace_bytes, b->max_workgroups, kPpoNP, kernel, ppo_reduce_kernel, 4, stream);
 }
 
 // The grid of an MLP-critic gradient launch (along x): a function of the batch and max_workgroups only.  0: default_cap, the waves
@@ -238,7 +265,7 @@ static int target_launch(const QrActor* p, const QrQCritic* c, const QrTransitio
                          bool supplied_ok, std::initializer_list<const void*> own, void (*const kernel[4])(Args), void* stream) {
   if (p && (p->squash != squash || (log_std ? !p->log_std_w || !p->log_std_b : p->log_std_w || p->log_std_b))) return QR_E_KIND;
   if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
-  if (p && (!ppo_np(p->obs_dim, p->hidden_dim, p->action_dim) || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
+  if (p && (actor_size(p->obs_dim, p->hidden_dim, p->action_dim) < 0 || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
   if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
   if (!scalars_ok) return QR_E_SIZE;
   if (int rc = twinq_critic_check(c)) return rc;
@@ -328,63 +355,30 @@ static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGra
   return (int)hipGetLastError();
 }
 
-// The grid of qr_dpg_actor_grad: ppo_grid's rule (0: one wave per SIMD at the kernel's register count, 256 CUs x 4).
-static int dpg_np(int32_t d, int32_t h, int32_t a) {  // length of a partial vector; 0: not one of the rollout's actor sizes
-  if (d == 23 && h == 16 && a == 4) return DpgLayout<23, 16, 4>::NP;
-  if (d == 15 && h == 16 && a == 4) return DpgLayout<15, 16, 4>::NP;
-  if (d == 3 && h == 4 && a == 1) return DpgLayout<3, 4, 1>::NP;
-  return 0;
-}
-
 static bool nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
 
+// (the grid of qr_dpg_actor_grad is ppo_grid's: one wave per SIMD at the kernel's register count, 256 CUs x 4)
 static int do_dpg_actor(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrDpgGrad* g, void* stream) {
   if (!p || !c || !b || !g) return QR_E_NULL;
-  if (p->squash != QR_ACTOR_TANH_MEAN || p->log_std_w || p->log_std_b) return QR_E_KIND;
-  const int np = dpg_np(p->obs_dim, p->hidden_dim, p->action_dim);
-  if (!np || !twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) || c->reserved0 != 0) return QR_E_SIZE;
-  if (p->obs_dim != c->obs_dim || p->action_dim != c->action_dim) return QR_E_SIZE;
-  if (b->batch < 1 || b->rows < 1 || g->max_workgroups < 0 || g->reserved0 != 0) return QR_E_SIZE;
-  if (!nonneg_finite(g->max_action) || !nonneg_finite(g->lam_T) || !nonneg_finite(g->lam_S) || !nonneg_finite(g->lam_M)) return QR_E_SIZE;
-  if (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b) return QR_E_NULL;
-  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b) return QR_E_NULL;  // (Q2 is not read)
-  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->mean_w || !g->mean_b || !g->stats || !g->workspace) return QR_E_NULL;
-  if (!b->obs || (g->lam_T != 0.0f && !b->obs_next) || (g->lam_S != 0.0f && !g->noise) || (g->lam_M != 0.0f && !g->nominal)) return QR_E_NULL;
-  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w,
-                                c->fc3_b, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->stats, g->noise, g->nominal, b->obs,
-                                b->obs_next};
-  for (const void* q : floats)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
-  const int64_t grid = ppo_grid(b->batch, g->max_workgroups);
-  if (g->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
-
-  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
-  const double B = (double)b->batch, ba = B * A;
+  const bool sizes_ok = twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) && c->reserved0 == 0 && p->obs_dim == c->obs_dim &&
+                        p->action_dim == c->action_dim && b->rows >= 1 && g->reserved0 == 0 && nonneg_finite(g->max_action) &&
+                        nonneg_finite(g->lam_T) && nonneg_finite(g->lam_S) && nonneg_finite(g->lam_M);
+  const bool supplied_ok = c->fc1_w && c->fc1_b && c->fc2_w && c->fc2_b && c->fc3_w && c->fc3_b && g->stats && b->obs &&  // (Q2 is not read)
+                           !(g->lam_T != 0.0f && !b->obs_next) && !(g->lam_S != 0.0f && !g->noise) && !(g->lam_M != 0.0f && !g->nominal);
   DpgArgs a{};
-  // log_std: PpoNet::fill copies action_dim floats from it into a slot this kernel never reads; mean_b is such an array
-  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->mean_b, nullptr, nullptr, QR_ACTOR_TANH_MEAN};
   a.q = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
   a.obs = b->obs; a.obs_next = g->lam_T != 0.0f ? b->obs_next : nullptr; a.index = b->index;
   a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
   a.partials = static_cast<double*>(g->workspace);
   a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim; a.max_action = g->max_action;
   a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
-  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * g->lam_T / ba); a.c_S = (float)(2.0 * g->lam_S / ba); a.c_M = (float)(2.0 * g->lam_M / ba);
   DpgReduceArgs r{};
-  r.partials = a.partials;
+  r.stats = g->stats; r.B = (double)b->batch; r.BA = r.B * p->action_dim; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
   float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b};
-  const int sizes[6] = {H * D, H, H * H, H, A * H, A};
-  for (int k = 0; k < 6; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
-  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = np; r.B = B; r.BA = ba; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
-
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (D == 23) hipLaunchKernelGGL((dpg_actor_kernel<23, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  else if (D == 15) hipLaunchKernelGGL((dpg_actor_kernel<15, 16, 4>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((dpg_actor_kernel<3, 4, 1>), dim3((unsigned)grid), dim3(64), 0, s, a);
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(dpg_reduce_kernel, dim3((unsigned)((r.off[6] + 15) / 16 + 1)), dim3(256), 0, s, r);
-  return (int)hipGetLastError();
+  static void (*const kernel[3])(DpgArgs) = {dpg_actor_kernel<23, 16, 4>, dpg_actor_kernel<15, 16, 4>, dpg_actor_kernel<3, 4, 1>};
+  return actor_grad_launch(p, a, r, false, sizes_ok, supplied_ok,
+                           {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, g->stats, g->noise, g->nominal, b->obs, b->obs_next}, grads, 6,
+                           g->workspace_bytes, g->max_workgroups, kDpgNP, kernel, dpg_reduce_kernel, 16, stream);
 }
 
 static int do_soft_update(const QrSoftUpdate* u, void* stream) {
@@ -420,9 +414,9 @@ int qr_dpg_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTra
 
 int64_t qr_dpg_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
                                      int32_t max_workgroups) {
-  const int np = qr::dpg_np(obs_dim, hidden_dim, action_dim);
-  if (!np || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
-  return qr::ppo_grid(batch, max_workgroups) * np * (int64_t)sizeof(double);
+  const int size = qr::actor_size(obs_dim, hidden_dim, action_dim);
+  if (size < 0 || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * qr::kDpgNP[size] * (int64_t)sizeof(double);
 }
 
 int qr_soft_update(const QrSoftUpdate* update, void* stream) { return qr::do_soft_update(update, stream); }
@@ -461,9 +455,9 @@ int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpo
 }
 
 int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups) {
-  const int np = qr::ppo_np(obs_dim, hidden_dim, action_dim);
-  if (!np || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
-  return qr::ppo_grid(batch, max_workgroups) * np * (int64_t)sizeof(double);
+  const int size = qr::actor_size(obs_dim, hidden_dim, action_dim);
+  if (size < 0 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * qr::kPpoNP[size] * (int64_t)sizeof(double);
 }
 
 int qr_critic_values(const QrCritic* critic, const float* obs0, const float* obs1, int64_t n_rows, float* value, int32_t value_stride,

@@ -334,6 +334,42 @@ def ppo_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
     return int(n)
 
 
+def _vector(t, width: int, dev, what: str, name: str):
+    if t is not None and (t.dtype != torch.float32 or t.device != dev or t.numel() != width or not t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {width} elements on {dev}")
+
+
+def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace, workspace_bytes, size_given: bool = True):
+    """How the four gradient functions (ppo_actor_grad, ppo_critic_grad, td3.twinq_grad, td3.dpg_actor_grad) end their checks: `grads`
+    ({name: tensor} over `shapes`) and `stats` [4] made or checked, the GPU-only error, B == 0, and the workspace made from
+    `workspace_bytes()` or checked (size_given: the library is asked for the size beside a given workspace too, so a max_workgroups
+    it refuses is reported under the size query's name).  Returns (grads, stats, workspace); workspace None: B == 0, there is nothing
+    to launch (and an empty tensor has no address to pass) — grads and stats are zero-filled and the caller returns them."""
+    if grads is None:
+        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
+    for n, s in shapes.items():
+        g = grads.get(n)
+        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
+            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    if stats is None:
+        stats = torch.empty(4, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
+        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:
+        for n in shapes:
+            grads[n].zero_()
+        stats.zero_()
+        return grads, stats, None
+    need = workspace_bytes() if workspace is None or size_given else 0
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
+    return grads, stats, workspace
+
+
 def _rows_view(t: torch.Tensor, T: int, N: int, A: int, col_offset: int, what: str, dev):
     """Row stride of a float32 [T, N, >= col_offset + A] tensor whose rows lie one row stride apart (the storage's own [T, N, 5]
     rows, or a per-agent view of them)."""
@@ -410,32 +446,13 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
             continue
         if t is None:
             raise ValueError(f"ppo_actor_grad: {name} is required when lam_{'S' if name == 'noise' else 'M'} != 0")
-        if t.dtype != torch.float32 or t.device != dev or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"ppo_actor_grad: {name} must be a contiguous float32 tensor of {n} elements on {dev}")
+        _vector(t, n, dev, "ppo_actor_grad", name)
         vecs[name] = t
     shapes = _GRAD_SHAPES(D, H, A)
-    if grads is None:
-        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
-    for n, s in shapes.items():
-        g = grads.get(n)
-        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
-            raise ValueError(f"ppo_actor_grad: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
-    if stats is None:
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError(f"ppo_actor_grad: stats must be a contiguous float32 [4] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
-        for n in shapes:
-            grads[n].zero_()
-        stats.zero_()
-        return grads, stats
-    need = ppo_workspace_bytes((D, H, A), B, max_workgroups)
+    grads, stats, workspace = _grad_outputs("ppo_actor_grad", shapes, dev, B, grads, stats, workspace,
+                                            lambda: ppo_workspace_bytes((D, H, A), B, max_workgroups))
     if workspace is None:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    elif workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError(f"ppo_actor_grad: workspace must be a contiguous tensor on {dev}")
+        return grads, stats
     b = _lib.QrPpoBatch()
     b.obs, b.final_obs, b.done, b.truncated = obs.data_ptr(), _lib.ptr(final_obs), _lib.ptr(done), _lib.ptr(truncated)
     b.action, b.logp_old, b.advantage, b.index = action.data_ptr(), logp_old.data_ptr(), advantage.data_ptr(), _lib.ptr(index)
@@ -518,28 +535,10 @@ def ppo_critic_grad(critic: CriticParams, obs, target: torch.Tensor, index: Opti
     if B and rows < 1:
         raise ValueError("ppo_critic_grad: an index needs a target with at least one element")
     shapes = {n: tuple(getattr(critic, n).shape) for n in _lib.PPO_CRITIC_GRAD_NAMES}
-    if grads is None:
-        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
-    for n, s in shapes.items():
-        g = grads.get(n)
-        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
-            raise ValueError(f"ppo_critic_grad: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
-    if stats is None:
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError(f"ppo_critic_grad: stats must be a contiguous float32 [4] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
-        for n in shapes:
-            grads[n].zero_()
-        stats.zero_()
-        return grads, stats
-    need = ppo_critic_workspace_bytes(critic.dims, B, max_workgroups)
+    grads, stats, workspace = _grad_outputs("ppo_critic_grad", shapes, dev, B, grads, stats, workspace,
+                                            lambda: ppo_critic_workspace_bytes(critic.dims, B, max_workgroups))
     if workspace is None:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    elif workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError(f"ppo_critic_grad: workspace must be a contiguous tensor on {dev}")
+        return grads, stats
     b = _lib.QrCriticBatch()
     b.obs0, b.obs1 = (_lib.ptr(obs[0]) if q.in0 else None), (_lib.ptr(obs[1]) if q.in1 else None)
     b.target, b.index = target.data_ptr(), _lib.ptr(index)

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams
+from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams, _grad_outputs, _vector
 
 
 class ReplayBuffer:
@@ -219,29 +219,10 @@ def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y
     B = rows if index is None else index.numel()
     if y is None or y.dtype != torch.float32 or y.device != dev or y.numel() != B or not y.is_contiguous():
         raise ValueError(f"{what}: y must be a contiguous float32 [{B}] tensor on {dev}")
-    shapes = critic.shapes
-    if grads is None:
-        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
-    for n, s in shapes.items():
-        g = grads.get(n)
-        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
-            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
-    if stats is None:
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
-        for n in shapes:
-            grads[n].zero_()
-        stats.zero_()
-        return grads, stats
-    need = twinq_workspace_bytes(critic.dims, B, max_workgroups)
+    grads, stats, workspace = _grad_outputs(what, critic.shapes, dev, B, grads, stats, workspace,
+                                            lambda: twinq_workspace_bytes(critic.dims, B, max_workgroups))
     if workspace is None:
-        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
-    elif workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
+        return grads, stats
     b = _lib.transitions(obs=obs, action=action, index=index, batch=B, rows=rows, row_stride=action.stride(0) if rows > 1 else max(action.shape[1], 1))
     g = _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups)
     q = critic.as_c()
@@ -301,11 +282,6 @@ def dpg_actor_workspace_bytes(actor_dims, critic_hidden: int, batch: int, max_wo
     return int(n)
 
 
-def _vector(t, width: int, dev, what: str, name: str):
-    if t is not None and (t.dtype != torch.float32 or t.device != dev or t.numel() != width or not t.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {width} elements on {dev}")
-
-
 def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor, obs_next: Optional[torch.Tensor] = None,
                    index: Optional[torch.Tensor] = None, *, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0,
                    noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None, grads: Optional[dict] = None,
@@ -337,27 +313,10 @@ def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
     _vector(nominal, A, dev, what, "nominal")
     _check_index(index, dev, what)
     B = rows if index is None else index.numel()
-    if grads is None:
-        grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
-    for n, s in shapes.items():
-        g = grads.get(n)
-        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
-            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
-    if stats is None:
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    if B == 0:   # nothing to launch (and an empty tensor has no address to pass)
-        for n in shapes:
-            grads[n].zero_()
-        stats.zero_()
-        return grads, stats
+    grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
+                                            lambda: dpg_actor_workspace_bytes(actor.dims, H, B, max_workgroups), size_given=False)
     if workspace is None:
-        workspace = torch.empty(dpg_actor_workspace_bytes(actor.dims, H, B, max_workgroups) // 8, dtype=torch.float64, device=dev)
-    elif workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
+        return grads, stats
     b = _lib.transitions(obs=obs, obs_next=obs_next if lam_T != 0 else None, index=index, batch=B, rows=rows)
     g = _lib.dpg_grad_args(grads, stats, noise if lam_S != 0 else None, nominal if lam_M != 0 else None, workspace, lam_T=lam_T, lam_S=lam_S,
                            lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)

@@ -5,7 +5,9 @@ dones, terminal observations, episode and tile counters — then the same for qr
 A third digest covers the update launches: ppo_critic_grad on every case of tests/golden/ppo_critic_grad.npz (gradients, stats), td3_target
 and twinq_grad on every case of tests/golden/td3_critic.npz (y, the twelve gradients, stats), each at the default grid, at
 max_workgroups 1 and 3, and once with a permuted index; sac_target on every case of tests/golden/sac_critic.npz (y, action_out,
-logp_out), in order and with the permuted index.
+logp_out), in order and with the permuted index; ppo_actor_grad on every case of tests/golden/ppo_actor_grad.npz (the seven gradients,
+stats) and dpg_actor_grad on every case of tests/golden/td3_actor.npz (the six gradients, stats), each at the default grid, at
+max_workgroups 1 and 3, and once with the permuted index.
 A build whose child does not exit 0 within QR_AB_TIMEOUT seconds (default 900) ends the run: nothing more is started on the card.
 
     [QR_AB_KIND=coupled] python tools/ab_equal.py build/ab/A.so build/ab/B.so        (GPU box)
@@ -61,8 +63,8 @@ rollout_digest = h.hexdigest()
 # the update launches on the fixtures of their tests
 import numpy as np
 sys.path.insert(0, os.path.join(%r, "tests"))
-import sac_ref, td3_ref, test_ppo_critic_host as pch, test_sac_critic_host as sch, test_td3_critic_host as tch
-from gym_rotor_amd import ActorParams, CriticParams, QCriticParams, _lib, ppo_critic_grad, sac_target, td3_target, twinq_grad
+import sac_ref, td3_actor_ref, td3_ref, test_ppo_actor_host as pah, test_ppo_critic_host as pch, test_sac_critic_host as sch, test_td3_critic_host as tch
+from gym_rotor_amd import ActorParams, CriticParams, QCriticParams, _lib, dpg_actor_grad, ppo_actor_grad, ppo_critic_grad, sac_target, td3_target, twinq_grad
 h = hashlib.sha256()
 cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 perm = cuda(np.random.default_rng(0).permutation(130).astype(np.int64))
@@ -103,9 +105,27 @@ for name in sch.CASES:
     for index in (None, perm):
         a_out, logp_out = torch.zeros(130, int(c["action_dim"]), device="cuda"), torch.zeros(130, device="cuda")
         put(sac_target(actor, critic_t, tens, 0, index, action_out=a_out, logp_out=logp_out, **kw), a_out, logp_out)
+g = dict(np.load(os.path.join(%r, "tests", "golden", "ppo_actor_grad.npz"), allow_pickle=False))
+for name in pah.CASES:
+    c = pah.case(g, name)
+    actor, pos = ActorParams(*[cuda(t) for t in c["w"]]), [cuda(c[k]) for k in ("obs", "action", "logp_old", "advantage")]
+    kw = dict(final_obs=cuda(c["final_obs"]), done=cuda(c["done"]), truncated=cuda(c["truncated"]), noise=cuda(c["noise"]),
+              nominal=cuda(c["nominal"].astype(np.float32)), **c["co"])
+    for index, mw in ((None, 0), (None, 1), (None, 3), (perm, 0)):
+        grads, stats = ppo_actor_grad(actor, *pos, index, max_workgroups=mw, **kw)
+        put(*[grads[n] for n in pah.NAMES], stats)
+g = td3_actor_ref.load()
+for name in td3_actor_ref.CASES:
+    c = td3_actor_ref.case(g, name)
+    q1 = [cuda(c["c_" + n]) for n in td3_actor_ref.Q1_NAMES]
+    actor, critic = ActorParams(*[cuda(c["a_" + n]) for n in td3_actor_ref.ACTOR_NAMES], None), QCriticParams(*q1, *q1, c["a_fc3_w"].shape[0])
+    kw = dict(zip(("lam_T", "lam_S", "lam_M"), c["lam"]), max_action=c["max_action"], noise=cuda(c["noise"]), nominal=cuda(c["nominal"].astype(np.float32)))
+    for index, mw in ((None, 0), (None, 1), (None, 3), (perm, 0)):
+        grads, stats = dpg_actor_grad(actor, critic, cuda(c["obs"]), cuda(c["obs_next"]), index, max_workgroups=mw, **kw)
+        put(*[grads[n] for n in _lib.DPG_GRAD_NAMES], stats)
 torch.cuda.synchronize()
 print(step_digest, rollout_digest, h.hexdigest(), int(env._episode.sum()))
-''' % (ROOT, ROOT, ROOT)
+''' % (ROOT, ROOT, ROOT, ROOT)
 out = []
 for lib in sys.argv[1:3]:
     try:

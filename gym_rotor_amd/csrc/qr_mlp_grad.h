@@ -1,8 +1,8 @@
 // qr_mlp_grad.h — part of the gfx950 quadrotor step library (included by qr_ppo_critic.h and qr_td3.h only).
 // What the update-side kernels of a three-layer MLP critic v = fc3(act(fc2(act(fc1(x))))) share: one half tile (32 rows) forwards
 // and backwards into resident gradient accumulators (mlp_grad_half), the partial vector a workgroup leaves behind
-// (MlpGradLayout, mlp_grad_write), the staging of gathered rows, and the two sums of the reduce kernels.  A kernel supplies its
-// rows, its targets, its statistics and a traits type (activation, input width, where layer 1's A operands live).
+// (MlpGradLayout, mlp_grad_write), the staging of gathered rows, the tile walk around them (mlp_grad_walk) and the sums of the reduce
+// kernels.  A kernel supplies a traits type (activation, input width, where layer 1's A operands live) and a rule (rows, targets, statistics).
 // Nothing a rollout, step, evaluate, actor or critic_kernel instantiation compiles includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -366,6 +366,68 @@ __device__ __forceinline__ void mlp_grad_write(double* P, const MlpGradLayout& Y
   }
 }
 
+// What ppo_critic_kernel (qr_ppo_critic.h) and twinq_kernel (qr_td3.h) share: the tile walk.  One wavefront per workgroup; workgroup
+// row blockIdx.y owns ONE network and walks the minibatch's 64-row tiles grid-stride along x.  Per tile: gather the rows (index,
+// clamped into [0, rows)) through the LDS tile — each row is formed there from its two sources — then per half tile mlp_grad_half
+// into the resident accumulators.  At the end the workgroup writes ONE partial vector, [blockIdx.y][blockIdx.x].
+// A Rule supplies what is the algorithm's own: Args (B, rows, index, hidden, g_scale and partials carry the same names in both), the
+// traits L1, SUMS statistics, the sizes W1S / SVEC of the LDS arrays behind layer 1's operands and the small vectors, SKIP_EMPTY
+// (a source of width 0 is not staged), and
+//   in0(a), in1(a), net(a)           the two sources' widths; the network of this workgroup row
+//   fill(w1s, svec, w, D, H, lane)   layer 1's operands and the small vectors, once per workgroup
+//   layer1(w1s)                      layer 1's operands as mlp_grad_half takes them, once per half tile
+//   row0(a, i), row1(a, i)           the two sources of storage row i
+//   target(a, i, j), stat(st, e, y)  the target of storage row i at minibatch position j; the statistics of one active row
+template <class Rule>
+__device__ __forceinline__ void mlp_grad_walk(const typename Rule::Args& a) {
+  using L1 = typename Rule::L1;
+  __shared__ float xs[64 * kMgX];          // the input tile; at the end: the lanes' VALU sums
+  __shared__ float ts[32 * kMgT], ds[32 * kMgT];
+  __shared__ float w1s[Rule::W1S], svec[Rule::SVEC], ys[64];
+  __shared__ const float *src0[64], *src1[64];
+  __shared__ double red64[64 * Rule::SUMS];
+  const int lane = threadIdx.x;
+  const int in0 = Rule::in0(a), in1 = Rule::in1(a), D = in0 + in1, H = a.hidden;
+  const MlpNetW w = Rule::net(a);
+  Rule rule;
+  float a2[4][4][4], a2t[4][4][4];
+  MlpGradAcc acc;
+  load_fc2(a2, a2t, w.fc2_w, H, lane);
+  acc.zero();
+  rule.fill(w1s, svec, w, D, H, lane);
+  for (int i = lane; i < 64 * kMgX; i += 64) xs[i] = (i % kMgX == L1::ONES) ? 1.0f : 0.0f;  // staging writes columns < D only
+  const float bias3 = w.fc3_b[0];
+  double st[Rule::SUMS] = {};
+  __syncthreads();
+
+  const int64_t tiles = (a.B + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t row0 = tile * 64;
+    {
+      const bool active = row0 + lane < a.B;
+      int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
+      i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the storage
+      src0[lane] = active ? Rule::row0(a, i) : nullptr;
+      src1[lane] = active ? Rule::row1(a, i) : nullptr;
+      ys[lane] = active ? Rule::target(a, i, row0 + lane) : 0.0f;
+    }
+    __syncthreads();
+    if (!Rule::SKIP_EMPTY || in0) stage_rows(xs, kMgX, src0, in0, 0, lane);
+    if (!Rule::SKIP_EMPTY || in1) stage_rows(xs, kMgX, src1, in1, in0, lane);
+    __syncthreads();
+
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+      const float* sv = lds_here(svec);
+      mlp_grad_half(acc, rule.layer1(w1s), a2, a2t, sv, xs, ts, ds, ys, half, row0, a.B, bias3, a.g_scale, lane,
+                    [&](float e, float y) { Rule::stat(st, e, y); });
+    }
+  }
+
+  const MlpGradLayout Y(D, H, Rule::SUMS);
+  mlp_grad_write(a.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Y.np, Y, acc, st, xs, red64, L1::ONES, D, H, lane);
+}
+
 // For the reduce kernels (256 threads, red: [256] doubles).  Workgroup blockIdx.x owns sixteen consecutive entries of the partial
 // vectors: entry e of the result = the sum over the n_parts partial vectors of entry e, in float64 and in an order the grid alone
 // fixes — sixteen slices of the partial vectors per entry, then a tree over the slices.  Returns e on the thread that holds the
@@ -392,6 +454,20 @@ __device__ __forceinline__ int entry_tensor(int e, const int32_t (&off)[7]) {
   for (int j = 1; j < 6; ++j)
     if (e >= off[j]) k = j;
   return k;
+}
+
+// A reduce kernel's gradient workgroup: reduce16_entries, then adjust(k, j, v) of the sum v of entry j of tensor k into grad[k][j].
+template <class Adjust>
+__device__ __forceinline__ void reduce16_store(const double* partials, int n_parts, int np, const int32_t (&off)[7], float* const* grad,
+                                               double* red, Adjust&& adjust) {
+  const int e = reduce16_entries(partials, n_parts, np, off[6], red);
+  if (e < 0) return;
+  const int k = entry_tensor(e, off);
+  float* dst = grad[0];
+#pragma unroll
+  for (int j = 1; j < 6; ++j)
+    if (k == j) dst = grad[j];
+  dst[e - off[k]] = (float)adjust(k, e - off[k], red[threadIdx.x]);
 }
 
 // the sum of `mine` over the workgroup's 256 threads (a tree), on every thread

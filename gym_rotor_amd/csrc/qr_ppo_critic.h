@@ -2,8 +2,8 @@
 // The critic half of one PPO minibatch update (PPO.train, algos/ppo/ppo.py:193-214): the mean squared error of MLP_Critic /
 // MLP_Critic_CTDE against the TD target plus the L2 term on the three weight tensors, and the gradients with respect to the critic's
 // six tensors, read from the rollout storage in place: ppo_critic_kernel + ppo_critic_reduce_kernel (qr_ppo_critic_grad).
-// The half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's; here: tanh, 24 inputs with fc1_w's operands
-// resident, rows from one or two sources, the target by storage row, four statistics and the L2 term.
+// The tile walk, the half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's, shared with twinq_kernel (qr_td3.h); here,
+// as PpoCriticL1 and PcRule: tanh, 24 inputs with fc1_w's operands resident, one or two row sources, the target by storage row, four statistics; the L2 term.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,58 +46,27 @@ struct PpoCriticL1 {
   }
 };
 
-// One wavefront per workgroup owns 64-row tiles of the minibatch and walks them grid-stride.  Per tile: gather the rows (index,
-// clamped into [0, rows)) through the LDS tile — a CTDE row is formed there from its two sources — then per half tile: forward,
-// the error against the target, the deltas, and the three weight-gradient contractions into the resident accumulators
-// (mlp_grad_half).  At the end the workgroup writes ONE partial vector; ppo_critic_reduce_kernel sums them.
-__global__ __launch_bounds__(64) void ppo_critic_kernel(const PpoCriticArgs a) {
-  __shared__ float xs[64 * kMgX];          // the input tile; at the end: the lanes' VALU sums
-  __shared__ float ts[32 * kMgT], ds[32 * kMgT];
-  __shared__ float svec[kMgB3], ys[64];
-  __shared__ const float* src0[64];
-  __shared__ const float* src1[64];
-  __shared__ double red64[64 * kPcSums];
-  const int lane = threadIdx.x;
-  const int D = a.in0 + a.in1, H = a.hidden;
-  PpoCriticL1 l1;
-  float a2[4][4][4], a2t[4][4][4];
-  MlpGradAcc acc;
-  l1.load(a.w.fc1_w, D, H, lane);
-  load_fc2(a2, a2t, a.w.fc2_w, H, lane);
-  acc.zero();
-  fill_vecs(svec, a.w, H, lane);
-  for (int i = lane; i < 64 * kMgX; i += 64) xs[i] = (i % kMgX == PpoCriticL1::ONES) ? 1.0f : 0.0f;  // staging writes columns < D only
-  const float bias3 = a.w.fc3_b[0];
-  double st[kPcSums] = {0.0, 0.0, 0.0, 0.0};
-  __syncthreads();
+// mlp_grad_walk's rule (qr_mlp_grad.h): one network, one or two row sources of which an empty one is skipped, fc1_w's operands
+// resident in the rule itself (no LDS behind them), the target by storage row, four statistics.
+struct PcRule {
+  using Args = PpoCriticArgs;
+  using L1 = PpoCriticL1;
+  static constexpr int SUMS = kPcSums, W1S = 1, SVEC = kMgB3;
+  static constexpr bool SKIP_EMPTY = true;
+  L1 l1;
+  static __device__ __forceinline__ int in0(const Args& a) { return a.in0; }
+  static __device__ __forceinline__ int in1(const Args& a) { return a.in1; }
+  static __device__ __forceinline__ const MlpNetW& net(const Args& a) { return a.w; }
+  __device__ __forceinline__ void fill(float*, float* svec, const MlpNetW& w, int D, int H, int lane) { l1.load(w.fc1_w, D, H, lane); fill_vecs(svec, w, H, lane); }
+  __device__ __forceinline__ const L1& layer1(const float*) const { return l1; }
+  static __device__ __forceinline__ const float* row0(const Args& a, int64_t i) { return a.rows0 + i * a.in0; }
+  static __device__ __forceinline__ const float* row1(const Args& a, int64_t i) { return a.rows1 + i * a.in1; }
+  static __device__ __forceinline__ float target(const Args& a, int64_t i, int64_t) { return a.target[i * a.tgt_stride]; }
+  static __device__ __forceinline__ void stat(double (&st)[SUMS], float e, float y) { st[0] += (double)e * (double)e; st[1] += (double)e; st[2] += (double)y; st[3] += (double)y * (double)y; }
+};
 
-  const int64_t tiles = (a.B + 63) / 64;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t row0 = tile * 64;
-    {
-      const bool active = row0 + lane < a.B;
-      int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
-      i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the storage
-      src0[lane] = active ? a.rows0 + i * a.in0 : nullptr;
-      src1[lane] = active ? a.rows1 + i * a.in1 : nullptr;
-      ys[lane] = active ? a.target[i * a.tgt_stride] : 0.0f;
-    }
-    __syncthreads();
-    if (a.in0) stage_rows(xs, kMgX, src0, a.in0, 0, lane);
-    if (a.in1) stage_rows(xs, kMgX, src1, a.in1, a.in0, lane);
-    __syncthreads();
-
-#pragma unroll 1
-    for (int half = 0; half < 2; ++half)
-      mlp_grad_half(acc, l1, a2, a2t, lds_here(svec), xs, ts, ds, ys, half, row0, a.B, bias3,
-                    a.g_scale, lane, [&](float e, float y) {
-                      st[0] += (double)e * (double)e; st[1] += (double)e; st[2] += (double)y; st[3] += (double)y * (double)y;
-                    });
-  }
-
-  const MlpGradLayout Y(D, H, kPcSums);
-  mlp_grad_write(a.partials + (int64_t)blockIdx.x * Y.np, Y, acc, st, xs, red64, PpoCriticL1::ONES, D, H, lane);
-}
+// (a CTDE row is formed in the walk's tile from its two sources; ppo_critic_reduce_kernel sums the workgroups' partial vectors)
+__global__ __launch_bounds__(64) void ppo_critic_kernel(const PpoCriticArgs a) { mlp_grad_walk<PcRule>(a); }
 
 struct PpoCriticReduceArgs {
   const double* partials;   // [n_parts][np]
@@ -116,13 +85,9 @@ __global__ __launch_bounds__(256) void ppo_critic_reduce_kernel(const PpoCriticR
   __shared__ double red[256];
   const int t = threadIdx.x;
   if (blockIdx.x + 1 < gridDim.x) {
-    const int e = reduce16_entries(o.partials, o.n_parts, o.np, o.off[6], red);
-    if (e >= 0) {
-      const int k = entry_tensor(e, o.off);
-      double v = red[t];
-      if ((k & 1) == 0) v += 2.0 * (double)o.l2_reg * (double)o.weight[k >> 1][e - o.off[k]];
-      o.grad[k][e - o.off[k]] = (float)v;
-    }
+    reduce16_store(o.partials, o.n_parts, o.np, o.off, o.grad, red, [&](int k, int j, double v) {
+      return (k & 1) == 0 ? v + 2.0 * (double)o.l2_reg * (double)o.weight[k >> 1][j] : v;
+    });
     return;
   }
   double sums[4], norm = 0.0;

@@ -4,8 +4,8 @@
 //   td3_target_kernel  (qr_twinq_target)   y = reward + discount (1 - done) min(Q1_targ, Q2_targ)(obs_next, a'), forward only:
 //                                           target_walk with Td3Rule; the walk is sac_target_kernel's too (qr_sac.h)
 //   twinq_kernel + twinq_reduce_kernel (qr_twinq_grad)   mse(Q1, y) + mse(Q2, y) and its gradients for the twelve tensors
-// The half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's, shared with ppo_critic_kernel; here: ReLU,
-// 28 inputs with fc1_w's operands in LDS, rows from obs + action, y by minibatch position, two statistics, two networks.
+// The tile walk, the half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's, shared with ppo_critic_kernel; here, as
+// TwinQL1 and TqRule: ReLU, 28 inputs with fc1_w's operands in LDS, rows from obs + action, y by minibatch position, two statistics, two networks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,57 +58,25 @@ __device__ __forceinline__ void twinq_fill_small(float* w1s, float* svec, const 
   if (lane == 0) svec[kMgB3] = p.fc3_b[0];
 }
 
-// One wavefront per workgroup; workgroup row blockIdx.y owns ONE of the two networks and walks the minibatch's 64-row tiles
-// grid-stride along x.  Per tile: gather the rows (index, clamped into [0, rows)) through the LDS tile — the observation row, then
-// the action row — then per half tile: forward, the error against y, the deltas, and the three weight-gradient contractions into
-// the resident accumulators (mlp_grad_half).  At the end the workgroup writes ONE partial vector; twinq_reduce_kernel sums them.
-__global__ __launch_bounds__(64) void twinq_kernel(const TwinQArgs a) {
-  __shared__ float xs[64 * kMgX];          // the input tile; at the end: the lanes' VALU sums
-  __shared__ float ts[32 * kMgT], ds[32 * kMgT];
-  __shared__ float w1s[TwinQL1::SIZE], svec[kTqVec], ys[64];
-  __shared__ const float* src0[64];
-  __shared__ const float* src1[64];
-  __shared__ double red64[64 * kTqSums];
-  const int lane = threadIdx.x;
-  const int D = a.obs_dim + a.action_dim, H = a.hidden;
-  const MlpNetW w = blockIdx.y ? a.net[1] : a.net[0];
-  float a2[4][4][4], a2t[4][4][4];
-  MlpGradAcc acc;
-  load_fc2(a2, a2t, w.fc2_w, H, lane);
-  acc.zero();
-  twinq_fill_small(w1s, svec, w, D, H, lane);
-  for (int i = lane; i < 64 * kMgX; i += 64) xs[i] = (i % kMgX == TwinQL1::ONES) ? 1.0f : 0.0f;  // staging writes columns < D only
-  const float bias3 = w.fc3_b[0];
-  double st[kTqSums] = {0.0, 0.0};
-  __syncthreads();
+// mlp_grad_walk's rule (qr_mlp_grad.h): workgroup row blockIdx.y owns net[blockIdx.y]; the observation row, then the action row, both
+// always staged; fc1_w's operands and fc3_b in LDS, read behind lds_here per half tile; y by minibatch position; two statistics.
+struct TqRule {
+  using Args = TwinQArgs;
+  using L1 = TwinQL1;
+  static constexpr int SUMS = kTqSums, W1S = TwinQL1::SIZE, SVEC = kTqVec;
+  static constexpr bool SKIP_EMPTY = false;
+  static __device__ __forceinline__ int in0(const Args& a) { return a.obs_dim; }
+  static __device__ __forceinline__ int in1(const Args& a) { return a.action_dim; }
+  static __device__ __forceinline__ const MlpNetW& net(const Args& a) { return blockIdx.y ? a.net[1] : a.net[0]; }
+  __device__ __forceinline__ void fill(float* w1s, float* svec, const MlpNetW& w, int D, int H, int lane) { twinq_fill_small(w1s, svec, w, D, H, lane); }
+  __device__ __forceinline__ L1 layer1(const float* w1s) const { return L1{lds_here(w1s)}; }
+  static __device__ __forceinline__ const float* row0(const Args& a, int64_t i) { return a.obs + i * a.obs_dim; }
+  static __device__ __forceinline__ const float* row1(const Args& a, int64_t i) { return a.action + i * a.act_stride; }
+  static __device__ __forceinline__ float target(const Args& a, int64_t, int64_t j) { return a.y[j]; }
+  static __device__ __forceinline__ void stat(double (&st)[SUMS], float e, float y) { st[0] += (double)e * (double)e; st[1] += (double)y; }
+};
 
-  const int64_t tiles = (a.B + 63) / 64;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t row0 = tile * 64;
-    {
-      const bool active = row0 + lane < a.B;
-      int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
-      i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
-      src0[lane] = active ? a.obs + i * a.obs_dim : nullptr;
-      src1[lane] = active ? a.action + i * a.act_stride : nullptr;
-      ys[lane] = active ? a.y[row0 + lane] : 0.0f;
-    }
-    __syncthreads();
-    stage_rows(xs, kMgX, src0, a.obs_dim, 0, lane);
-    stage_rows(xs, kMgX, src1, a.action_dim, a.obs_dim, lane);
-    __syncthreads();
-
-#pragma unroll 1
-    for (int half = 0; half < 2; ++half) {
-      const float* sv = lds_here(svec);
-      mlp_grad_half(acc, TwinQL1{lds_here(w1s)}, a2, a2t, sv, xs, ts, ds, ys, half, row0, a.B, bias3,
-                    a.g_scale, lane, [&](float e, float y) { st[0] += (double)e * (double)e; st[1] += (double)y; });
-    }
-  }
-
-  const MlpGradLayout Y(D, H, kTqSums);
-  mlp_grad_write(a.partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * Y.np, Y, acc, st, xs, red64, TwinQL1::ONES, D, H, lane);
-}
+__global__ __launch_bounds__(64) void twinq_kernel(const TwinQArgs a) { mlp_grad_walk<TqRule>(a); }
 
 struct TwinQReduceArgs {
   const double* partials;   // [2][n_parts][np]
@@ -128,16 +96,7 @@ __global__ __launch_bounds__(256) void twinq_reduce_kernel(const TwinQReduceArgs
   const int nn = blockIdx.y;
   const double* net1 = o.partials + (int64_t)o.n_parts * o.np;
   if (blockIdx.x + 1 < gridDim.x) {
-    const int e = reduce16_entries(nn ? net1 : o.partials, o.n_parts, o.np, o.off[6], red);
-    if (e >= 0) {
-      const int k = entry_tensor(e, o.off);
-      float* const* gr = nn ? o.grad[1] : o.grad[0];
-      float* dst = gr[0];
-#pragma unroll
-      for (int j = 1; j < 6; ++j)
-        if (k == j) dst = gr[j];
-      dst[e - o.off[k]] = (float)red[t];
-    }
+    reduce16_store(nn ? net1 : o.partials, o.n_parts, o.np, o.off, nn ? o.grad[1] : o.grad[0], red, [](int, int, double v) { return v; });
     return;
   }
   if (nn) return;

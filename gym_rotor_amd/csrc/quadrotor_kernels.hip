@@ -44,15 +44,15 @@
 //   qr_aux.h       auxiliary kernels (error observation, reset, state get / set, goal generator), touch_kernel, gae_kernel
 //   qr_critic.h    the PPO critic over a whole horizon (qr_critic_values, qr_critic_next_values): critic_kernel
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
-//   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): the half-tile gradient body, the partial vector, the reduction's sums
+//   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): mlp_grad_walk, the gradient kernels' shared tile walk; the half-tile gradient body, the partial vector, the reduction's sums
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
-//   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad) and
-//                  target_launch (qr_twinq_target and qr_sac_target)
+//   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad),
+//                  mlp_grad_launch (qr_ppo_critic_grad and qr_twinq_grad) and target_launch (qr_twinq_target and qr_sac_target)
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -203,42 +203,55 @@ static bool ppo_critic_sizes_ok(int64_t in0, int64_t in1, int64_t hidden) {
   return in0 >= 0 && in1 >= 0 && in0 <= kCriticIn && in1 <= kCriticIn && in0 + in1 >= 1 && in0 + in1 <= kCriticIn && hidden >= 1 && hidden <= 64;
 }
 
+// What qr_ppo_critic_grad and qr_twinq_grad check, fill and launch alike; the caller's own structs are not NULL.  The caller has filled
+// its own fields of `a` and `r` (among them a.index, a.partials = the workspace, a.B and r.grad) and says: whether its sizes are in range,
+// whether its own pointers are there, its own float pointers, the gradient tensors (6 per network), the two input widths, the hidden
+// width and the number of statistics, its grid rule, its workgroup rows (networks), and its two kernels.  The codes come in the order
+// SIZE, NULL, ALIGN, the workspace's SIZE: what each entry returned before, which ordered its checks differently only inside one class.
+template <class Args, class RArgs>
+static int mlp_grad_launch(Args& a, RArgs& r, bool sizes_ok, bool supplied_ok, std::initializer_list<const void*> own, float* const* grads,
+                           int in0, int in1, int H, int n_sums, int64_t (*grid_of)(int64_t, int32_t), int rows, int64_t workspace_bytes, int32_t max_workgroups,
+                           void (*kernel)(Args), void (*reduce)(RArgs), void* stream) {
+  if (!sizes_ok) return QR_E_SIZE;
+  for (int k = 0; k < 6 * rows; ++k)
+    if (!grads[k]) return QR_E_NULL;
+  if (!supplied_ok) return QR_E_NULL;
+  for (const void* q : own)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (int k = 0; k < 6 * rows; ++k)
+    if (reinterpret_cast<uintptr_t>(grads[k]) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(a.index) | reinterpret_cast<uintptr_t>(a.partials)) & 7u) return QR_E_ALIGN;
+  const MlpGradLayout Y(in0 + in1, H, n_sums);
+  const int64_t grid = grid_of(a.B, max_workgroups);
+  if (workspace_bytes < rows * grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
+  a.g_scale = (float)(2.0 / (double)a.B);
+  r.partials = a.partials; Y.starts(r.off); r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)a.B;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid, (unsigned)rows), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(reduce, dim3((unsigned)((Y.st + 15) / 16 + 1), (unsigned)rows), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
+
 static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCriticGrad* g, void* stream) {
   if (!c || !b || !g) return QR_E_NULL;
-  if (!ppo_critic_sizes_ok(c->in0, c->in1, c->hidden_dim)) return QR_E_SIZE;
-  if (b->batch < 1 || b->rows < 1 || b->target_stride < 1 || b->max_workgroups < 0) return QR_E_SIZE;
-  if (!c->fc1_w || !c->fc1_b || !c->fc2_w || !c->fc2_b || !c->fc3_w || !c->fc3_b) return QR_E_NULL;
-  if (!g->fc1_w || !g->fc1_b || !g->fc2_w || !g->fc2_b || !g->fc3_w || !g->fc3_b || !g->stats) return QR_E_NULL;
-  if ((c->in0 && !b->obs0) || (c->in1 && !b->obs1) || !b->target || !b->workspace) return QR_E_NULL;
-  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w,
-                                g->fc3_b, g->stats, b->obs0, b->obs1, b->target};
-  for (const void* p : floats)
-    if (reinterpret_cast<uintptr_t>(p) & 3u) return QR_E_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(b->workspace)) & 7u) return QR_E_ALIGN;
-  const int D = c->in0 + c->in1, H = c->hidden_dim;
-  const MlpGradLayout Y(D, H, kPcSums);
-  const int64_t grid = ppo_critic_grid(b->batch, b->max_workgroups);
-  if (b->workspace_bytes < grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
-
+  const bool sizes_ok = ppo_critic_sizes_ok(c->in0, c->in1, c->hidden_dim) && b->batch >= 1 && b->rows >= 1 && b->target_stride >= 1 && b->max_workgroups >= 0;
+  const bool supplied_ok = c->fc1_w && c->fc1_b && c->fc2_w && c->fc2_b && c->fc3_w && c->fc3_b && g->stats && !(c->in0 && !b->obs0) &&
+                           !(c->in1 && !b->obs1) && b->target && b->workspace;
   PpoCriticArgs a{};
   a.w = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
   a.rows0 = c->in0 ? b->obs0 : nullptr; a.rows1 = c->in1 ? b->obs1 : nullptr;
   a.target = b->target; a.index = b->index; a.partials = static_cast<double*>(b->workspace);
-  a.B = b->batch; a.rows = b->rows; a.in0 = c->in0; a.in1 = c->in1; a.hidden = H; a.tgt_stride = b->target_stride;
-  a.g_scale = (float)(2.0 / (double)b->batch);
+  a.B = b->batch; a.rows = b->rows; a.in0 = c->in0; a.in1 = c->in1; a.hidden = c->hidden_dim; a.tgt_stride = b->target_stride;
   PpoCriticReduceArgs r{};
-  r.partials = a.partials;
   r.weight[0] = c->fc1_w; r.weight[1] = c->fc2_w; r.weight[2] = c->fc3_w;
-  float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b};
-  for (int k = 0; k < 6; ++k) r.grad[k] = grads[k];
-  Y.starts(r.off);
-  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch; r.l2_reg = b->l2_reg;
-
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ppo_critic_kernel, dim3((unsigned)grid), dim3(64), 0, s, a);
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(ppo_critic_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1)), dim3(256), 0, s, r);
-  return (int)hipGetLastError();
+  r.grad[0] = g->fc1_w; r.grad[1] = g->fc1_b; r.grad[2] = g->fc2_w; r.grad[3] = g->fc2_b; r.grad[4] = g->fc3_w; r.grad[5] = g->fc3_b;
+  r.stats = g->stats; r.l2_reg = b->l2_reg;
+  return mlp_grad_launch(a, r, sizes_ok, supplied_ok,
+                         {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, g->stats, b->obs0, b->obs1, b->target}, r.grad,
+                         c->in0, c->in1, c->hidden_dim, kPcSums, ppo_critic_grid, 1, b->workspace_bytes, b->max_workgroups,
+                         ppo_critic_kernel, ppo_critic_reduce_kernel, stream);
 }
 
 static bool twinq_sizes_ok(int64_t obs_dim, int64_t action_dim, int64_t hidden) {
@@ -317,42 +330,24 @@ static int do_sac_target(const QrActor* p, const QrQCritic* c, const QrTransitio
 
 static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGrad* g, void* stream) {
   if (!c || !b || !g) return QR_E_NULL;
-  if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
-  if (b->batch < 1 || b->rows < 1 || b->row_stride < 1 || g->max_workgroups < 0 || g->reserved0 != 0) return QR_E_SIZE;
-  if (b->col_offset < 0 || b->col_offset + c->action_dim > b->row_stride) return QR_E_SIZE;
-  if (int rc = twinq_critic_check(c)) return rc;
-  float* const grads[12] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b, g->fc4_w, g->fc4_b, g->fc5_w, g->fc5_b, g->fc6_w, g->fc6_b};
-  for (const float* q : grads)
-    if (!q) return QR_E_NULL;
-  if (!g->stats || !g->y || !g->workspace || !b->obs || !b->action) return QR_E_NULL;
-  const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
-                                c->fc6_b, g->stats, g->y, b->obs, b->action};
-  for (const void* q : floats)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  for (const float* q : grads)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
-  const int D = c->obs_dim + c->action_dim, H = c->hidden_dim;
-  const MlpGradLayout Y(D, H, kTqSums);
-  const int64_t grid = twinq_grid(b->batch, g->max_workgroups);
-  if (g->workspace_bytes < 2 * grid * Y.np * (int64_t)sizeof(double)) return QR_E_SIZE;
-
+  const int critic = twinq_critic_check(c);
+  const bool sizes_ok = critic != QR_E_SIZE && b->batch >= 1 && b->rows >= 1 && b->row_stride >= 1 && g->max_workgroups >= 0 && g->reserved0 == 0 &&
+                        b->col_offset >= 0 && b->col_offset + c->action_dim <= b->row_stride;
+  const bool supplied_ok = critic == 0 && g->stats && g->y && g->workspace && b->obs && b->action;
   TwinQArgs a{};
   twinq_nets(a.net, c);
-  a.obs = b->obs; a.action = b->action + b->col_offset; a.y = g->y; a.index = b->index; a.partials = static_cast<double*>(g->workspace);
-  a.B = b->batch; a.rows = b->rows; a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = H; a.act_stride = b->row_stride;
-  a.g_scale = (float)(2.0 / (double)b->batch);
+  const int64_t col = sizes_ok && supplied_ok ? b->col_offset : 0;  // (no arithmetic on what the checks refuse)
+  a.obs = b->obs; a.action = b->action + col; a.y = g->y; a.index = b->index; a.partials = static_cast<double*>(g->workspace);
+  a.B = b->batch; a.rows = b->rows; a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.act_stride = b->row_stride;
   TwinQReduceArgs r{};
-  r.partials = a.partials;
+  float* const grads[12] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b, g->fc4_w, g->fc4_b, g->fc5_w, g->fc5_b, g->fc6_w, g->fc6_b};
   for (int k = 0; k < 12; ++k) r.grad[k / 6][k % 6] = grads[k];
-  Y.starts(r.off);
-  r.stats = g->stats; r.n_parts = (int32_t)grid; r.np = Y.np; r.B = (double)b->batch;
-
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(twinq_kernel, dim3((unsigned)grid, 2), dim3(64), 0, s, a);
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(twinq_reduce_kernel, dim3((unsigned)((Y.st + 15) / 16 + 1), 2), dim3(256), 0, s, r);
-  return (int)hipGetLastError();
+  r.stats = g->stats;
+  return mlp_grad_launch(a, r, sizes_ok, supplied_ok,
+                         {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b,
+                          g->stats, g->y, b->obs, b->action}, grads,
+                         c->obs_dim, c->action_dim, c->hidden_dim, kTqSums, twinq_grid, 2, g->workspace_bytes, g->max_workgroups,
+                         twinq_kernel, twinq_reduce_kernel, stream);
 }
 
 static bool nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }

@@ -35,7 +35,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
            "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
            "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
-           "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target")
+           "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target",
+           "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -171,6 +172,17 @@ class QrSacTarget(C.Structure):
                 ("action_out", C.c_void_p), ("logp_out", C.c_void_p), ("discount", C.c_float), ("alpha", C.c_float)]
 
 
+SAC_ACTOR_GRAD_NAMES = DPG_GRAD_NAMES + ("log_std_w", "log_std_b")   # qr_sac_actor_grad: the gradient tensors, in order
+SAC_ACTOR_STATS = 6                                                    # ... and the length of its stats
+
+
+class QrSacActorGrad(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in SAC_ACTOR_GRAD_NAMES + ("stats", "eps", "eps_reg", "eps_next", "eps_pert", "noise", "nominal", "alpha_dev",
+                                                                  "alpha_grad", "workspace")] + [
+        ("workspace_bytes", C.c_int64), ("alpha", C.c_float), ("target_entropy", C.c_float), ("lam_T", C.c_float), ("lam_S", C.c_float),
+        ("lam_M", C.c_float), ("max_action", C.c_float), ("max_workgroups", C.c_int32), ("reserved0", C.c_int32)]
+
+
 def transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None, index=None, batch, rows, row_stride=1, col_offset=0,
                 reward_stride=1, done_stride=1) -> QrTransitions:
     """QrTransitions of one minibatch of a flat transition buffer; a tensor the entry point does not read stays None."""
@@ -203,6 +215,19 @@ def dpg_grad_args(grads, stats, noise, nominal, workspace, *, lam_T, lam_S, lam_
     """QrDpgGrad of one qr_dpg_actor_grad launch: grads = {name: tensor} over DPG_GRAD_NAMES."""
     g = QrDpgGrad(*[grads[n].data_ptr() for n in DPG_GRAD_NAMES], stats.data_ptr(), ptr(noise), ptr(nominal), workspace.data_ptr())
     g.workspace_bytes = workspace.numel() * workspace.element_size()
+    g.lam_T, g.lam_S, g.lam_M, g.max_action = float(lam_T), float(lam_S), float(lam_M), float(max_action)
+    g.max_workgroups, g.reserved0 = int(max_workgroups), 0
+    return g
+
+
+def sac_actor_grad_args(grads, stats, workspace, *, eps, eps_reg, eps_next, eps_pert, noise, nominal, alpha_dev, alpha_grad, alpha, target_entropy,
+                        lam_T, lam_S, lam_M, max_action, max_workgroups) -> QrSacActorGrad:
+    """QrSacActorGrad of one qr_sac_actor_grad launch: grads = {name: tensor} over SAC_ACTOR_GRAD_NAMES; alpha_dev: the device scalar that
+    wins over `alpha`, or None."""
+    g = QrSacActorGrad(*[grads[n].data_ptr() for n in SAC_ACTOR_GRAD_NAMES], stats.data_ptr(), ptr(eps), ptr(eps_reg), ptr(eps_next), ptr(eps_pert),
+                       ptr(noise), ptr(nominal), ptr(alpha_dev), ptr(alpha_grad), workspace.data_ptr())
+    g.workspace_bytes = workspace.numel() * workspace.element_size()
+    g.alpha, g.target_entropy = float(alpha), float(target_entropy)
     g.lam_T, g.lam_S, g.lam_M, g.max_action = float(lam_T), float(lam_S), float(lam_M), float(max_action)
     g.max_workgroups, g.reserved0 = int(max_workgroups), 0
     return g
@@ -361,6 +386,10 @@ def load():
     lib.qr_soft_update.argtypes = [P(QrSoftUpdate), C.c_void_p]
     lib.qr_sac_target.restype = C.c_int
     lib.qr_sac_target.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrSacTarget), C.c_void_p]
+    lib.qr_sac_actor_grad.restype = C.c_int
+    lib.qr_sac_actor_grad.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrSacActorGrad), C.c_void_p]
+    lib.qr_sac_actor_workspace_bytes.restype = C.c_int64
+    lib.qr_sac_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

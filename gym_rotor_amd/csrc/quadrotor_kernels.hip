@@ -50,6 +50,7 @@
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
+//   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad and qr_twinq_grad) and target_launch (qr_twinq_target and qr_sac_target)
@@ -76,6 +77,7 @@
 #include "qr_td3.h"
 #include "qr_td3_actor.h"
 #include "qr_sac.h"
+#include "qr_sac_actor.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -376,6 +378,68 @@ static int do_dpg_actor(const QrActor* p, const QrQCritic* c, const QrTransition
                            g->workspace_bytes, g->max_workgroups, kDpgNP, kernel, dpg_reduce_kernel, 16, stream);
 }
 
+constexpr int kSacNP[3] = {SacLayout<23, 16, 4>::NP, SacLayout<15, 16, 4>::NP, SacLayout<3, 4, 1>::NP};
+
+// (actor_grad_launch does not fit: it takes the tanh-of-mean form with six or seven tensors and no second critic; the order of the
+//  checks is its own — KIND, SIZE, NULL, ALIGN, the workspace's SIZE — and the grid is ppo_grid's)
+static int do_sac_actor(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrSacActorGrad* g, void* stream) {
+  if (!p || !c || !b || !g) return QR_E_NULL;
+  if (p->squash != QR_ACTOR_TANH_SAMPLE || !p->log_std_w || !p->log_std_b) return QR_E_KIND;
+  const int size = actor_size(p->obs_dim, p->hidden_dim, p->action_dim);
+  if (size < 0 || !twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) || c->reserved0 != 0 || p->obs_dim != c->obs_dim ||
+      p->action_dim != c->action_dim || b->batch < 1 || b->rows < 1 || g->reserved0 != 0 || g->max_workgroups < 0 || !nonneg_finite(g->alpha) ||
+      !nonneg_finite(g->max_action) || !nonneg_finite(g->lam_T) || !nonneg_finite(g->lam_S) || !nonneg_finite(g->lam_M) ||
+      !(g->target_entropy >= -3.0e38f && g->target_entropy <= 3.0e38f))
+    return QR_E_SIZE;
+  if (int rc = twinq_critic_check(c)) return rc;
+  if (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b) return QR_E_NULL;
+  float* const grads[8] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b};
+  for (float* q : grads)
+    if (!q) return QR_E_NULL;
+  if (!g->stats || !g->workspace || !b->obs || (g->lam_T != 0.0f && !b->obs_next) || (g->lam_S != 0.0f && !g->noise) ||
+      (g->lam_M != 0.0f && !g->nominal))
+    return QR_E_NULL;
+  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->log_std_w, p->log_std_b, c->fc1_w, c->fc1_b,
+                                c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b, g->fc1_w,
+                                g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b, g->stats, g->eps, g->eps_reg,
+                                g->eps_next, g->eps_pert, g->noise, g->nominal, g->alpha_dev, g->alpha_grad, b->obs, b->obs_next};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
+  const int64_t grid = ppo_grid(b->batch, g->max_workgroups);
+  const int np = kSacNP[size];
+  if (g->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
+  const double B = (double)b->batch, ba = B * A;
+  SacActorArgs a{};
+  // (PpoNet::fill copies action_dim floats from log_std into a slot this kernel never reads; mean_b is such an array)
+  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->mean_b, p->log_std_w, p->log_std_b, QR_ACTOR_TANH_SAMPLE};
+  twinq_nets(a.q, c);
+  const bool any = g->lam_T != 0.0f || g->lam_S != 0.0f || g->lam_M != 0.0f;
+  a.obs = b->obs; a.obs_next = g->lam_T != 0.0f ? b->obs_next : nullptr; a.index = b->index;
+  a.eps[0] = g->eps; a.eps[1] = any ? g->eps_reg : nullptr; a.eps[2] = g->lam_T != 0.0f ? g->eps_next : nullptr;
+  a.eps[3] = g->lam_S != 0.0f ? g->eps_pert : nullptr;
+  a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
+  a.alpha_dev = g->alpha_dev; a.partials = static_cast<double*>(g->workspace);
+  a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim; a.alpha = g->alpha; a.max_action = g->max_action;
+  a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
+  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * a.lam_T / ba); a.c_S = (float)(2.0 * a.lam_S / ba); a.c_M = (float)(2.0 * a.lam_M / ba);
+  SacActorReduceArgs r{};
+  const int sizes[8] = {H * D, H, H * H, H, A * H, A, A * H, A};
+  r.partials = a.partials;
+  for (int k = 0; k < 8; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
+  r.stats = g->stats; r.alpha_grad = g->alpha_grad; r.alpha_dev = g->alpha_dev; r.n_parts = (int32_t)grid; r.np = np; r.B = B; r.BA = ba;
+  r.alpha = g->alpha; r.target_entropy = g->target_entropy; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
+
+  static void (*const kernel[3])(SacActorArgs) = {sac_actor_kernel<23, 16, 4>, sac_actor_kernel<15, 16, 4>, sac_actor_kernel<3, 4, 1>};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel[size], dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(sac_actor_reduce_kernel, dim3((unsigned)((r.off[8] + 15) / 16 + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
+
 static int do_soft_update(const QrSoftUpdate* u, void* stream) {
   if (!u) return QR_E_NULL;
   if (u->n_tensors < 1 || u->n_tensors > kSoftMax || u->reserved0 != 0 || !(u->tau >= 0.0 && u->tau <= 1.0)) return QR_E_SIZE;
@@ -418,6 +482,17 @@ int qr_soft_update(const QrSoftUpdate* update, void* stream) { return qr::do_sof
 
 int qr_sac_target(const QrActor* actor, const QrQCritic* critic_target, const QrTransitions* batch, const QrSacTarget* target, void* stream) {
   return qr::do_sac_target(actor, critic_target, batch, target, stream);
+}
+
+int qr_sac_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTransitions* batch, const QrSacActorGrad* grad, void* stream) {
+  return qr::do_sac_actor(actor, critic, batch, grad, stream);
+}
+
+int64_t qr_sac_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
+                                     int32_t max_workgroups) {
+  const int size = qr::actor_size(obs_dim, hidden_dim, action_dim);
+  if (size < 0 || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * qr::kSacNP[size] * (int64_t)sizeof(double);
 }
 
 int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,

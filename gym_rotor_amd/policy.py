@@ -339,9 +339,9 @@ def _vector(t, width: int, dev, what: str, name: str):
         raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {width} elements on {dev}")
 
 
-def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace, workspace_bytes, size_given: bool = True):
-    """How the four gradient functions (ppo_actor_grad, ppo_critic_grad, td3.twinq_grad, td3.dpg_actor_grad) end their checks: `grads`
-    ({name: tensor} over `shapes`) and `stats` [4] made or checked, the GPU-only error, B == 0, and the workspace made from
+def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace, workspace_bytes, size_given: bool = True, n_stats: int = 4):
+    """How the gradient functions (ppo_actor_grad, ppo_critic_grad, td3.twinq_grad, td3.dpg_actor_grad, sac.sac_actor_grad) end their checks:
+    `grads` ({name: tensor} over `shapes`) and `stats` [n_stats] made or checked, the GPU-only error, B == 0, and the workspace made from
     `workspace_bytes()` or checked (size_given: the library is asked for the size beside a given workspace too, so a max_workgroups
     it refuses is reported under the size query's name).  Returns (grads, stats, workspace); workspace None: B == 0, there is nothing
     to launch (and an empty tensor has no address to pass) — grads and stats are zero-filled and the caller returns them."""
@@ -352,9 +352,9 @@ def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace,
         if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
             raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
     if stats is None:
-        stats = torch.empty(4, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != 4 or not stats.is_contiguous():
-        raise ValueError(f"{what}: stats must be a contiguous float32 [4] tensor on {dev}")
+        stats = torch.empty(n_stats, dtype=torch.float32, device=dev)
+    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != n_stats or not stats.is_contiguous():
+        raise ValueError(f"{what}: stats must be a contiguous float32 [{n_stats}] tensor on {dev}")
     if dev.type != "cuda":
         raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
     if B == 0:

@@ -1,21 +1,27 @@
-"""The critic half of a SAC update on the device: the soft target values of a minibatch in one launch (`sac_target`: qr_sac_target)
+"""Both halves of a SAC update on the device.  The critic half: the soft target values of a minibatch in one launch (`sac_target`: qr_sac_target)
 and, on live modules, the whole critic update (`sac_critic_loss`: `sac_target`, then `td3.twinq_grad`).  The replay buffer, the
 twin-Q regression and the Polyak step are td3.py's (`ReplayBuffer`, `twinq_grad`, `soft_update`): SAC's critic has TD3's form.
 
 Replaces, per minibatch of `SAC.train` (algos/sac/sac.py:123-170, the non-CTDE branch without the spectral-norm term): the index
 clones, `actor.sample` on obs_next (two heads, the clamp, rsample, tanh, the log-probability with its tanh correction), the target
-critic's two passes, min, the entropy term and the Bellman line, two mse_loss and the autograd backward pass.  The actor half, alpha's
-own update and the optimiser group of twelve tensors are not here (twelve tensors: two `optim.DeviceAdamW` groups of six).
+critic's two passes, min, the entropy term and the Bellman line, two mse_loss and the autograd backward pass.
+
+The actor half (`sac_actor_grad`: qr_sac_actor_grad; on live modules `sac_actor_loss`) replaces, per minibatch (sac.py:182-211 with
+algos/policy_regularization.py): the index clones, four `actor.sample` passes, two critic passes, min, the three smoothness terms and
+autograd through all of it — and leaves d alpha_loss / d log_alpha beside the gradients.  The optimiser steps stay the caller's: no
+updater class is built here.
 """
 from __future__ import annotations
 
 from typing import Optional, Union
 
+import ctypes as C
+
 import torch
 
 from . import _lib
-from .policy import ActorParams, QCriticParams
-from .td3 import ReplayBuffer, _critic_update_state, _target, twinq_grad
+from .policy import ActorParams, QCriticParams, _grad_outputs, _vector
+from .td3 import ReplayBuffer, _check_actor, _check_index, _critic_update_state, _rows, _target, twinq_grad
 
 
 def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
@@ -79,4 +85,132 @@ def sac_critic_loss(critic_module, critic_target_module, actor_module, buffer: R
                discount=discount, alpha=alpha, noise=noise, out=y)
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
                           workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def sac_actor_workspace_bytes(actor_dims, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `sac_actor_grad` call needs (qr_sac_actor_workspace_bytes); actor_dims = (obs_dim, hidden, action_dim)."""
+    n = _lib.load().qr_sac_actor_workspace_bytes(*(int(d) for d in actor_dims), int(critic_hidden), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_sac_actor_workspace_bytes")
+    return int(n)
+
+
+def sac_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor, obs_next: Optional[torch.Tensor] = None,
+                   index: Optional[torch.Tensor] = None, *, alpha: Union[float, torch.Tensor] = 0.2, lam_T: float = 0.4, lam_S: float = 0.3,
+                   lam_M: float = 0.6, max_action: float = 1.0, eps: Optional[torch.Tensor] = None, eps_reg: Optional[torch.Tensor] = None,
+                   eps_next: Optional[torch.Tensor] = None, eps_pert: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                   nominal: Optional[torch.Tensor] = None, alpha_grad: Optional[torch.Tensor] = None, target_entropy: Optional[float] = None,
+                   grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                   max_workgroups: int = 0):
+    """SAC's actor loss and its gradients (qr_sac_actor_grad; sac.py:182-211 without the spectral-norm term, with
+    algos/policy_regularization.py), c = clamp to +-max_action, i = index[j], sample = MLP_Actor_SAC.sample with the given draws:
+        (a, logp) = sample(obs[i], eps[j]);   L0 = mean_j (alpha logp_j - min(Q1, Q2)(obs[i], a_j))
+        r = c(sample(obs[i], eps_reg[j]).a);  rn = c(sample(obs_next[i], eps_next[j]).a);  rp = c(sample(obs[i] + noise, eps_pert[j]).a)
+        loss = L0 + lam_T mse(r, rn) + lam_S mse(r, rp) + lam_M mse(r, nominal)
+    — no autograd, no copies of the minibatch's rows.  actor: `ActorParams.from_sac_module(module)` in one of the three sizes of the
+    rollout; critic: the twin critic, both networks are read.  obs, obs_next [rows, D] contiguous float32 (obs_next: needed when
+    lam_T != 0); the four eps: float32 [B, A] standard-normal draws by minibatch position (rsample's), None: zeros; noise [D]: ONE row,
+    needed when lam_S != 0; nominal [A]: needed when lam_M != 0; index int64 [B], None: all rows in order.  alpha: a Python float, or a
+    float32 tensor of one element on the device that the kernels read (no host synchronisation); it is a constant of this loss.
+    alpha_grad: an optional float32 tensor of one element that receives d alpha_loss / d log_alpha = -(target_entropy + mean_j logp_j);
+    target_entropy: None is -A.
+    Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b —
+    `grads` given: overwritten in place — and stats float32 [6] = loss, the mean of min(Q1, Q2), the mean logp of the loss pass, the
+    weighted sum of the three smoothness terms, the share of the loss pass's raw log_std components outside [-20, 2], the share of
+    rows that took Q2."""
+    what = "sac_actor_grad"
+    dev = critic.device
+    D, A, H = critic.dims
+    shapes = _check_actor(actor, D, A, dev, what, _lib.ACTOR_TANH_SAMPLE, True,
+                          "the actor must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
+    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
+        if not 0.0 <= float(v) < float("inf"):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    a, alpha_dev = alpha, None
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
+            raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
+        alpha_dev, a = a, 0.0
+    elif not 0.0 <= float(a) < float("inf"):
+        raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
+    te = -float(A) if target_entropy is None else float(target_entropy)
+    if not -float("inf") < te < float("inf"):
+        raise ValueError(f"{what}: target_entropy must be finite, got {target_entropy}")
+    if alpha_grad is not None and (alpha_grad.dtype != torch.float32 or alpha_grad.device != dev or alpha_grad.numel() != 1):
+        raise ValueError(f"{what}: alpha_grad must be a float32 tensor of one element on {dev}")
+    rows = _rows(obs, D, dev, what, "obs")
+    if lam_T != 0 and _rows(obs_next, D, dev, what, "obs_next") != rows:
+        raise ValueError(f"{what}: obs_next must have obs's {rows} rows")
+    if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
+        raise ValueError(f"{what}: noise [{D}] is required when lam_S != 0, nominal [{A}] when lam_M != 0")
+    _vector(noise, D, dev, what, "noise")
+    _vector(nominal, A, dev, what, "nominal")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    for name, x in (("eps", eps), ("eps_reg", eps_reg), ("eps_next", eps_next), ("eps_pert", eps_pert)):
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
+    shapes = {n: shapes[n] for n in _lib.SAC_ACTOR_GRAD_NAMES}
+    grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
+                                            lambda: sac_actor_workspace_bytes(actor.dims, H, B, max_workgroups), size_given=False,
+                                            n_stats=_lib.SAC_ACTOR_STATS)
+    if workspace is None:
+        if alpha_grad is not None:
+            alpha_grad.zero_()
+        return grads, stats
+    b = _lib.transitions(obs=obs, obs_next=obs_next if lam_T != 0 else None, index=index, batch=B, rows=rows)
+    g = _lib.sac_actor_grad_args(grads, stats, workspace, eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert,
+                                 noise=noise if lam_S != 0 else None, nominal=nominal if lam_M != 0 else None, alpha_dev=alpha_dev,
+                                 alpha_grad=alpha_grad, alpha=a, target_entropy=te, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                                 max_action=max_action, max_workgroups=max_workgroups)
+    p, q = actor.as_c(), critic.as_c()
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_sac_actor_grad(C.byref(p), C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_sac_actor_grad")
+    return grads, stats
+
+
+def sac_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                   log_alpha: Optional[torch.Tensor] = None, target_entropy: Optional[float] = None, alpha: Union[float, torch.Tensor] = 0.2,
+                   lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, eps: Optional[torch.Tensor] = None,
+                   eps_reg: Optional[torch.Tensor] = None, eps_next: Optional[torch.Tensor] = None, eps_pert: Optional[torch.Tensor] = None,
+                   noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                   max_workgroups: int = 0) -> torch.Tensor:
+    """The actor update of SAC.train, as the reference writes it, without autograd: `sac_actor_grad` on the live `actor_module`
+    (attributes fc1, fc2, mean_linear, log_std_linear) and `critic_module` (fc1 .. fc6) for agent k of `buffer`; writes the gradients
+    into the eight `.grad` tensors of the actor in place, as `loss.backward()` after `zero_grad()` leaves them.  log_alpha: the
+    one-element parameter of automatic entropy tuning; given, its `.grad` receives d alpha_loss / d log_alpha =
+    -(target_entropy + mean logp) (target_entropy: None is -A).  alpha: a float, or the device tensor exp(log_alpha) — it is read, not
+    formed here.  The four eps: the [B, A] draws of the four samples (rsample's), None: zeros; noise: policy_regularization's ONE [D]
+    row; nominal: its [A] hover action.  Returns stats [6] (stats[0] = the loss).  From the second call on with an unchanged B nothing
+    is allocated: the workspace and stats are cached on the buffer.
+    The optimiser steps stay the caller's: the actor's eight tensors are one `optim.DeviceAdamW` group, log_alpha is a group of one,
+    and `torch.exp(log_alpha, out=alpha)` feeds the next `sac_target` and `sac_actor_loss`."""
+    if not isinstance(buffer, ReplayBuffer):
+        raise ValueError("sac_actor_loss: buffer must be a ReplayBuffer")
+    m = actor_module
+    params = [t for l in (m.fc1, m.fc2, m.mean_linear, m.log_std_linear) for t in (l.weight, l.bias)]
+    if log_alpha is not None:
+        if log_alpha.numel() != 1:
+            raise ValueError("sac_actor_loss: log_alpha must have one element")
+        params.append(log_alpha)
+    for p in params:
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+    grads = {n: p.grad for n, p in zip(_lib.SAC_ACTOR_GRAD_NAMES, params)}
+    actor = ActorParams.from_sac_module(m)
+    critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
+    B = buffer.capacity if index is None else index.numel()
+    key = ("sac_actor", k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = sac_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev),
+                                    torch.empty(_lib.SAC_ACTOR_STATS, dtype=torch.float32, device=dev))
+    workspace, own_stats = hit
+    _, stats = sac_actor_grad(actor, critic, buffer.obs[k], buffer.obs_next[k], index, alpha=alpha, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                              max_action=max_action, eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert, noise=noise,
+                              nominal=nominal, alpha_grad=None if log_alpha is None else log_alpha.grad, target_entropy=target_entropy,
+                              grads=grads, stats=own_stats if stats is None else stats, workspace=workspace, max_workgroups=max_workgroups)
     return stats

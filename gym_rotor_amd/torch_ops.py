@@ -435,6 +435,26 @@ def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_
                noise=noise, action_next=action_next, logp_next=logp_next, out=y, action_out=action_out, logp_out=logp_out)
 
 
+@torch.library.custom_op(f"{_NS}::qr_sac_actor_grad", mutates_args=("grads", "stats", "alpha_grad"))
+def qr_sac_actor_grad(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor, obs_next: Optional[torch.Tensor],
+                      index: Optional[torch.Tensor], eps: Optional[torch.Tensor], eps_reg: Optional[torch.Tensor], eps_next: Optional[torch.Tensor],
+                      eps_pert: Optional[torch.Tensor], noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor], grads: List[torch.Tensor],
+                      stats: torch.Tensor, alpha_grad: Optional[torch.Tensor], alpha: float, target_entropy: float, lam_T: float, lam_S: float,
+                      lam_M: float, max_action: float, alpha_dev: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> None:
+    """SAC's actor loss and its eight gradients for one minibatch (qr_sac_actor_grad).  actor and grads: eight tensors each, fc1_w, fc1_b,
+    fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b; critic: the twin critic's twelve; stats float32 [6]; alpha_dev: the temperature
+    as a device tensor of one element, which wins over alpha.  Everything else as sac.sac_actor_grad."""
+    from .policy import ActorParams
+    from .sac import sac_actor_grad
+    _gpu(stats)
+    if len(actor) != 8 or len(grads) != 8:
+        raise ValueError("a SAC actor and its gradients are 8 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b")
+    sac_actor_grad(ActorParams(*actor[:6], None, actor[6], actor[7], _lib.ACTOR_TANH_SAMPLE), _qcritic_params(critic, action_dim), obs, obs_next,
+                   index, alpha=alpha if alpha_dev is None else alpha_dev, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action,
+                   eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert, noise=noise, nominal=nominal, alpha_grad=alpha_grad,
+                   target_entropy=target_entropy, grads=dict(zip(_lib.SAC_ACTOR_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

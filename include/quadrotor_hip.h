@@ -701,6 +701,60 @@ typedef struct QrSacTarget {
  * for a float pointer that is not 4-byte aligned or an index pointer that is not 8-byte aligned.  Nothing is launched on an error. */
 int qr_sac_target(const QrActor* actor, const QrQCritic* critic_target, const QrTransitions* batch, const QrSacTarget* target, void* stream);
 
+/* The actor half of one SAC minibatch update (SAC.train, algos/sac/sac.py:182-211, the non-CTDE branch without the spectral-norm
+ * term, with algos/policy_regularization.py for rl_algo == "SAC" and MLP_Actor_SAC.sample, algos/sac/sac_mlp.py:55-79) for ONE agent,
+ * read from the transition buffer in place: the loss, loss.backward()'s gradients with respect to the actor's eight tensors and what
+ * alpha's own update needs, without autograd.  With j the minibatch position, i = index[j] and c(.) the clamp to +-max_action:
+ *     sample(x, e):  mean, ls = pi(x);  ls = clamp(ls, -20, 2);  u = mean + exp(ls) * e;  a = tanh(u)
+ *                    logp = sum_f [ -e^2 / 2 - ls - log sqrt(2 pi) - log(1 - a^2 + 1e-6) ]
+ *     loss pass:     (a, logp) = sample(obs[i], eps[j])                              (no clamp on a)
+ *                    L0 = mean_j ( alpha * logp_j - min(Q1, Q2)(obs[i], a_j) )
+ *     reg passes:    r  = c(sample(obs[i],         eps_reg[j]).a)                    when any lam != 0
+ *                    rn = c(sample(obs_next[i],    eps_next[j]).a)                   when lam_T != 0
+ *                    rp = c(sample(obs[i] + noise, eps_pert[j]).a)                   when lam_S != 0;  noise: ONE [obs_dim] row
+ *     loss = L0 + lam_T mse(r, rn) + lam_S mse(r, rp) + lam_M mse(r, nominal)        mse: the mean over batch x action_dim elements
+ *     alpha_grad = d alpha_loss / d log_alpha = -(target_entropy + mean_j logp_j)    (logp of the loss pass, detached)
+ * Four independent noises; the smoothness terms use the regulariser's own sample r, not the loss pass's action.  Gradients flow through
+ * both heads in every pass: da/dmean = 1 - a^2, da/dls = (1 - a^2) exp(ls) e, dlogp/du = 2 a (1 - a^2) / (1 - a^2 + 1e-6) and
+ * dlogp/dls = -1 beside it; everything through ls is gated by -20 <= raw ls <= 2 (torch.clamp passes the gradient at the bounds), and
+ * c(.) by |a| <= max_action.  min(Q1, Q2) sends a row's gradient to the smaller critic, half to each on an exact tie; the critics' own
+ * gradients are not produced.  alpha is a constant of this loss.  1 - a^2 and a are formed from t = exp(-2 |u|) as in qr_sac_target,
+ * -e^2 / 2 from e.  A coefficient lam_* equal to 0 skips that term's passes and reads none of their inputs; with all three 0 only the
+ * loss pass runs.
+ *   actor: a QrActor of the QR_ACTOR_TANH_SAMPLE form with the log_std head, in one of the sizes (23,16,4), (15,16,4), (3,4,1).
+ *   critic: a QrQCritic whose obs_dim and action_dim equal the actor's; both networks are read.
+ *   batch: obs, obs_next (read only with lam_T != 0) and index of a QrTransitions.
+ *   eps, eps_reg, eps_next, eps_pert: [batch][action_dim] float32 standard-normal draws, row j for minibatch position j; NULL: zeros
+ *   through the same code path.  noise [obs_dim]: required when lam_S != 0; nominal [action_dim]: when lam_M != 0.
+ *   alpha: the temperature; alpha_dev, where not NULL, is a device float read in the kernels and wins.  alpha_grad: optional, one float.
+ * Outputs, overwritten: the eight gradient tensors in the shapes of the QrActor's, and stats [6] = loss, the mean of min(Q1, Q2), the
+ * mean logp of the loss pass, lam_T L_T + lam_S L_S + lam_M L_M, the share of the loss pass's batch x action_dim raw log_std components
+ * outside [-20, 2], the share of rows with Q2 < Q1 (both exact counts divided once).
+ * Two launches: one wavefront per workgroup accumulates its share of the 64-row tiles and writes ONE partial vector into `workspace`;
+ * a second kernel sums the partial vectors in float64 in a fixed order.  The same inputs and grid give the same bits (no atomics).
+ * The grid is min(ceil(batch / 64), max_workgroups), max_workgroups = 0: the library's rule (1024). */
+typedef struct QrSacActorGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *mean_w, *mean_b, *log_std_w, *log_std_b, *stats;
+  const float *eps, *eps_reg, *eps_next, *eps_pert;
+  const float* noise;      const float* nominal;
+  const float* alpha_dev;  float* alpha_grad;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_sac_actor_workspace_bytes(...); 8-byte aligned */
+  float alpha, target_entropy;
+  float lam_T, lam_S, lam_M, max_action;
+  int32_t max_workgroups, reserved0;
+} QrSacActorGrad;
+/* QR_E_NULL for a NULL struct, actor weight, critic weight, obs, output or workspace pointer (index, the four eps, alpha_dev and
+ * alpha_grad optional; obs_next, noise, nominal as above); QR_E_KIND for squash != QR_ACTOR_TANH_SAMPLE or an actor without the log_std
+ * head; QR_E_SIZE for an actor size other than the three above, critic widths outside their ranges, an actor whose obs_dim or
+ * action_dim differs from the critic's, reserved0 != 0 (either struct), batch < 1, rows < 1, max_workgroups < 0, a negative or
+ * non-finite alpha, max_action or lam_*, a non-finite target_entropy, or a workspace that is too small; QR_E_ALIGN for a float pointer
+ * that is not 4-byte aligned or an index / workspace pointer that is not 8-byte aligned.  Nothing is launched or written on an error. */
+int qr_sac_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTransitions* batch, const QrSacActorGrad* grad, void* stream);
+/* Bytes of workspace qr_sac_actor_grad needs for this actor size, critic width, batch and max_workgroups; QR_E_SIZE (< 0) where it
+ * would refuse them. */
+int64_t qr_sac_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
+                                     int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

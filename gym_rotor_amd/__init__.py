@@ -13,7 +13,9 @@ from .rollout import RolloutStorage  # noqa: F401
 from .policy import ActorParams, ActorPopulation, CriticParams, QCriticParams, actor_loss, critic_loss, ppo_actor_grad, ppo_critic_grad, random_actors  # noqa: F401
 from .optim import DeviceAdamW, PpoUpdater, adamw_step, minibatch_slices  # noqa: F401
 from .td3 import ReplayBuffer, dpg_actor_grad, soft_update, td3_actor_loss, td3_critic_loss, td3_target, twinq_grad  # noqa: F401
+from .td3 import td3_critic_loss_ctde, td3_target_ctde, twinq_grad_ctde  # noqa: F401
 from .sac import sac_actor_grad, sac_actor_loss, sac_actor_workspace_bytes, sac_critic_loss, sac_target  # noqa: F401
+from .sac import sac_critic_loss_ctde, sac_target_ctde  # noqa: F401
 from .evaluate import EvalResult, PopulationResult, evaluate_policy, evaluate_population  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)
 

@@ -36,7 +36,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
            "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
            "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target",
-           "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes")
+           "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes",
+           "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -233,6 +234,53 @@ def sac_actor_grad_args(grads, stats, workspace, *, eps, eps_reg, eps_next, eps_
     return g
 
 
+class QrCtdeTransitions(C.Structure):
+    _fields_ = [("obs", C.c_void_p * 2), ("obs_next", C.c_void_p * 2), ("action", C.c_void_p * 2), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("index", C.c_void_p), ("batch", C.c_int64), ("rows", C.c_int64), ("obs_dim", C.c_int32 * 2), ("action_dim", C.c_int32 * 2),
+                ("row_stride", C.c_int32 * 2), ("col_offset", C.c_int32 * 2), ("reward_stride", C.c_int32), ("done_stride", C.c_int32)]
+
+
+class QrCtdeTd3Target(C.Structure):
+    _fields_ = [("eps", C.c_void_p * 2), ("action_next", C.c_void_p * 2), ("y", C.c_void_p), ("discount", C.c_float), ("target_noise", C.c_float),
+                ("noise_clip", C.c_float), ("max_action", C.c_float)]
+
+
+class QrCtdeSacTarget(C.Structure):
+    _fields_ = [("eps", C.c_void_p * 2), ("eps_logp", C.c_void_p), ("action_next", C.c_void_p * 2), ("logp_next", C.c_void_p),
+                ("alpha_dev", C.c_void_p), ("y", C.c_void_p), ("action_out", C.c_void_p * 2), ("logp_out", C.c_void_p), ("discount", C.c_float),
+                ("alpha", C.c_float), ("agent", C.c_int32), ("reserved0", C.c_int32)]
+
+
+def _pair(x):
+    x = (None, None) if x is None else x
+    return (C.c_void_p * 2)(ptr(x[0]), ptr(x[1]))
+
+
+def ctde_transitions(*, obs=None, obs_next=None, action=None, reward=None, done=None, index=None, batch, rows, obs_dims, action_dims,
+                     row_strides=(1, 1), col_offsets=(0, 0), reward_stride=1, done_stride=1) -> QrCtdeTransitions:
+    """QrCtdeTransitions of one minibatch of a two-agent buffer: obs, obs_next, action are pairs of tensors (or None where the entry point
+    does not read them); reward, done: the columns of the agent whose target this is."""
+    b = QrCtdeTransitions()
+    b.obs, b.obs_next, b.action = _pair(obs), _pair(obs_next), _pair(action)
+    b.reward, b.done, b.index = ptr(reward), ptr(done), ptr(index)
+    b.batch, b.rows = int(batch), int(rows)
+    for m in range(2):
+        b.obs_dim[m], b.action_dim[m], b.row_stride[m], b.col_offset[m] = int(obs_dims[m]), int(action_dims[m]), int(row_strides[m]), int(col_offsets[m])
+    b.reward_stride, b.done_stride = int(reward_stride), int(done_stride)
+    return b
+
+
+def ctde_td3_target_args(*, eps, action_next, y, discount, target_noise, noise_clip, max_action) -> QrCtdeTd3Target:
+    """QrCtdeTd3Target of one qr_ctde_twinq_target launch; eps, action_next: pairs (or None)."""
+    return QrCtdeTd3Target(_pair(eps), _pair(action_next), ptr(y), float(discount), float(target_noise), float(noise_clip), float(max_action))
+
+
+def ctde_sac_target_args(*, eps, eps_logp, action_next, logp_next, alpha_dev, y, action_out, logp_out, discount, alpha, agent) -> QrCtdeSacTarget:
+    """QrCtdeSacTarget of one qr_ctde_sac_target launch; eps, action_next, action_out: pairs (or None)."""
+    return QrCtdeSacTarget(_pair(eps), ptr(eps_logp), _pair(action_next), ptr(logp_next), ptr(alpha_dev), ptr(y), _pair(action_out), ptr(logp_out),
+                           float(discount), float(alpha), int(agent), 0)
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -390,6 +438,14 @@ def load():
     lib.qr_sac_actor_grad.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrSacActorGrad), C.c_void_p]
     lib.qr_sac_actor_workspace_bytes.restype = C.c_int64
     lib.qr_sac_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_ctde_twinq_target.restype = C.c_int
+    lib.qr_ctde_twinq_target.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeTd3Target), C.c_void_p]
+    lib.qr_ctde_sac_target.restype = C.c_int
+    lib.qr_ctde_sac_target.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeSacTarget), C.c_void_p]
+    lib.qr_ctde_twinq_grad.restype = C.c_int
+    lib.qr_ctde_twinq_grad.argtypes = [P(QrQCritic), P(QrCtdeTransitions), P(QrTwinQGrad), C.c_void_p]
+    lib.qr_ctde_twinq_workspace_bytes.restype = C.c_int64
+    lib.qr_ctde_twinq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -368,15 +368,15 @@ __device__ __forceinline__ void mlp_grad_write(double* P, const MlpGradLayout& Y
 
 // What ppo_critic_kernel (qr_ppo_critic.h) and twinq_kernel (qr_td3.h) share: the tile walk.  One wavefront per workgroup; workgroup
 // row blockIdx.y owns ONE network and walks the minibatch's 64-row tiles grid-stride along x.  Per tile: gather the rows (index,
-// clamped into [0, rows)) through the LDS tile — each row is formed there from its two sources — then per half tile mlp_grad_half
+// clamped into [0, rows)) through the LDS tile — each row is formed there from its SRC sources — then per half tile mlp_grad_half
 // into the resident accumulators.  At the end the workgroup writes ONE partial vector, [blockIdx.y][blockIdx.x].
 // A Rule supplies what is the algorithm's own: Args (B, rows, index, hidden, g_scale and partials carry the same names in both), the
-// traits L1, SUMS statistics, the sizes W1S / SVEC of the LDS arrays behind layer 1's operands and the small vectors, SKIP_EMPTY
-// (a source of width 0 is not staged), and
-//   in0(a), in1(a), net(a)           the two sources' widths; the network of this workgroup row
+// traits L1, SUMS statistics, the sizes W1S / SVEC of the LDS arrays behind layer 1's operands and the small vectors, SRC (how many
+// sources a row has: two, or the four of a centralized critic, qr_td3.h), SKIP_EMPTY (a source of width 0 is not staged), and
+//   width(a, s), net(a)              the width of source s; the network of this workgroup row
 //   fill(w1s, svec, w, D, H, lane)   layer 1's operands and the small vectors, once per workgroup
 //   layer1(w1s)                      layer 1's operands as mlp_grad_half takes them, once per half tile
-//   row0(a, i), row1(a, i)           the two sources of storage row i
+//   row(a, i, s)                     source s of storage row i
 //   target(a, i, j), stat(st, e, y)  the target of storage row i at minibatch position j; the statistics of one active row
 template <class Rule>
 __device__ __forceinline__ void mlp_grad_walk(const typename Rule::Args& a) {
@@ -384,10 +384,13 @@ __device__ __forceinline__ void mlp_grad_walk(const typename Rule::Args& a) {
   __shared__ float xs[64 * kMgX];          // the input tile; at the end: the lanes' VALU sums
   __shared__ float ts[32 * kMgT], ds[32 * kMgT];
   __shared__ float w1s[Rule::W1S], svec[Rule::SVEC], ys[64];
-  __shared__ const float *src0[64], *src1[64];
+  __shared__ const float* src[Rule::SRC][64];
   __shared__ double red64[64 * Rule::SUMS];
   const int lane = threadIdx.x;
-  const int in0 = Rule::in0(a), in1 = Rule::in1(a), D = in0 + in1, H = a.hidden;
+  int in[Rule::SRC], D = 0;
+#pragma unroll
+  for (int s = 0; s < Rule::SRC; ++s) { in[s] = Rule::width(a, s); D += in[s]; }
+  const int H = a.hidden;
   const MlpNetW w = Rule::net(a);
   Rule rule;
   float a2[4][4][4], a2t[4][4][4];
@@ -407,13 +410,17 @@ __device__ __forceinline__ void mlp_grad_walk(const typename Rule::Args& a) {
       const bool active = row0 + lane < a.B;
       int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
       i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the storage
-      src0[lane] = active ? Rule::row0(a, i) : nullptr;
-      src1[lane] = active ? Rule::row1(a, i) : nullptr;
+#pragma unroll
+      for (int s = 0; s < Rule::SRC; ++s) src[s][lane] = active ? Rule::row(a, i, s) : nullptr;
       ys[lane] = active ? Rule::target(a, i, row0 + lane) : 0.0f;
     }
     __syncthreads();
-    if (!Rule::SKIP_EMPTY || in0) stage_rows(xs, kMgX, src0, in0, 0, lane);
-    if (!Rule::SKIP_EMPTY || in1) stage_rows(xs, kMgX, src1, in1, in0, lane);
+    int col = 0;
+#pragma unroll
+    for (int s = 0; s < Rule::SRC; ++s) {
+      if (!Rule::SKIP_EMPTY || in[s]) stage_rows(xs, kMgX, src[s], in[s], col, lane);
+      col += in[s];
+    }
     __syncthreads();
 
 #pragma unroll 1

@@ -52,15 +52,14 @@ struct PcRule {
   using Args = PpoCriticArgs;
   using L1 = PpoCriticL1;
   static constexpr int SUMS = kPcSums, W1S = 1, SVEC = kMgB3;
+  static constexpr int SRC = 2;
   static constexpr bool SKIP_EMPTY = true;
   L1 l1;
-  static __device__ __forceinline__ int in0(const Args& a) { return a.in0; }
-  static __device__ __forceinline__ int in1(const Args& a) { return a.in1; }
+  static __device__ __forceinline__ int width(const Args& a, int s) { return s ? a.in1 : a.in0; }
   static __device__ __forceinline__ const MlpNetW& net(const Args& a) { return a.w; }
   __device__ __forceinline__ void fill(float*, float* svec, const MlpNetW& w, int D, int H, int lane) { l1.load(w.fc1_w, D, H, lane); fill_vecs(svec, w, H, lane); }
   __device__ __forceinline__ const L1& layer1(const float*) const { return l1; }
-  static __device__ __forceinline__ const float* row0(const Args& a, int64_t i) { return a.rows0 + i * a.in0; }
-  static __device__ __forceinline__ const float* row1(const Args& a, int64_t i) { return a.rows1 + i * a.in1; }
+  static __device__ __forceinline__ const float* row(const Args& a, int64_t i, int s) { return s ? a.rows1 + i * a.in1 : a.rows0 + i * a.in0; }
   static __device__ __forceinline__ float target(const Args& a, int64_t i, int64_t) { return a.target[i * a.tgt_stride]; }
   static __device__ __forceinline__ void stat(double (&st)[SUMS], float e, float y) { st[0] += (double)e * (double)e; st[1] += (double)e; st[2] += (double)y; st[3] += (double)y * (double)y; }
 };

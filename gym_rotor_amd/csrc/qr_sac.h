@@ -24,21 +24,24 @@
 
 namespace qr {
 
+// Per-agent members are arrays of two, as Td3TargetArgs's (qr_td3.h): the one-agent entry fills [0]; the centralized (CTDE) entry
+// fills both.  There logp is agent `own`'s alone, from a draw of its own where eps_logp is given (sac.py:139-141 samples that agent twice).
 struct SacTargetArgs {
-  ActorW actor;                      // pi (AD > 0): the LIVE actor, mean head and log_std head; log_std is NULL: never read
+  ActorW actor[2];                   // pi (AD > 0): the LIVE actors, mean head and log_std head; log_std is NULL: never read
   MlpNetW net[2];                    // Q1_targ, Q2_targ
-  const float* obs_next;             // [>= rows][obs_dim]
+  const float* obs_next[2];          // [>= rows][obs_dim[m]]
   const float *reward, *done;        // element i at [i * rwd_stride] / [i * done_stride]
-  const float* eps;                  // [B][action_dim] by minibatch position, or NULL: zeros
-  const float* action_next;          // AD = 0: a' [B][action_dim] by minibatch position, used as it is
+  const float* eps[2];               // [B][action_dim[m]] by minibatch position, or NULL: zeros
+  const float* eps_logp;             // the centralized form: [B][action_dim[own]], or NULL: eps[own]
+  const float* action_next[2];       // AD = 0: a' [B][action_dim[m]] by minibatch position, used as it is
   const float* logp_next;            // AD = 0: logp [B] by minibatch position
   const float* alpha_dev;            // device scalar, or NULL: `alpha`
   const int64_t* index;
   float* y;                          // [B]
-  float* action_out;                 // [B][action_dim] or NULL
+  float* action_out[2];              // [B][action_dim[m]] or NULL
   float* logp_out;                   // [B] or NULL
   int64_t B, rows;
-  int32_t obs_dim, action_dim, hidden, rwd_stride, done_stride;
+  int32_t obs_dim[2], action_dim[2], hidden, rwd_stride, done_stride, own;
   float discount, alpha;
 };
 
@@ -60,15 +63,26 @@ struct SacRule {
   const Args& a;
   const float alpha;
   __device__ __forceinline__ explicit SacRule(const Args& args) : a(args), alpha(args.alpha_dev ? args.alpha_dev[0] : args.alpha) {}
-  __device__ __forceinline__ float component(float pre, float ls, int64_t k, bool active, float& logp) const {
-    const float z = (a.eps && active) ? a.eps[k] : 0.0f;
+  template <bool TWO>
+  __device__ __forceinline__ float component(int m, float pre, float ls, int64_t k, bool active, bool own, float& logp) const {
+    const float* eps = (TWO && m) ? a.eps[1] : a.eps[0];
+    const float z = (eps && active) ? eps[k] : 0.0f;
     float act, lp;
     sac_sample(pre, ls, z, act, lp);
-    logp += lp;
+    if constexpr (TWO) {
+      if (own && a.eps_logp) {  // the log-probability's own draw: the same function of (pre, ls, e), its action dropped
+        float other;
+        sac_sample(pre, ls, active ? a.eps_logp[k] : 0.0f, other, lp);
+      }
+      if (own) logp += lp;
+    } else {
+      logp += lp;
+    }
     return act;
   }
-  __device__ __forceinline__ void keep(int64_t k, float act, bool active) const {
-    if (a.action_out && active) a.action_out[k] = act;
+  __device__ __forceinline__ void keep(int m, int64_t k, float act, bool active) const {
+    float* out = m ? a.action_out[1] : a.action_out[0];
+    if (out && active) out[k] = act;
   }
   __device__ __forceinline__ float supplied(int64_t j, bool active) const { return active ? a.logp_next[j] : 0.0f; }
   __device__ __forceinline__ void bellman(int64_t j, float rwd, float dn, float qmin, float logp) const {
@@ -77,7 +91,7 @@ struct SacRule {
   }
 };
 
-template <int AD>
-__global__ __launch_bounds__(64) void sac_target_kernel(const SacTargetArgs a) { target_walk<AD, SacRule>(a); }
+template <int AD, int AD1 = -1>
+__global__ __launch_bounds__(64) void sac_target_kernel(const SacTargetArgs a) { target_walk<AD, SacRule, AD1>(a); }
 
 }  // namespace qr

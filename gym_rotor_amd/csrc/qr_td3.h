@@ -6,6 +6,8 @@
 //   twinq_kernel + twinq_reduce_kernel (qr_twinq_grad)   mse(Q1, y) + mse(Q2, y) and its gradients for the twelve tensors
 // The tile walk, the half-tile body, the partial vector and the reduction's sums are qr_mlp_grad.h's, shared with ppo_critic_kernel; here, as
 // TwinQL1 and TqRule: ReLU, 28 inputs with fc1_w's operands in LDS, rows from obs + action, y by minibatch position, two statistics, two networks.
+// The centralized (CTDE) critic of two agents (td3.py:124-137, 157-158; sac.py:136-144, 156-157) is the same code on rows from four
+// sources: ctde_twinq_kernel (qr_ctde_twinq_grad) and target_walk's two-agent forms (qr_ctde_twinq_target, qr_ctde_sac_target).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,19 +66,46 @@ struct TqRule {
   using Args = TwinQArgs;
   using L1 = TwinQL1;
   static constexpr int SUMS = kTqSums, W1S = TwinQL1::SIZE, SVEC = kTqVec;
+  static constexpr int SRC = 2;
   static constexpr bool SKIP_EMPTY = false;
-  static __device__ __forceinline__ int in0(const Args& a) { return a.obs_dim; }
-  static __device__ __forceinline__ int in1(const Args& a) { return a.action_dim; }
+  static __device__ __forceinline__ int width(const Args& a, int s) { return s ? a.action_dim : a.obs_dim; }
   static __device__ __forceinline__ const MlpNetW& net(const Args& a) { return blockIdx.y ? a.net[1] : a.net[0]; }
   __device__ __forceinline__ void fill(float* w1s, float* svec, const MlpNetW& w, int D, int H, int lane) { twinq_fill_small(w1s, svec, w, D, H, lane); }
   __device__ __forceinline__ L1 layer1(const float* w1s) const { return L1{lds_here(w1s)}; }
-  static __device__ __forceinline__ const float* row0(const Args& a, int64_t i) { return a.obs + i * a.obs_dim; }
-  static __device__ __forceinline__ const float* row1(const Args& a, int64_t i) { return a.action + i * a.act_stride; }
+  static __device__ __forceinline__ const float* row(const Args& a, int64_t i, int s) { return s ? a.action + i * a.act_stride : a.obs + i * a.obs_dim; }
   static __device__ __forceinline__ float target(const Args& a, int64_t, int64_t j) { return a.y[j]; }
   static __device__ __forceinline__ void stat(double (&st)[SUMS], float e, float y) { st[0] += (double)e * (double)e; st[1] += (double)y; }
 };
 
 __global__ __launch_bounds__(64) void twinq_kernel(const TwinQArgs a) { mlp_grad_walk<TqRule>(a); }
+
+// The centralized (CTDE) twin critic of two agents, MLP_Critic_CTDE (td3_mlp.py:102-168): the same regression on the row
+// [obs_0 | obs_1 | act_0 | act_1], formed in the walk's tile from its four sources (qr_ctde_twinq_grad).  Everything behind the
+// staging is TqRule's, so the partial vector and twinq_reduce_kernel serve as they are.
+struct CtdeTwinQArgs {
+  MlpNetW net[2];
+  const float* obs[2];               // [>= rows][obs_dim[m]]
+  const float* action[2];            // row i of agent m at action[m] + i * act_stride[m] (the column offset is already added)
+  const float* y;
+  const int64_t* index;
+  double* partials;
+  int64_t B, rows;
+  int32_t obs_dim[2], action_dim[2], act_stride[2], hidden;
+  float g_scale;
+};
+
+struct CtdeTqRule : TqRule {
+  using Args = CtdeTwinQArgs;
+  static constexpr int SRC = 4;
+  static __device__ __forceinline__ int width(const Args& a, int s) { return s < 2 ? a.obs_dim[s] : a.action_dim[s - 2]; }
+  static __device__ __forceinline__ const MlpNetW& net(const Args& a) { return blockIdx.y ? a.net[1] : a.net[0]; }
+  static __device__ __forceinline__ const float* row(const Args& a, int64_t i, int s) {
+    return s < 2 ? a.obs[s] + i * a.obs_dim[s] : a.action[s - 2] + i * a.act_stride[s - 2];
+  }
+  static __device__ __forceinline__ float target(const Args& a, int64_t, int64_t j) { return a.y[j]; }
+};
+
+__global__ __launch_bounds__(64) void ctde_twinq_kernel(const CtdeTwinQArgs a) { mlp_grad_walk<CtdeTqRule>(a); }
 
 struct TwinQReduceArgs {
   const double* partials;   // [2][n_parts][np]
@@ -114,19 +143,21 @@ __global__ __launch_bounds__(256) void twinq_reduce_kernel(const TwinQReduceArgs
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// qr_twinq_target
+// qr_twinq_target, qr_ctde_twinq_target
 // ------------------------------------------------------------------------------------------------------------------
+// Per-agent members are arrays of two: the one-agent entry fills [0] and its kernels never read [1]; the centralized (CTDE) entries
+// (quadrotor_kernels.hip) fill both, and `own` = the agent whose reward and done columns these are.
 struct Td3TargetArgs {
-  ActorW actor;                      // pi_targ (AD > 0); log_std and the log_std head are NULL: never read
+  ActorW actor[2];                   // pi_targ (AD > 0); log_std and the log_std head are NULL: never read
   MlpNetW net[2];                    // Q1_targ, Q2_targ
-  const float* obs_next;             // [>= rows][obs_dim]
+  const float* obs_next[2];          // [>= rows][obs_dim[m]]
   const float *reward, *done;        // element i at [i * rwd_stride] / [i * done_stride]
-  const float* eps;                  // [B][action_dim] by minibatch position, or NULL
-  const float* action_next;          // AD = 0: a' [B][action_dim] by minibatch position, used as it is
+  const float* eps[2];               // [B][action_dim[m]] by minibatch position, or NULL
+  const float* action_next[2];       // AD = 0: a' [B][action_dim[m]] by minibatch position, used as it is
   const int64_t* index;
   float* y;                          // [B]
   int64_t B, rows;
-  int32_t obs_dim, action_dim, hidden, rwd_stride, done_stride;
+  int32_t obs_dim[2], action_dim[2], hidden, rwd_stride, done_stride, own;
   float discount, target_noise, noise_clip, max_action;
 };
 
@@ -170,34 +201,45 @@ __device__ __forceinline__ float twinq_forward(const float (&a2)[4][4][4], const
 }
 
 // What td3_target_kernel and sac_target_kernel (qr_sac.h) share: the tile walk.  AD = the actor's obs_dim: 23 or 15 (ActorMfma,
-// hidden 16, 4 actions), 3 (ActorLds<3, 4, 1>), or 0: no actor, a' is supplied.  One wavefront per workgroup walks 64-row tiles
-// grid-stride: gather obs_next rows (index, clamped) into the critic's input tile and the actor's tile, the actor's heads for the
-// lane's own row, a' into the columns behind the observation, then both target networks over the tile and min.  Lane l owns row l.
+// hidden 16, 4 actions), 3 (ActorLds<3, 4, 1>), or 0: no actor, a' is supplied.  AD1 < 0: one agent.  AD1 >= 0: the centralized
+// (CTDE) critic of two agents, whose row is [obs_next_0 | obs_next_1 | a'_0 | a'_1] — AD = 15 with AD1 = 3, both Decoupled actors in
+// the one wave (agent 0's on the matrix cores with its weights resident, agent 1's from LDS), or AD = AD1 = 0, both a' supplied.
+// One wavefront per workgroup walks 64-row tiles grid-stride: gather obs_next rows (index, clamped) into the critic's input tile and
+// the actors' tiles, the actors' heads for the lane's own row, a' into the columns behind the observations, then both target
+// networks over the tile and min.  Lane l owns row l.
 // A Rule supplies what is the algorithm's own: Args (the fields read here carry the same names in both), LOG_STD (has the actor a
-// log_std head), and for minibatch position j, with `sum` what the rule adds up over a row (zero at the row's start):
-//   component(pre, ls, k, active, sum)  a' of one component from the heads' outputs; k = j * action_dim + f
-//   keep(k, act, active)                a' of one component is settled, computed or supplied
-//   supplied(j, active)                 `sum` of a row whose a' is supplied
-//   bellman(j, rwd, dn, qmin, sum)      y[j], for active rows only
-template <int AD, class Rule>
+// log_std head), and for minibatch position j, with `sum` what the rule adds up over a row (zero at the row's start), m the agent,
+// TWO = the centralized form and own = is m the agent whose row sum this is (always, with one agent):
+//   component<TWO>(m, pre, ls, k, active, own, sum)  a' of one component from the heads' outputs; k = j * action_dim[m] + f
+//   keep(m, k, act, active)                          a' of one component is settled, computed or supplied
+//   supplied(j, active)                              `sum` of a row whose a' is supplied
+//   bellman(j, rwd, dn, qmin, sum)                   y[j], for active rows only
+template <int AD, class Rule, int AD1 = -1>
 __device__ __forceinline__ void target_walk(const typename Rule::Args& a) {
+  constexpr bool TWO = AD1 >= 0;
+  static_assert(!TWO || (AD == 15 && AD1 == 3) || (AD == 0 && AD1 == 0), "the centralized form: both Decoupled actors or none");
   constexpr int AA = AD == 3 ? 1 : 4;  // the actor's action_dim
   using Actor1 = ActorLds<3, 4, 1>;
+  constexpr bool LDS_ACTOR = AD == 3 || AD1 == 3;
   __shared__ float xs[64 * kMgX];
   __shared__ float as[AD > 0 ? 64 * AD : 4];
-  __shared__ __attribute__((aligned(16))) float wsm[AD == 3 ? Actor1::SIZE : 4];
+  __shared__ float as1[AD1 > 0 ? 64 * AD1 : 4];
+  __shared__ __attribute__((aligned(16))) float wsm[LDS_ACTOR ? Actor1::SIZE : 4];
   __shared__ float w1s[2][TwinQL1::SIZE], svec[2][kTqVec];
   __shared__ const float* src0[64];
+  __shared__ const float* src1[TWO ? 64 : 1];
   const int lane = threadIdx.x;
-  const int D = a.obs_dim + a.action_dim, H = a.hidden;
+  const int od1 = TWO ? a.obs_dim[1] : 0, ad1 = TWO ? a.action_dim[1] : 0;
+  const int OD = a.obs_dim[0] + od1;  // the observations' columns; a' behind them
+  const int D = OD + a.action_dim[0] + ad1, H = a.hidden;
   float q1[4][4][4], q2[4][4][4];  // fc2_w of Q1_targ, Q2_targ
   load_fc2(q1, a.net[0].fc2_w, H, lane);
   load_fc2(q2, a.net[1].fc2_w, H, lane);
   twinq_fill_small(w1s[0], svec[0], a.net[0], D, H, lane);
   twinq_fill_small(w1s[1], svec[1], a.net[1], D, H, lane);
   ActorMfma<(AD == 23 || AD == 15) ? AD : 23, Rule::LOG_STD> actor;
-  if constexpr (AD == 23 || AD == 15) actor.load(a.actor, lane);
-  if constexpr (AD == 3) Actor1::fill(wsm, a.actor, lane);
+  if constexpr (AD == 23 || AD == 15) actor.load(a.actor[0], lane);
+  if constexpr (LDS_ACTOR) Actor1::fill(wsm, a.actor[AD == 3 ? 0 : 1], lane);
   const Rule rule(a);
   for (int i = lane; i < 64 * kMgX; i += 64) xs[i] = 0.0f;  // the padding columns stay zero: nothing below writes them
   __syncthreads();
@@ -208,15 +250,19 @@ __device__ __forceinline__ void target_walk(const typename Rule::Args& a) {
     const bool active = j < a.B;
     int64_t i = active ? (a.index ? a.index[j] : j) : 0;
     i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
-    src0[lane] = active ? a.obs_next + i * a.obs_dim : nullptr;
+    src0[lane] = active ? a.obs_next[0] + i * a.obs_dim[0] : nullptr;
+    if constexpr (TWO) src1[lane] = active ? a.obs_next[1] + i * od1 : nullptr;
     const float rwd = active ? a.reward[i * a.rwd_stride] : 0.0f;
     const float dn = active ? a.done[i * a.done_stride] : 0.0f;
     __syncthreads();
-    stage_rows(xs, kMgX, src0, a.obs_dim, 0, lane);
+    stage_rows(xs, kMgX, src0, a.obs_dim[0], 0, lane);
+    if constexpr (TWO) stage_rows(xs, kMgX, src1, od1, a.obs_dim[0], lane);
     if constexpr (AD > 0) stage_rows(as, AD, src0, AD, 0, lane);
+    if constexpr (AD1 > 0) stage_rows(as1, AD1, src1, AD1, 0, lane);
     __syncthreads();
     float sum = 0.0f;
     if constexpr (AD > 0) {
+      const int acol = TWO ? OD : AD;
       float pre[AA], ls[AA];
       if constexpr (AD == 3) {
         float x[3];
@@ -226,17 +272,33 @@ __device__ __forceinline__ void target_walk(const typename Rule::Args& a) {
       } else {
         actor.heads(as, lane, pre, ls);
       }
+      const bool own0 = !TWO || a.own == 0;
 #pragma unroll
       for (int f = 0; f < AA; ++f) {
-        const float act = rule.component(pre[f], ls[f], j * AA + f, active, sum);
-        xs[lane * kMgX + AD + f] = act;
-        rule.keep(j * AA + f, act, active);
+        const float act = rule.template component<TWO>(0, pre[f], ls[f], j * AA + f, active, own0, sum);
+        xs[lane * kMgX + acol + f] = act;
+        rule.keep(0, j * AA + f, act, active);
+      }
+      if constexpr (AD1 == 3) {
+        float x[3], pre1[1], ls1[1];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[k] = as1[lane * 3 + k];
+        Actor1::heads(wsm, Rule::LOG_STD, x, pre1, ls1);
+        const float act = rule.template component<TWO>(1, pre1[0], ls1[0], j, active, a.own == 1, sum);
+        xs[lane * kMgX + acol + AA] = act;
+        rule.keep(1, j, act, active);
       }
     } else {
-      for (int f = 0; f < a.action_dim; ++f) {
-        const float act = active ? a.action_next[j * a.action_dim + f] : 0.0f;
-        xs[lane * kMgX + a.obs_dim + f] = act;
-        rule.keep(j * a.action_dim + f, act, active);
+      int col = OD;
+#pragma unroll
+      for (int m = 0; m < (TWO ? 2 : 1); ++m) {
+        const int w = a.action_dim[m];
+        for (int f = 0; f < w; ++f) {
+          const float act = active ? a.action_next[m][j * w + f] : 0.0f;
+          xs[lane * kMgX + col + f] = act;
+          rule.keep(m, j * w + f, act, active);
+        }
+        col += w;
       }
       sum = rule.supplied(j, active);
     }
@@ -254,19 +316,21 @@ struct Td3Rule {
   static constexpr bool LOG_STD = false;
   const Args& a;
   __device__ __forceinline__ explicit Td3Rule(const Args& args) : a(args) {}
-  __device__ __forceinline__ float component(float pre, float, int64_t k, bool active, float&) const {
+  template <bool TWO>
+  __device__ __forceinline__ float component(int m, float pre, float, int64_t k, bool active, bool, float&) const {
+    const float* eps = (TWO && m) ? a.eps[1] : a.eps[0];
     float n = 0.0f;
-    if (a.eps && active) n = fminf(fmaxf(a.target_noise * a.eps[k], -a.noise_clip), a.noise_clip);
+    if (eps && active) n = fminf(fmaxf(a.target_noise * eps[k], -a.noise_clip), a.noise_clip);
     return fminf(fmaxf(tanh_fast(pre) + n, -a.max_action), a.max_action);
   }
-  __device__ __forceinline__ void keep(int64_t, float, bool) const {}
+  __device__ __forceinline__ void keep(int, int64_t, float, bool) const {}
   __device__ __forceinline__ float supplied(int64_t, bool) const { return 0.0f; }
   __device__ __forceinline__ void bellman(int64_t j, float rwd, float dn, float qmin, float) const {
     a.y[j] = fmaf(a.discount * (1.0f - dn), qmin, rwd);
   }
 };
 
-template <int AD>
-__global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) { target_walk<AD, Td3Rule>(a); }
+template <int AD, int AD1 = -1>
+__global__ __launch_bounds__(64) void td3_target_kernel(const Td3TargetArgs a) { target_walk<AD, Td3Rule, AD1>(a); }
 
 }  // namespace qr

@@ -47,13 +47,14 @@
 //   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): mlp_grad_walk, the gradient kernels' shared tile walk; the half-tile gradient body, the partial vector, the reduction's sums
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
-//   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk
+//   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk;
+//                  the centralized (CTDE) critic of two agents (qr_ctde_twinq_target, qr_ctde_sac_target, qr_ctde_twinq_grad): the walks' two-agent forms, ctde_twinq_kernel
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad),
-//                  mlp_grad_launch (qr_ppo_critic_grad and qr_twinq_grad) and target_launch (qr_twinq_target and qr_sac_target)
+//                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad) and target_launch (the four target entries)
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -256,6 +257,8 @@ static int do_ppo_critic(const QrCritic* c, const QrCriticBatch* b, const QrCrit
                          ppo_critic_kernel, ppo_critic_reduce_kernel, stream);
 }
 
+static bool nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
+
 static bool twinq_sizes_ok(int64_t obs_dim, int64_t action_dim, int64_t hidden) {
   return obs_dim >= 1 && action_dim >= 1 && obs_dim + action_dim <= TwinQL1::XS && hidden >= 1 && hidden <= 64;
 }
@@ -272,62 +275,134 @@ static void twinq_nets(MlpNetW (&n)[2], const QrQCritic* c) {
   n[1] = MlpNetW{c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b};
 }
 
-// What qr_twinq_target and qr_sac_target check, fill and launch alike; c, b and the caller's own struct are not NULL.  The caller has
-// filled its own fields of `a` and says: the actor form it takes (squash, log_std: with the log_std head), whether its scalars are
-// in range, whether what the no-actor form reads is there, its own float pointers, and its kernels for AD = 23, 15, 3, 0.
+// The rows a target launch reads, from a QrTransitions (one agent: `two` false, [1] unused) or a QrCtdeTransitions.
+struct TargetRows {
+  const float* obs_next[2];
+  const float *reward, *done;
+  const int64_t* index;
+  int64_t batch, rows;
+  int32_t obs_dim[2], action_dim[2], reward_stride, done_stride;
+  bool two;
+};
+static TargetRows target_rows(const QrQCritic* c, const QrTransitions* b) {
+  return TargetRows{{b->obs_next, nullptr}, b->reward, b->done, b->index, b->batch, b->rows, {c->obs_dim, 0}, {c->action_dim, 0},
+                    b->reward_stride, b->done_stride, false};
+}
+static TargetRows target_rows(const QrCtdeTransitions* b) {
+  return TargetRows{{b->obs_next[0], b->obs_next[1]}, b->reward, b->done, b->index, b->batch, b->rows, {b->obs_dim[0], b->obs_dim[1]},
+                    {b->action_dim[0], b->action_dim[1]}, b->reward_stride, b->done_stride, true};
+}
+// the four widths of a centralized critic's row: each >= 1, adding up to the critic's
+static bool ctde_widths_ok(const QrQCritic* c, const int32_t (&od)[2], const int32_t (&ad)[2]) {
+  return od[0] >= 1 && od[1] >= 1 && ad[0] >= 1 && ad[1] >= 1 && (int64_t)od[0] + od[1] == c->obs_dim && (int64_t)ad[0] + ad[1] == c->action_dim;
+}
+
+// What the four target entries check, fill and launch alike; c and the caller's own structs are not NULL.  p: the actor(s), both
+// or neither in the centralized form.  The caller has filled its own fields of `a` and says: the actor form it takes (squash, log_std:
+// with the log_std head), whether its scalars are in range, whether what the no-actor form reads is there, its own float pointers,
+// and its kernels for AD = 23, 15, 3, 0 and the centralized form with both Decoupled actors and with none.
 template <class Args>
-static int target_launch(const QrActor* p, const QrQCritic* c, const QrTransitions* b, Args& a, int32_t squash, bool log_std, bool scalars_ok,
-                         bool supplied_ok, std::initializer_list<const void*> own, void (*const kernel[4])(Args), void* stream) {
-  if (p && (p->squash != squash || (log_std ? !p->log_std_w || !p->log_std_b : p->log_std_w || p->log_std_b))) return QR_E_KIND;
+static int target_launch(const QrActor* const (&p)[2], const QrQCritic* c, const TargetRows& b, Args& a, int32_t squash, bool log_std,
+                         bool scalars_ok, bool supplied_ok, std::initializer_list<const void*> own, void (*const kernel[6])(Args), void* stream) {
+  const int n = b.two ? 2 : 1;
+  for (int m = 0; m < n; ++m)
+    if (p[m] && (p[m]->squash != squash || (log_std ? !p[m]->log_std_w || !p[m]->log_std_b : p[m]->log_std_w || p[m]->log_std_b))) return QR_E_KIND;
   if (int rc = twinq_critic_check(c); rc == QR_E_SIZE) return rc;
-  if (p && (actor_size(p->obs_dim, p->hidden_dim, p->action_dim) < 0 || p->obs_dim != c->obs_dim || p->action_dim != c->action_dim)) return QR_E_SIZE;
-  if (b->batch < 1 || b->rows < 1 || b->reward_stride < 1 || b->done_stride < 1) return QR_E_SIZE;
+  if (b.two) {
+    if (!ctde_widths_ok(c, b.obs_dim, b.action_dim)) return QR_E_SIZE;
+    if (p[0] && (actor_size(p[0]->obs_dim, p[0]->hidden_dim, p[0]->action_dim) != 1 || b.obs_dim[0] != 15 || b.action_dim[0] != 4)) return QR_E_SIZE;
+    if (p[1] && (actor_size(p[1]->obs_dim, p[1]->hidden_dim, p[1]->action_dim) != 2 || b.obs_dim[1] != 3 || b.action_dim[1] != 1)) return QR_E_SIZE;
+  } else if (p[0] && (actor_size(p[0]->obs_dim, p[0]->hidden_dim, p[0]->action_dim) < 0 || p[0]->obs_dim != c->obs_dim || p[0]->action_dim != c->action_dim)) {
+    return QR_E_SIZE;
+  }
+  if (b.batch < 1 || b.rows < 1 || b.reward_stride < 1 || b.done_stride < 1) return QR_E_SIZE;
   if (!scalars_ok) return QR_E_SIZE;
   if (int rc = twinq_critic_check(c)) return rc;
-  if (p && (!p->fc1_w || !p->fc1_b || !p->fc2_w || !p->fc2_b || !p->mean_w || !p->mean_b)) return QR_E_NULL;
-  if (!b->obs_next || !b->reward || !b->done || !a.y || (!p && !supplied_ok)) return QR_E_NULL;
+  if (b.two && !p[0] != !p[1]) return QR_E_NULL;
+  for (int m = 0; m < n; ++m)
+    if (p[m] && (!p[m]->fc1_w || !p[m]->fc1_b || !p[m]->fc2_w || !p[m]->fc2_b || !p[m]->mean_w || !p[m]->mean_b)) return QR_E_NULL;
+  if (!b.obs_next[0] || (b.two && !b.obs_next[1]) || !b.reward || !b.done || !a.y || (!p[0] && !supplied_ok)) return QR_E_NULL;
   const void* const floats[] = {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w,
-                                c->fc6_b, b->obs_next, b->reward, b->done, p ? p->fc1_w : nullptr, p ? p->fc1_b : nullptr,
-                                p ? p->fc2_w : nullptr, p ? p->fc2_b : nullptr, p ? p->mean_w : nullptr, p ? p->mean_b : nullptr,
-                                p ? p->log_std_w : nullptr, p ? p->log_std_b : nullptr};
+                                c->fc6_b, b.obs_next[0], b.obs_next[1], b.reward, b.done};
   for (const void* q : floats)
     if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (int m = 0; m < n; ++m) {
+    if (!p[m]) continue;
+    const void* const w[] = {p[m]->fc1_w, p[m]->fc1_b, p[m]->fc2_w, p[m]->fc2_b, p[m]->mean_w, p[m]->mean_b, p[m]->log_std_w, p[m]->log_std_b};
+    for (const void* q : w)
+      if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  }
   for (const void* q : own)
     if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  if (reinterpret_cast<uintptr_t>(b->index) & 7u) return QR_E_ALIGN;
+  if (reinterpret_cast<uintptr_t>(b.index) & 7u) return QR_E_ALIGN;
 
-  if (p) a.actor = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, nullptr, p->log_std_w, p->log_std_b, squash};
+  for (int m = 0; m < n; ++m) {
+    if (p[m]) a.actor[m] = ActorW{p[m]->fc1_w, p[m]->fc1_b, p[m]->fc2_w, p[m]->fc2_b, p[m]->mean_w, p[m]->mean_b, nullptr, p[m]->log_std_w, p[m]->log_std_b, squash};
+    a.obs_next[m] = b.obs_next[m]; a.obs_dim[m] = b.obs_dim[m]; a.action_dim[m] = b.action_dim[m];
+  }
   twinq_nets(a.net, c);
-  a.obs_next = b->obs_next; a.reward = b->reward; a.done = b->done; a.index = b->index; a.B = b->batch; a.rows = b->rows;
-  a.obs_dim = c->obs_dim; a.action_dim = c->action_dim; a.hidden = c->hidden_dim; a.rwd_stride = b->reward_stride; a.done_stride = b->done_stride;
+  a.reward = b.reward; a.done = b.done; a.index = b.index; a.B = b.batch; a.rows = b.rows;
+  a.hidden = c->hidden_dim; a.rwd_stride = b.reward_stride; a.done_stride = b.done_stride;
   // grid-stride over the tiles: at most the waves resident at once, one per SIMD at the kernels' register count
-  const int64_t tiles = (b->batch + 63) / 64;
+  const int64_t tiles = (b.batch + 63) / 64;
   const dim3 grid((unsigned)(tiles < 1024 ? tiles : 1024));
-  const int ad = p ? p->obs_dim : 0;
-  hipLaunchKernelGGL(kernel[ad == 23 ? 0 : ad == 15 ? 1 : ad == 3 ? 2 : 3], grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+  const int ad = p[0] ? p[0]->obs_dim : 0;
+  const int which = b.two ? (p[0] ? 4 : 5) : ad == 23 ? 0 : ad == 15 ? 1 : ad == 3 ? 2 : 3;
+  hipLaunchKernelGGL(kernel[which], grid, dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
+
+static bool td3_scalars_ok(float noise_clip, float max_action) { return nonneg_finite(noise_clip) && nonneg_finite(max_action); }
+static void (*const kTd3TargetKernel[6])(Td3TargetArgs) = {td3_target_kernel<23>, td3_target_kernel<15>, td3_target_kernel<3>, td3_target_kernel<0>,
+                                                           td3_target_kernel<15, 3>, td3_target_kernel<0, 0>};
+static void (*const kSacTargetKernel[6])(SacTargetArgs) = {sac_target_kernel<23>, sac_target_kernel<15>, sac_target_kernel<3>, sac_target_kernel<0>,
+                                                           sac_target_kernel<15, 3>, sac_target_kernel<0, 0>};
 
 static int do_td3_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrTd3Target* t, void* stream) {
   if (!c || !b || !t) return QR_E_NULL;
   Td3TargetArgs a{};
-  a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next; a.y = t->y;
+  a.eps[0] = p ? t->eps : nullptr; a.action_next[0] = p ? nullptr : t->action_next; a.y = t->y;
   a.discount = t->discount; a.target_noise = t->target_noise; a.noise_clip = t->noise_clip; a.max_action = t->max_action;
-  const bool scalars_ok = t->noise_clip >= 0.0f && t->max_action >= 0.0f && t->noise_clip <= 3.0e38f && t->max_action <= 3.0e38f;
-  static void (*const kernel[4])(Td3TargetArgs) = {td3_target_kernel<23>, td3_target_kernel<15>, td3_target_kernel<3>, td3_target_kernel<0>};
-  return target_launch(p, c, b, a, QR_ACTOR_TANH_MEAN, false, scalars_ok, t->action_next != nullptr, {t->eps, t->action_next, t->y}, kernel, stream);
+  return target_launch({p, nullptr}, c, target_rows(c, b), a, QR_ACTOR_TANH_MEAN, false, td3_scalars_ok(t->noise_clip, t->max_action),
+                       t->action_next != nullptr, {t->eps, t->action_next, t->y}, kTd3TargetKernel, stream);
+}
+
+static int do_ctde_td3_target(const QrActor* p0, const QrActor* p1, const QrQCritic* c, const QrCtdeTransitions* b, const QrCtdeTd3Target* t, void* stream) {
+  if (!c || !b || !t) return QR_E_NULL;
+  const bool actors = p0 || p1;
+  Td3TargetArgs a{};
+  for (int m = 0; m < 2; ++m) { a.eps[m] = actors ? t->eps[m] : nullptr; a.action_next[m] = actors ? nullptr : t->action_next[m]; }
+  a.y = t->y; a.discount = t->discount; a.target_noise = t->target_noise; a.noise_clip = t->noise_clip; a.max_action = t->max_action;
+  return target_launch({p0, p1}, c, target_rows(b), a, QR_ACTOR_TANH_MEAN, false, td3_scalars_ok(t->noise_clip, t->max_action),
+                       t->action_next[0] && t->action_next[1], {t->eps[0], t->eps[1], t->action_next[0], t->action_next[1], t->y},
+                       kTd3TargetKernel, stream);
 }
 
 static int do_sac_target(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrSacTarget* t, void* stream) {
   if (!c || !b || !t) return QR_E_NULL;
   SacTargetArgs a{};
-  a.eps = p ? t->eps : nullptr; a.action_next = p ? nullptr : t->action_next; a.logp_next = p ? nullptr : t->logp_next;
-  a.alpha_dev = t->alpha_dev; a.y = t->y; a.action_out = t->action_out; a.logp_out = t->logp_out;
+  a.eps[0] = p ? t->eps : nullptr; a.action_next[0] = p ? nullptr : t->action_next; a.logp_next = p ? nullptr : t->logp_next;
+  a.alpha_dev = t->alpha_dev; a.y = t->y; a.action_out[0] = t->action_out; a.logp_out = t->logp_out;
   a.discount = t->discount; a.alpha = t->alpha;
-  const bool scalars_ok = t->discount >= 0.0f && t->alpha >= 0.0f && t->discount <= 3.0e38f && t->alpha <= 3.0e38f;
-  static void (*const kernel[4])(SacTargetArgs) = {sac_target_kernel<23>, sac_target_kernel<15>, sac_target_kernel<3>, sac_target_kernel<0>};
-  return target_launch(p, c, b, a, QR_ACTOR_TANH_SAMPLE, true, scalars_ok, t->action_next && t->logp_next,
-                       {t->eps, t->action_next, t->logp_next, t->alpha_dev, t->y, t->action_out, t->logp_out}, kernel, stream);
+  return target_launch({p, nullptr}, c, target_rows(c, b), a, QR_ACTOR_TANH_SAMPLE, true, nonneg_finite(t->discount) && nonneg_finite(t->alpha),
+                       t->action_next && t->logp_next, {t->eps, t->action_next, t->logp_next, t->alpha_dev, t->y, t->action_out, t->logp_out},
+                       kSacTargetKernel, stream);
+}
+
+static int do_ctde_sac_target(const QrActor* p0, const QrActor* p1, const QrQCritic* c, const QrCtdeTransitions* b, const QrCtdeSacTarget* t, void* stream) {
+  if (!c || !b || !t) return QR_E_NULL;
+  const bool actors = p0 || p1;
+  SacTargetArgs a{};
+  for (int m = 0; m < 2; ++m) {
+    a.eps[m] = actors ? t->eps[m] : nullptr; a.action_next[m] = actors ? nullptr : t->action_next[m]; a.action_out[m] = t->action_out[m];
+  }
+  a.eps_logp = actors ? t->eps_logp : nullptr; a.logp_next = actors ? nullptr : t->logp_next;
+  a.alpha_dev = t->alpha_dev; a.y = t->y; a.logp_out = t->logp_out; a.discount = t->discount; a.alpha = t->alpha; a.own = t->agent;
+  const bool scalars_ok = nonneg_finite(t->discount) && nonneg_finite(t->alpha) && (t->agent == 0 || t->agent == 1) && t->reserved0 == 0;
+  return target_launch({p0, p1}, c, target_rows(b), a, QR_ACTOR_TANH_SAMPLE, true, scalars_ok,
+                       t->action_next[0] && t->action_next[1] && t->logp_next,
+                       {t->eps[0], t->eps[1], t->eps_logp, t->action_next[0], t->action_next[1], t->logp_next, t->alpha_dev, t->y, t->action_out[0],
+                        t->action_out[1], t->logp_out}, kSacTargetKernel, stream);
 }
 
 static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGrad* g, void* stream) {
@@ -352,7 +427,33 @@ static int do_twinq(const QrQCritic* c, const QrTransitions* b, const QrTwinQGra
                          twinq_kernel, twinq_reduce_kernel, stream);
 }
 
-static bool nonneg_finite(float v) { return v >= 0.0f && v <= 3.0e38f; }
+// qr_twinq_grad's checks, launcher, grid and reduction; the kernel's rule stages four sources.
+static int do_ctde_twinq(const QrQCritic* c, const QrCtdeTransitions* b, const QrTwinQGrad* g, void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  const int critic = twinq_critic_check(c);
+  bool sizes_ok = critic != QR_E_SIZE && ctde_widths_ok(c, b->obs_dim, b->action_dim) && b->batch >= 1 && b->rows >= 1 && g->max_workgroups >= 0 &&
+                  g->reserved0 == 0;
+  for (int m = 0; m < 2; ++m)
+    sizes_ok = sizes_ok && b->row_stride[m] >= 1 && b->col_offset[m] >= 0 && (int64_t)b->col_offset[m] + b->action_dim[m] <= b->row_stride[m];
+  const bool supplied_ok = critic == 0 && g->stats && g->y && g->workspace && b->obs[0] && b->obs[1] && b->action[0] && b->action[1];
+  CtdeTwinQArgs a{};
+  twinq_nets(a.net, c);
+  for (int m = 0; m < 2; ++m) {
+    const int64_t col = sizes_ok && supplied_ok ? b->col_offset[m] : 0;  // (no arithmetic on what the checks refuse)
+    a.obs[m] = b->obs[m]; a.action[m] = b->action[m] + col;
+    a.obs_dim[m] = b->obs_dim[m]; a.action_dim[m] = b->action_dim[m]; a.act_stride[m] = b->row_stride[m];
+  }
+  a.y = g->y; a.index = b->index; a.partials = static_cast<double*>(g->workspace); a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim;
+  TwinQReduceArgs r{};
+  float* const grads[12] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->fc3_w, g->fc3_b, g->fc4_w, g->fc4_b, g->fc5_w, g->fc5_b, g->fc6_w, g->fc6_b};
+  for (int k = 0; k < 12; ++k) r.grad[k / 6][k % 6] = grads[k];
+  r.stats = g->stats;
+  return mlp_grad_launch(a, r, sizes_ok, supplied_ok,
+                         {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b,
+                          g->stats, g->y, b->obs[0], b->obs[1], b->action[0], b->action[1]}, grads,
+                         c->obs_dim, c->action_dim, c->hidden_dim, kTqSums, twinq_grid, 2, g->workspace_bytes, g->max_workgroups,
+                         ctde_twinq_kernel, twinq_reduce_kernel, stream);
+}
 
 // (the grid of qr_dpg_actor_grad is ppo_grid's: one wave per SIMD at the kernel's register count, 256 CUs x 4)
 static int do_dpg_actor(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrDpgGrad* g, void* stream) {
@@ -502,6 +603,25 @@ int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target,
 
 int qr_twinq_grad(const QrQCritic* critic, const QrTransitions* batch, const QrTwinQGrad* grad, void* stream) {
   return qr::do_twinq(critic, batch, grad, stream);
+}
+
+int qr_ctde_twinq_target(const QrActor* actor_target_0, const QrActor* actor_target_1, const QrQCritic* critic_target,
+                         const QrCtdeTransitions* batch, const QrCtdeTd3Target* target, void* stream) {
+  return qr::do_ctde_td3_target(actor_target_0, actor_target_1, critic_target, batch, target, stream);
+}
+
+int qr_ctde_sac_target(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic_target, const QrCtdeTransitions* batch,
+                       const QrCtdeSacTarget* target, void* stream) {
+  return qr::do_ctde_sac_target(actor_0, actor_1, critic_target, batch, target, stream);
+}
+
+int qr_ctde_twinq_grad(const QrQCritic* critic, const QrCtdeTransitions* batch, const QrTwinQGrad* grad, void* stream) {
+  return qr::do_ctde_twinq(critic, batch, grad, stream);
+}
+
+int64_t qr_ctde_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {
+  if (in_dim < 4) return QR_E_SIZE;
+  return qr_twinq_workspace_bytes(in_dim, hidden_dim, batch, max_workgroups);
 }
 
 int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups) {

@@ -10,6 +10,9 @@ The actor half (`sac_actor_grad`: qr_sac_actor_grad; on live modules `sac_actor_
 algos/policy_regularization.py): the index clones, four `actor.sample` passes, two critic passes, min, the three smoothness terms and
 autograd through all of it — and leaves d alpha_loss / d log_alpha beside the gradients.  The optimiser steps stay the caller's: no
 updater class is built here.
+
+The critic half also exists for ONE centralized (CTDE) twin critic over the two agents of a Decoupled buffer (sac.py:136-144, 156-157):
+`sac_target_ctde` (qr_ctde_sac_target) and, on live modules, `sac_critic_loss_ctde`; the regression is `td3.twinq_grad_ctde`.
 """
 from __future__ import annotations
 
@@ -21,7 +24,8 @@ import torch
 
 from . import _lib
 from .policy import ActorParams, QCriticParams, _grad_outputs, _vector
-from .td3 import ReplayBuffer, _check_actor, _check_index, _critic_update_state, _rows, _target, twinq_grad
+from .td3 import (ReplayBuffer, _check_actor, _check_index, _critic_update_state, _pair_of, _rows, _target, _target_ctde, twinq_grad,
+                  twinq_grad_ctde)
 
 
 def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
@@ -85,6 +89,69 @@ def sac_critic_loss(critic_module, critic_target_module, actor_module, buffer: R
                discount=discount, alpha=alpha, noise=noise, out=y)
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
                           workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def sac_target_ctde(actors, critic_target: QCriticParams, buffer_or_tensors, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                    discount: float = 0.99, alpha: Union[float, torch.Tensor] = 0.2, noise=None, noise_logp: Optional[torch.Tensor] = None,
+                    action_next=None, logp_next: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, action_out=None,
+                    logp_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """SAC's target values for the centralized (CTDE) twin critic of two agents in one launch (qr_ctde_sac_target; sac.py:136-153), j the
+    minibatch position, i = index[j], m = 0, 1:
+        mean_m, ls_m = actors[m](obs_next_m[i]);  ls_m = clamp(ls_m, -20, 2);  a'_m = tanh(mean_m + exp(ls_m) * noise[m][j])
+        logp_j = sum_f [ -e^2 / 2 - ls_k - log sqrt(2 pi) - log(1 - tanh(mean_k + exp(ls_k) e)^2 + 1e-6) ],  e = noise_logp[j]
+        y[j] = rwd_k[i] + discount * (1 - done_k[i]) * (min(Q1, Q2)([obs_next_0[i] | obs_next_1[i] | a'_0 | a'_1]) - alpha * logp_j)
+    The reference samples agent k a second time for the log-probability: noise_logp [B, A_k] is that draw; None: noise[k], one sample
+    (the same tensor for both gives the same bits).  actors: the pair of `ActorParams.from_sac_module` — the LIVE actors — of the sizes
+    (15,16,4) and (3,4,1), or None with action_next = (a'_0, a'_1) and logp_next [B] used as they are, for any widths whose sum the
+    critic reads.  critic_target, buffer_or_tensors, noise, index, out: `td3.td3_target_ctde`'s; alpha: `sac_target`'s.  action_out: a
+    pair of optional outputs [B, A_m]; logp_out [B]: optional."""
+    what = "sac_target_ctde"
+
+    def own(B, ad, dev, supplied):
+        outs = _pair_of(what, "action_out", action_out, B, ad, dev)
+        x = noise_logp
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, ad[k]) or not x.is_contiguous()):
+            raise ValueError(f"{what}: noise_logp must be a contiguous float32 [{B}, {ad[k]}] tensor on {dev}")
+        for name, x in (("logp_next", logp_next), ("logp_out", logp_out)):
+            if x is not None and (x.dtype != torch.float32 or x.device != dev or x.numel() != B or not x.is_contiguous()):
+                raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}] tensor on {dev}")
+        if supplied and logp_next is None:
+            raise ValueError(f"{what}: without actors, logp_next [B] is required")
+        a, alpha_dev = alpha, None
+        if isinstance(a, torch.Tensor):
+            if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
+                raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
+            alpha_dev, a = a, 0.0
+        elif not 0.0 <= float(a) < float("inf"):
+            raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
+        if not 0.0 <= float(discount) < float("inf"):
+            raise ValueError(f"{what}: discount must be finite and >= 0, got {discount}")
+        return dict(eps_logp=noise_logp, logp_next=logp_next, alpha_dev=alpha_dev, action_out=outs, logp_out=logp_out, discount=discount, alpha=a,
+                    agent=k)
+
+    return _target_ctde(what, "qr_ctde_sac_target", _lib.ctde_sac_target_args, actors,
+                        (_lib.ACTOR_TANH_SAMPLE, True, "the actors must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head"),
+                        critic_target, buffer_or_tensors, k, index, noise, action_next, out, own)
+
+
+def sac_critic_loss_ctde(critic_module, critic_target_module, actor_modules, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                         discount: float = 0.99, alpha: Union[float, torch.Tensor] = 0.2, noise=None, noise_logp: Optional[torch.Tensor] = None,
+                         stats: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """`sac_critic_loss` for the centralized (CTDE) critic of a two-agent `buffer`, for agent k's reward and done: `sac_target_ctde` on
+    the two LIVE `actor_modules` and the target critic, then `td3.twinq_grad_ctde` on the live `critic_module` (MLP_Critic_CTDE:
+    fc1 .. fc6 over [obs_0 | obs_1 | act_0 | act_1]); fills `critic_module.fc{1..6}.{weight,bias}.grad` in place.  noise: the pair of
+    rsample draws, noise_logp: the draw of the reference's second sample of agent k (None: noise[k]).  Returns stats (stats[0] = the
+    loss).  y, the workspace and stats are cached on the buffer under a key of their own: from the second call on with an unchanged B
+    nothing is allocated.  The optimiser step stays the caller's."""
+    if not isinstance(buffer, ReplayBuffer):
+        raise ValueError("sac_critic_loss_ctde: buffer must be a ReplayBuffer")
+    A = sum(buffer.action_dims)
+    grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups, ("sac_ctde",), action_dim=A)
+    sac_target_ctde([ActorParams.from_sac_module(m) for m in actor_modules], QCriticParams.from_module(critic_target_module, A), buffer, k, index,
+                    discount=discount, alpha=alpha, noise=noise, noise_logp=noise_logp, out=y)
+    _, stats = twinq_grad_ctde(critic, buffer.obs, buffer.act, y, index, grads=grads, stats=own_stats if stats is None else stats,
+                               workspace=workspace, max_workgroups=max_workgroups)
     return stats
 
 

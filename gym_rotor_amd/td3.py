@@ -9,6 +9,10 @@ clamps, two twin-critic forward passes, min, the Bellman line, two mse_loss and 
 policy_update_freq-th iteration three actor passes, the Q1 pass, the backward pass through the critic and three times through the
 actor, and eighteen copy_ lines.  The optimiser group of twelve tensors is not here: `optim.DeviceAdamW` takes eight tensors, so a
 twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
+
+The critic half also exists for ONE centralized (CTDE) twin critic over the two agents of a Decoupled buffer (td3.py:124-137, 157-158):
+`td3_target_ctde` (qr_ctde_twinq_target), `twinq_grad_ctde` (qr_ctde_twinq_grad) and `td3_critic_loss_ctde` on live modules.  The
+critic's row [obs_0 | obs_1 | act_0 | act_1] is formed inside the kernels from the agents' tensors; nothing is concatenated.
 """
 from __future__ import annotations
 
@@ -191,6 +195,161 @@ def td3_target(actor_target: Optional[ActorParams], critic_target: QCriticParams
                    lambda B, A, dev: dict(discount=discount, target_noise=target_noise, noise_clip=noise_clip, max_action=max_action))
 
 
+CTDE_ACTOR_DIMS = ((15, 16, 4), (3, 4, 1))   # the Decoupled wrapper's two actors: what the centralized target kernels hold
+
+
+def _ctde_tensors(what: str, buffer_or_tensors, critic: QCriticParams, k: int):
+    """Both agents' tensors of a two-agent `ReplayBuffer` (or a pair of dicts with obs, obs_next, act and, for agent k, rwd and done),
+    their observation and action widths — which must add up to the centralized critic's — and the common row count."""
+    if k not in (0, 1):
+        raise ValueError(f"{what}: k must be 0 or 1 (two agents), got {k}")
+    if isinstance(buffer_or_tensors, ReplayBuffer):
+        if buffer_or_tensors.n_agents != 2:
+            raise ValueError(f"{what}: buffer must hold two agents, it holds {buffer_or_tensors.n_agents}")
+        t = [buffer_or_tensors.tensors(m) for m in range(2)]
+    else:
+        t = [dict(x) for x in buffer_or_tensors]
+        if len(t) != 2:
+            raise ValueError(f"{what}: buffer must be a two-agent ReplayBuffer or a pair of per-agent dicts")
+    dev = critic.device
+    for m in range(2):
+        for name in ("obs_next", "act"):
+            x = t[m].get(name)
+            if x is None or x.dim() != 2 or x.shape[1] < 1:
+                raise ValueError(f"{what}: agent {m}'s {name} must be a float32 [rows, width] tensor on {dev}")
+    od, ad = [t[m]["obs_next"].shape[1] for m in range(2)], [t[m]["act"].shape[1] for m in range(2)]
+    D, A, _ = critic.dims
+    if sum(od) != D or sum(ad) != A:
+        raise ValueError(f"{what}: the buffer's widths {od[0]}+{od[1]} / {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
+    rows = _rows(t[0]["obs_next"], od[0], dev, what, "agent 0's obs_next")
+    if _rows(t[1]["obs_next"], od[1], dev, what, "agent 1's obs_next") != rows:
+        raise ValueError(f"{what}: agent 1's obs_next must have agent 0's {rows} rows")
+    return t, od, ad, rows
+
+
+def _pair_of(what: str, name: str, x, B: int, widths, dev):
+    """None, or a pair of None / contiguous float32 [B, widths[m]] tensors."""
+    if x is None:
+        return (None, None)
+    x = tuple(x)
+    if len(x) != 2:
+        raise ValueError(f"{what}: {name} must be a pair, one entry per agent")
+    for m, e in enumerate(x):
+        if e is not None and (e.dtype != torch.float32 or e.device != dev or tuple(e.shape) != (B, widths[m]) or not e.is_contiguous()):
+            raise ValueError(f"{what}: {name}[{m}] must be a contiguous float32 [{B}, {widths[m]}] tensor on {dev}")
+    return x
+
+
+def _target_ctde(what: str, entry: str, make_args, actors, form: tuple, critic_target: QCriticParams, buffer_or_tensors, k: int, index, noise,
+                 action_next, out, own) -> torch.Tensor:
+    """`_target` for the centralized critic of two agents, shared by `td3_target_ctde` and `sac.sac_target_ctde`: both agents'
+    transitions, both actors (`form`: _check_actor's last three arguments) or neither, the pairs noise and action_next, the caller's
+    `own(B, widths, dev, supplied)` checks — which return its own keywords of `make_args` — out, and the launch of `entry`."""
+    t, od, ad, rows = _ctde_tensors(what, buffer_or_tensors, critic_target, k)
+    dev = critic_target.device
+    rs, ds = _column(t[k].get("rwd"), rows, dev, what, "rwd"), _column(t[k].get("done"), rows, dev, what, "done")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    actors = (None, None) if actors is None else tuple(actors)
+    if len(actors) != 2 or (actors[0] is None) != (actors[1] is None):
+        raise ValueError(f"{what}: actors must be a pair of both agents' actors, or None for both")
+    supplied = actors[0] is None
+    for m in range(2):
+        if not supplied:
+            _check_actor(actors[m], od[m], ad[m], dev, what, *form)
+            if actors[m].dims != CTDE_ACTOR_DIMS[m]:
+                raise ValueError(f"{what}: actor {m} must have the sizes {CTDE_ACTOR_DIMS[m]} (obs, hidden, action), got {actors[m].dims}")
+    noise = _pair_of(what, "noise", noise, B, ad, dev)
+    action_next = _pair_of(what, "action_next", action_next, B, ad, dev)
+    if supplied and (action_next[0] is None or action_next[1] is None):
+        raise ValueError(f"{what}: without actors, action_next ([B, {ad[0]}], [B, {ad[1]}]) is required")
+    kw = own(B, ad, dev, supplied)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if B == 0:
+        return out
+    b = _lib.ctde_transitions(obs_next=(t[0]["obs_next"], t[1]["obs_next"]), reward=t[k]["rwd"], done=t[k]["done"], index=index, batch=B, rows=rows,
+                              obs_dims=od, action_dims=ad, reward_stride=rs, done_stride=ds)
+    g = make_args(eps=noise, action_next=action_next, y=out, **kw)
+    q = critic_target.as_c()
+    p = [None, None]
+    if not supplied:
+        p = [a.as_c() for a in actors]
+        for c in p:
+            c.log_std = None
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.load(), entry)(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
+                                         torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, entry)
+    return out
+
+
+def td3_target_ctde(actor_targets, critic_target: QCriticParams, buffer_or_tensors, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                    discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5, max_action: float = 1.0, noise=None,
+                    action_next=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TD3's target values for the centralized (CTDE) twin critic of two agents in one launch (qr_ctde_twinq_target; td3.py:124-154),
+    j the minibatch position, i = index[j], m = 0, 1:
+        a'_m = clamp(actor_targets[m](obs_next_m[i]) + clamp(target_noise * noise[m][j], +-noise_clip), +-max_action)
+        y[j] = rwd_k[i] + discount * (1 - done_k[i]) * min(Q1, Q2)([obs_next_0[i] | obs_next_1[i] | a'_0 | a'_1])
+    critic_target: `QCriticParams.from_module(MLP_Critic_CTDE, action_dim=sum(action_dims))`.  actor_targets: the pair of
+    `ActorParams.from_td3_module` of the sizes (15,16,4) and (3,4,1), or None with action_next = (a'_0 [B, A_0], a'_1 [B, A_1]) used as
+    they are, for any widths whose sum the critic reads.  buffer_or_tensors: a two-agent `ReplayBuffer`, or a pair of dicts with
+    obs_next, act (its width is read) and, for agent k, rwd and done.  noise: a pair of float32 [B, A_m] standard-normal draws (either
+    may be None) or None.  No concatenated copy of the rows is made.  Returns y float32 [B] (`out` given: written in place)."""
+    return _target_ctde("td3_target_ctde", "qr_ctde_twinq_target", _lib.ctde_td3_target_args, actor_targets,
+                        (_lib.ACTOR_TANH_MEAN, False, "the target actors must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head"),
+                        critic_target, buffer_or_tensors, k, index, noise, action_next, out,
+                        lambda B, ad, dev, supplied: dict(discount=discount, target_noise=target_noise, noise_clip=noise_clip, max_action=max_action))
+
+
+def twinq_grad_ctde(critic: QCriticParams, obs, action, y: torch.Tensor, index: Optional[torch.Tensor] = None, *, grads: Optional[dict] = None,
+                    stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, max_workgroups: int = 0):
+    """`twinq_grad` for the centralized (CTDE) critic (qr_ctde_twinq_grad): the row [obs[0][i] | obs[1][i] | action[0][i] | action[1][i]]
+    is formed inside the kernel from the two agents' tensors — no concatenated copy.  obs: a pair of contiguous float32 [rows, D_m];
+    action: a pair of float32 [rows, A_m] whose rows lie one row stride apart (all columns are read); the widths must add up to the
+    critic's.  y, index, grads, stats, workspace, max_workgroups and the return value: `twinq_grad`'s, as are the bits where the
+    concatenated rows are given to it at the same grid."""
+    what = "twinq_grad_ctde"
+    dev = critic.device
+    D, A, H = critic.dims
+    obs, action = tuple(obs), tuple(action)
+    if len(obs) != 2 or len(action) != 2:
+        raise ValueError(f"{what}: obs and action must be pairs, one tensor per agent")
+    for m in range(2):
+        if obs[m] is None or obs[m].dim() != 2 or obs[m].shape[1] < 1:
+            raise ValueError(f"{what}: obs[{m}] must be a contiguous float32 [rows, width] tensor on {dev}")
+    rows = _rows(obs[0], obs[0].shape[1], dev, what, "obs[0]")
+    if _rows(obs[1], obs[1].shape[1], dev, what, "obs[1]") != rows:
+        raise ValueError(f"{what}: obs[1] must have obs[0]'s {rows} rows")
+    for m, a in enumerate(action):
+        if (a is None or a.dtype != torch.float32 or a.device != dev or a.dim() != 2 or a.shape[0] != rows or a.shape[1] < 1
+                or (a.shape[1] > 1 and a.stride(1) != 1) or a.stride(0) < a.shape[1]):
+            raise ValueError(f"{what}: action[{m}] must be float32 [{rows}, width] rows with unit column stride on {dev}")
+    od, ad = [o.shape[1] for o in obs], [a.shape[1] for a in action]
+    if sum(od) != D or sum(ad) != A:
+        raise ValueError(f"{what}: the widths of obs {od[0]}+{od[1]} / action {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    if y is None or y.dtype != torch.float32 or y.device != dev or y.numel() != B or not y.is_contiguous():
+        raise ValueError(f"{what}: y must be a contiguous float32 [{B}] tensor on {dev}")
+    grads, stats, workspace = _grad_outputs(what, critic.shapes, dev, B, grads, stats, workspace,
+                                            lambda: twinq_workspace_bytes(critic.dims, B, max_workgroups))
+    if workspace is None:
+        return grads, stats
+    b = _lib.ctde_transitions(obs=obs, action=action, index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad,
+                              row_strides=[a.stride(0) if rows > 1 else a.shape[1] for a in action])
+    g = _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups)
+    q = critic.as_c()
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_ctde_twinq_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ctde_twinq_grad")
+    return grads, stats
+
+
 def twinq_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `twinq_grad` call needs (qr_twinq_workspace_bytes); dims = (obs_dim, action_dim, hidden width)."""
     n = _lib.load().qr_twinq_workspace_bytes(int(dims[0]) + int(dims[1]), int(dims[2]), int(batch), int(max_workgroups))
@@ -232,16 +391,17 @@ def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y
     return grads, stats
 
 
-def _critic_update_state(critic_module, buffer: ReplayBuffer, k: int, index, max_workgroups: int, tag: tuple = ()):
-    """For `td3_critic_loss` and `sac.sac_critic_loss`: the live twin critic's twelve .grad tensors by name (made where there is none),
-    its `QCriticParams`, and (y, workspace, stats) from the buffer's cache under tag + (k, B, max_workgroups)."""
+def _critic_update_state(critic_module, buffer: ReplayBuffer, k: int, index, max_workgroups: int, tag: tuple = (), action_dim: Optional[int] = None):
+    """For `td3_critic_loss`, `sac.sac_critic_loss` and their centralized forms: the live twin critic's twelve .grad tensors by name (made
+    where there is none), its `QCriticParams` (action_dim: agent k's, or what the centralized form gives), and (y, workspace, stats)
+    from the buffer's cache under tag + (k, B, max_workgroups)."""
     layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
     grads = {}
     for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
         if p.grad is None or not p.grad.is_contiguous():
             p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
         grads[n] = p.grad
-    critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
+    critic = QCriticParams.from_module(critic_module, buffer.action_dims[k] if action_dim is None else action_dim)
     B = buffer.capacity if index is None else index.numel()
     key = tag + (k, B, int(max_workgroups))
     hit = buffer._cache.get(key)
@@ -272,6 +432,27 @@ def td3_critic_loss(critic_module, critic_target_module, actor_target_module, bu
                noise_clip=noise_clip, max_action=max_action, noise=noise, out=y)
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
                           workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def td3_critic_loss_ctde(critic_module, critic_target_module, actor_target_modules, buffer: ReplayBuffer, k: int = 0,
+                         index: Optional[torch.Tensor] = None, *, discount: float = 0.99, target_noise: float = 0.2, noise_clip: float = 0.5,
+                         max_action: float = 1.0, noise=None, stats: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """`td3_critic_loss` for the centralized (CTDE) critic of a two-agent `buffer`, for agent k's reward and done: `td3_target_ctde` on
+    the two target actors and the target critic, then `twinq_grad_ctde` on the live `critic_module` (MLP_Critic_CTDE: fc1 .. fc6 over
+    [obs_0 | obs_1 | act_0 | act_1]); fills `critic_module.fc{1..6}.{weight,bias}.grad` in place.  noise: the pair of [B, A_m]
+    smoothing draws, or None.  Returns stats (stats[0] = the loss).  y, the workspace and stats are cached on the buffer under a key of
+    their own: from the second call on with an unchanged B nothing is allocated.  The optimiser step stays the caller's."""
+    if not isinstance(buffer, ReplayBuffer):
+        raise ValueError("td3_critic_loss_ctde: buffer must be a ReplayBuffer")
+    A = sum(buffer.action_dims)
+    grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups, ("td3_ctde",), action_dim=A)
+    actors = [ActorParams(m.fc1.weight.data, m.fc1.bias.data, m.fc2.weight.data, m.fc2.bias.data, m.fc3.weight.data, m.fc3.bias.data, None)
+              for m in actor_target_modules]
+    td3_target_ctde(actors, QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
+                    noise_clip=noise_clip, max_action=max_action, noise=noise, out=y)
+    _, stats = twinq_grad_ctde(critic, buffer.obs, buffer.act, y, index, grads=grads, stats=own_stats if stats is None else stats,
+                               workspace=workspace, max_workgroups=max_workgroups)
     return stats
 
 

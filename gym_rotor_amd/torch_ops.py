@@ -435,6 +435,72 @@ def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_
                noise=noise, action_next=action_next, logp_next=logp_next, out=y, action_out=action_out, logp_out=logp_out)
 
 
+def _ctde_agents(obs_next0, obs_next1, act0, act1, reward, done, k: int):
+    """The pair of per-agent dicts the centralized helpers take; reward and done are agent k's."""
+    t = [{"obs_next": obs_next0, "act": act0}, {"obs_next": obs_next1, "act": act1}]
+    if k in (0, 1):
+        t[k].update(rwd=reward, done=done)
+    return t
+
+
+@torch.library.custom_op(f"{_NS}::qr_ctde_twinq_target", mutates_args=("y",))
+def qr_ctde_twinq_target(actors: List[torch.Tensor], critic: List[torch.Tensor], obs_next0: torch.Tensor, obs_next1: torch.Tensor,
+                         action0: torch.Tensor, action1: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, index: Optional[torch.Tensor],
+                         noise0: Optional[torch.Tensor], noise1: Optional[torch.Tensor], action_next0: Optional[torch.Tensor],
+                         action_next1: Optional[torch.Tensor], y: torch.Tensor, discount: float, target_noise: float, noise_clip: float,
+                         max_action: float) -> None:
+    """TD3's target values for the centralized critic of two agents (qr_ctde_twinq_target).  actors: both target actors' six tensors each
+    (twelve: agent 0's fc1_w .. fc3_b, then agent 1's), or an empty list with action_next0 / action_next1; critic: the target critic's
+    twelve; action0, action1: the agents' action tensors (their widths are read); reward, done: the columns of the agent whose target
+    this is.  Everything else as td3.td3_target_ctde."""
+    from .policy import ActorParams
+    from .td3 import td3_target_ctde
+    _gpu(y)
+    if len(actors) not in (0, 12):
+        raise ValueError("two TD3 actors are 12 tensors: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b of agent 0, then of agent 1")
+    pair = [ActorParams(*actors[6 * m:6 * m + 6], None) for m in range(2)] if actors else None
+    td3_target_ctde(pair, _qcritic_params(critic, action0.shape[-1] + action1.shape[-1]),
+                    _ctde_agents(obs_next0, obs_next1, action0, action1, reward, done, 0), 0, index, discount=discount, target_noise=target_noise,
+                    noise_clip=noise_clip, max_action=max_action, noise=(noise0, noise1),
+                    action_next=None if action_next0 is None and action_next1 is None else (action_next0, action_next1), out=y)
+
+
+@torch.library.custom_op(f"{_NS}::qr_ctde_sac_target", mutates_args=("y", "action_out0", "action_out1", "logp_out"))
+def qr_ctde_sac_target(actors: List[torch.Tensor], critic: List[torch.Tensor], agent: int, obs_next0: torch.Tensor, obs_next1: torch.Tensor,
+                       action0: torch.Tensor, action1: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, index: Optional[torch.Tensor],
+                       noise0: Optional[torch.Tensor], noise1: Optional[torch.Tensor], noise_logp: Optional[torch.Tensor],
+                       action_next0: Optional[torch.Tensor], action_next1: Optional[torch.Tensor], logp_next: Optional[torch.Tensor], y: torch.Tensor,
+                       action_out0: Optional[torch.Tensor], action_out1: Optional[torch.Tensor], logp_out: Optional[torch.Tensor], discount: float,
+                       alpha: float, alpha_dev: Optional[torch.Tensor] = None) -> None:
+    """SAC's target values for the centralized critic of two agents (qr_ctde_sac_target).  actors: both live actors' eight tensors each
+    (sixteen: agent 0's fc1_w .. log_std_b, then agent 1's), or an empty list with action_next0 / action_next1 and logp_next; agent: whose
+    reward, done and log-probability.  Everything else as qr_ctde_twinq_target's and sac.sac_target_ctde."""
+    from .policy import ActorParams
+    from .sac import sac_target_ctde
+    _gpu(y)
+    if len(actors) not in (0, 16):
+        raise ValueError("two SAC actors are 16 tensors: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b of agent 0, then of agent 1")
+    pair = [ActorParams(*actors[8 * m:8 * m + 6], None, actors[8 * m + 6], actors[8 * m + 7], _lib.ACTOR_TANH_SAMPLE) for m in range(2)] if actors else None
+    sac_target_ctde(pair, _qcritic_params(critic, action0.shape[-1] + action1.shape[-1]),
+                    _ctde_agents(obs_next0, obs_next1, action0, action1, reward, done, agent), agent, index, discount=discount,
+                    alpha=alpha if alpha_dev is None else alpha_dev, noise=(noise0, noise1), noise_logp=noise_logp,
+                    action_next=None if action_next0 is None and action_next1 is None else (action_next0, action_next1), logp_next=logp_next,
+                    out=y, action_out=(action_out0, action_out1), logp_out=logp_out)
+
+
+@torch.library.custom_op(f"{_NS}::qr_ctde_twinq_grad", mutates_args=("grads", "stats"))
+def qr_ctde_twinq_grad(critic: List[torch.Tensor], obs0: torch.Tensor, obs1: torch.Tensor, action0: torch.Tensor, action1: torch.Tensor,
+                       y: torch.Tensor, index: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor, max_workgroups: int = 0) -> None:
+    """The twin-Q loss of the centralized critic against y and its twelve gradients (qr_ctde_twinq_grad); as qr_twinq_grad, with the row
+    formed from obs0, obs1, action0, action1 in the kernel.  Everything else as td3.twinq_grad_ctde."""
+    from .td3 import twinq_grad_ctde
+    _gpu(stats)
+    if len(grads) != 12:
+        raise ValueError("grads is 12 tensors: fc1_w, fc1_b, ..., fc6_w, fc6_b")
+    twinq_grad_ctde(_qcritic_params(critic, action0.shape[-1] + action1.shape[-1]), (obs0, obs1), (action0, action1), y, index,
+                    grads=dict(zip(_lib.TWINQ_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_actor_grad", mutates_args=("grads", "stats", "alpha_grad"))
 def qr_sac_actor_grad(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor, obs_next: Optional[torch.Tensor],
                       index: Optional[torch.Tensor], eps: Optional[torch.Tensor], eps_reg: Optional[torch.Tensor], eps_next: Optional[torch.Tensor],

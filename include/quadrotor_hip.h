@@ -541,8 +541,8 @@ int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream);
  * flat transition buffer in place, without autograd.  The reference's twin critic MLP_Critic (algos/td3/td3_mlp.py:36-99), twelve
  * float32 tensors in torch.nn.Linear layout, used in place:
  *     Q1 = fc3(relu(fc2(relu(fc1(sa)))))     Q2 = fc6(relu(fc5(relu(fc4(sa)))))     sa = the observation row followed by the action row
- * obs_dim >= 1, action_dim >= 1, obs_dim + action_dim <= 28, 1 <= hidden_dim <= 64.  reserved0 must be 0 (a later CTDE form, rows
- * from four sources, takes it). */
+ * obs_dim >= 1, action_dim >= 1, obs_dim + action_dim <= 28, 1 <= hidden_dim <= 64.  reserved0 must be 0.  The centralized (CTDE)
+ * critic, whose rows come from four sources, is this struct too, with the summed widths: the sources are QrCtdeTransitions', below. */
 typedef struct QrQCritic {
   const float *fc1_w, *fc1_b;       /* [hidden][obs_dim+action_dim], [hidden]     Q1 */
   const float *fc2_w, *fc2_b;       /* [hidden][hidden], [hidden]                    */
@@ -754,6 +754,75 @@ int qr_sac_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTra
  * would refuse them. */
 int64_t qr_sac_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int32_t critic_hidden_dim, int64_t batch,
                                      int32_t max_workgroups);
+
+/* The critic half of one TD3 / SAC minibatch update with ONE centralized twin critic over TWO agents (the reference's CTDE branches:
+ * TD3.train, algos/td3/td3.py:124-137, 157-158; SAC.train, algos/sac/sac.py:136-144, 156-157; MLP_Critic_CTDE,
+ * algos/td3/td3_mlp.py:102-168), for agent k's reward and done.  The critic is a QrQCritic with obs_dim = obs_dim[0] + obs_dim[1] and
+ * action_dim = action_dim[0] + action_dim[1]; its input row is [obs_0 | obs_1 | act_0 | act_1] (torch.cat(state), torch.cat(action)),
+ * formed inside the kernels from the two agents' buffers: no concatenated copy of the minibatch exists.
+ * What a two-agent ReplayBuffer holds, and one minibatch of it.  Per agent m: obs[m], obs_next[m] [>= rows][obs_dim[m]]; action: row i
+ * at action[m] + i * row_stride[m] + col_offset[m]; widths >= 1 each, their sum <= 28.  reward, done: agent k's columns, element i at
+ * reward[i * reward_stride], done[i * done_stride].  index, batch, rows: as in QrTransitions.  A pointer the entry point does not read
+ * may be NULL: the targets read obs_next, reward, done and index; qr_ctde_twinq_grad reads obs, action and index. */
+typedef struct QrCtdeTransitions {
+  const float* obs[2];     const float* obs_next[2];
+  const float* action[2];
+  const float* reward;     const float* done;
+  const int64_t* index;
+  int64_t batch, rows;
+  int32_t obs_dim[2], action_dim[2];
+  int32_t row_stride[2], col_offset[2];               /* of the action rows */
+  int32_t reward_stride, done_stride;
+} QrCtdeTransitions;
+/* The TD3 target in ONE launch (td3.py:124-154), j the minibatch position and i = index[j], m = 0, 1:
+ *     a'_m = clamp(pi_targ_m(obs_next_m[i]) + clamp(target_noise * eps_m[j], +-noise_clip), +-max_action)
+ *     y[j] = reward[i] + discount * (1 - done[i]) * min(Q1_targ, Q2_targ)([obs_next_0[i] | obs_next_1[i] | a'_0 | a'_1])
+ * Both actors: QR_ACTOR_TANH_MEAN forms of exactly the sizes (15,16,4) and (3,4,1), the Decoupled wrapper's, equal to the batch's widths.
+ * Both actors NULL: a'_m = action_next[m][j] ([batch][action_dim[m]], used as it is), any widths.  One NULL and one not is an error.
+ * eps[m]: [batch][action_dim[m]] by minibatch position, or NULL: no noise.  A row with done = 1 gets y = reward exactly. */
+typedef struct QrCtdeTd3Target {
+  const float* eps[2];
+  const float* action_next[2];
+  float* y;
+  float discount, target_noise, noise_clip, max_action;
+} QrCtdeTd3Target;
+/* QR_E_NULL for a NULL critic, batch or target struct, weight, obs_next, reward, done or y pointer, exactly one actor NULL, or both
+ * NULL with an action_next NULL; QR_E_KIND for an actor with squash != QR_ACTOR_TANH_MEAN or a log_std head; QR_E_SIZE for widths
+ * outside the ranges above, widths that do not add up to the critic's, reserved0 != 0, actor sizes other than (15,16,4) and (3,4,1) or
+ * different from the batch's widths, batch < 1, rows < 1, a stride < 1 or a negative or non-finite noise_clip / max_action; QR_E_ALIGN
+ * for a float pointer that is not 4-byte aligned or an index pointer that is not 8-byte aligned.  Nothing is launched on an error. */
+int qr_ctde_twinq_target(const QrActor* actor_target_0, const QrActor* actor_target_1, const QrQCritic* critic_target,
+                         const QrCtdeTransitions* batch, const QrCtdeTd3Target* target, void* stream);
+/* SAC's soft target in ONE launch (sac.py:136-153), with qr_sac_target's sample and its arithmetic, m = 0, 1 and k = agent:
+ *     (mean_m, ls_m) = pi_m(obs_next_m[i]);  ls_m = clamp(ls_m, -20, 2);  a'_m = tanh(mean_m + exp(ls_m) * eps_m[j])     (the LIVE actors)
+ *     logp_j = sum_f [ -e^2 / 2 - ls_k - log sqrt(2 pi) - log(1 - tanh(mean_k + exp(ls_k) e)^2 + 1e-6) ],   e = eps_logp[j]
+ *     y[j] = reward[i] + discount * (1 - done[i]) * ( min(Q1_targ, Q2_targ)([obs_next_0[i] | obs_next_1[i] | a'_0 | a'_1]) - alpha * logp_j )
+ * The reference samples agent k a second time for the log-probability: eps_logp [batch][action_dim[k]] is that draw; NULL: eps[k], one
+ * sample, and the same tensor for both gives the bits of NULL.  eps[m] NULL: zeros.  Both actors: QR_ACTOR_TANH_SAMPLE forms with the
+ * log_std head, sizes as above.  Both NULL: a'_m = action_next[m][j] and logp_j = logp_next[j] as they are.  alpha, alpha_dev: as in
+ * QrSacTarget.  action_out[m] [batch][action_dim[m]] and logp_out [batch]: optional, what was used.  agent: 0 or 1. */
+typedef struct QrCtdeSacTarget {
+  const float* eps[2];       const float* eps_logp;
+  const float* action_next[2];  const float* logp_next;
+  const float* alpha_dev;
+  float* y;
+  float* action_out[2];      float* logp_out;
+  float discount, alpha;
+  int32_t agent, reserved0;
+} QrCtdeSacTarget;
+/* As qr_ctde_twinq_target, with: QR_E_NULL also for both actors NULL with logp_next NULL; QR_E_KIND for an actor with squash !=
+ * QR_ACTOR_TANH_SAMPLE or without the log_std head; QR_E_SIZE also for agent outside 0..1, reserved0 != 0 (either struct) or a
+ * negative or non-finite discount or alpha (no noise_clip / max_action here).  Nothing is launched on an error. */
+int qr_ctde_sac_target(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic_target, const QrCtdeTransitions* batch,
+                       const QrCtdeSacTarget* target, void* stream);
+/* qr_twinq_grad for the centralized critic: the same loss, the same twelve gradients and stats [4], the row x_i = [obs_0[i] | obs_1[i]
+ * | act_0[i] | act_1[i]] formed in the kernel's tile from its four sources.  The QrTwinQGrad, the two launches, the grid rule and the
+ * workspace are qr_twinq_grad's; with the concatenated rows materialised, qr_twinq_grad gives the same bits at the same grid.
+ * QR_E_NULL, QR_E_SIZE and QR_E_ALIGN as qr_twinq_grad, per agent for obs, action, row_stride and col_offset; QR_E_SIZE also for
+ * widths < 1 or widths that do not add up to the critic's.  Nothing is launched on an error. */
+int qr_ctde_twinq_grad(const QrQCritic* critic, const QrCtdeTransitions* batch, const QrTwinQGrad* grad, void* stream);
+/* Bytes of workspace qr_ctde_twinq_grad needs (in_dim = the four widths' sum, >= 4): qr_twinq_workspace_bytes's figure. */
+int64_t qr_ctde_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
 
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);

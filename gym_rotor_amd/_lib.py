@@ -37,7 +37,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
            "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target",
            "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes",
-           "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes")
+           "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
+           "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -251,6 +252,10 @@ class QrCtdeSacTarget(C.Structure):
                 ("alpha", C.c_float), ("agent", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class QrCtdeDpgGrad(C.Structure):
+    _fields_ = QrDpgGrad._fields_ + [("agent", C.c_int32), ("reserved1", C.c_int32), ("action_other", C.c_void_p)]
+
+
 def _pair(x):
     x = (None, None) if x is None else x
     return (C.c_void_p * 2)(ptr(x[0]), ptr(x[1]))
@@ -279,6 +284,14 @@ def ctde_sac_target_args(*, eps, eps_logp, action_next, logp_next, alpha_dev, y,
     """QrCtdeSacTarget of one qr_ctde_sac_target launch; eps, action_next, action_out: pairs (or None)."""
     return QrCtdeSacTarget(_pair(eps), ptr(eps_logp), _pair(action_next), ptr(logp_next), ptr(alpha_dev), ptr(y), _pair(action_out), ptr(logp_out),
                            float(discount), float(alpha), int(agent), 0)
+
+
+def ctde_dpg_grad_args(grads, stats, noise, nominal, workspace, *, agent, action_other, lam_T, lam_S, lam_M, max_action, max_workgroups) -> QrCtdeDpgGrad:
+    """QrCtdeDpgGrad of one qr_ctde_dpg_actor_grad launch: dpg_grad_args' fields, the agent k and the other agent's action (or None)."""
+    d = dpg_grad_args(grads, stats, noise, nominal, workspace, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
+    g = QrCtdeDpgGrad(*[getattr(d, n) for n, _ in QrDpgGrad._fields_])
+    g.agent, g.reserved1, g.action_other = int(agent), 0, ptr(action_other)
+    return g
 
 
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
@@ -446,6 +459,10 @@ def load():
     lib.qr_ctde_twinq_grad.argtypes = [P(QrQCritic), P(QrCtdeTransitions), P(QrTwinQGrad), C.c_void_p]
     lib.qr_ctde_twinq_workspace_bytes.restype = C.c_int64
     lib.qr_ctde_twinq_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_ctde_dpg_actor_grad.restype = C.c_int
+    lib.qr_ctde_dpg_actor_grad.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeDpgGrad), C.c_void_p]
+    lib.qr_ctde_dpg_actor_workspace_bytes.restype = C.c_int64
+    lib.qr_ctde_dpg_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

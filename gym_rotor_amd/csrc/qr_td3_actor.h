@@ -3,6 +3,8 @@
 // algos/policy_regularization.py):
 //   dpg_actor_kernel + dpg_reduce_kernel (qr_dpg_actor_grad)   -mean Q1(s, pi(s)) with the three smoothness terms, and its gradients
 //                                                               for MLP_Actor_TD3's six tensors
+//   ctde_dpg_actor_kernel + dpg_reduce_kernel (qr_ctde_dpg_actor_grad)   the same for agent k of two under ONE centralized (CTDE) critic
+//                                                               (td3.py:180-196): the same walk (dpg_walk) in its two-agent form
 //   soft_update_kernel (qr_soft_update)                         target = tau param + (1 - tau) target for up to 24 tensors
 // The pieces are shared: the actor's passes are PpoNet's (qr_ppo.h: forward, backward, the MFMA weight gradients, emit), Q1's forward
 // pass and the product W2^T dz2 are qr_mlp_grad.h's pieces with qr_td3.h's TwinQL1, the reduction is reduce16_entries /
@@ -31,6 +33,18 @@ struct DpgArgs {
   float max_action;
   float lam_T, lam_S, lam_M;         // only their being zero is read here (wave-uniform branches)
   float inv_b, c_T, c_S, c_M;        // 1 / B and 2 lam / (B A): the per-row factors of the gradient
+};
+
+// The centralized (CTDE) form for agent k of two (qr_ctde_dpg_actor_grad): DpgArgs' members are agent k's (w = pi_k, obs / obs_next /
+// noise / nominal its own), q = Q1 of the centralized critic whose row is [obs_0 | obs_1 | a_0 | a_1].
+struct CtdeDpgArgs : DpgArgs {
+  ActorW other;                      // pi_{1-k}, forward only (log_std and the log_std head NULL); read when action_other is NULL
+  const float* obs_other;            // [>= rows][od_other]
+  const float* action_other;         // [B][ad_other] by minibatch position, used as it is, or NULL: pi_{1-k}'s clamped output
+  int32_t od_other, ad_other;        // the other agent's widths
+  int32_t col_own, col_other;        // first column of each agent's observation in the critic's row
+  int32_t acol_own, acol_other;      // first column of each agent's action: D + off_k, D + off_{1-k}
+  int32_t in_dim;                    // the row's width, <= 28
 };
 
 // One workgroup's partial vector: PpoLayout's six weight and bias tensors, then the five sums of `stats`:
@@ -120,8 +134,17 @@ __device__ __forceinline__ void dpg_q1_half(const float (&a2)[4][4][4], const fl
 // dQ1/da per half tile on the matrix cores; back on lane = row, dmu = -(1/B) dQ/da plus the smoothness deltas under the clamp mask,
 // and up to three PpoNet::backward passes — on obs + noise (lam_S), on obs_next (lam_T) and on obs itself — into the same resident
 // accumulators, exactly as ppo_actor_kernel orders them.  At the end the workgroup writes ONE partial vector.
-template <int D, int H, int A>
-__global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
+//
+// CT: the centralized (CTDE) form, Args = CtdeDpgArgs.  The critic's tile takes the other agent's observation rows at their columns
+// (stage_rows, a second pointer array) and its action: supplied by minibatch position, or pi_{1-k} forward only on the lane's own row
+// from LDS (PpoNet::forward of the pair's other size: (3,4,1) beside a (15,16,4) agent k and the reverse), clamped, before agent k's own pass so that it costs no
+// register across the critic's phase.  Agent k's observation and action go to their own columns, `was` is fc1_w's columns of a_k.
+// The other agent's action is a VALUE: no gradient for agent 1-k is produced (the reference's backward pass leaves one in that actor's
+// .grad, which that agent zeroes before anything reads it; include/quadrotor_hip.h).
+// Everything else is the one-agent walk; the whole body is ONE force-inlined function with the form as a compile-time argument,
+// which leaves the one-agent kernels their registers, where hooks around the loss phase did not (§8.9).
+template <int D, int H, int A, bool CT, class Args>
+__device__ __forceinline__ void dpg_walk(const Args& a) {
   using Net = PpoNet<D, H, A>;
   using PY = PpoLayout<D, H, A>;
   using Y = DpgLayout<D, H, A>;
@@ -131,8 +154,13 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
   __shared__ float qs[64 * kMgX], w1s[TwinQL1::SIZE], w2ts[64 * 64], svec[kTqVec], was[64 * 4], dq[64 * kDpgQ];
   __shared__ const float* src[64];
   __shared__ double red[64 * Y::NS];
+  using Other = PpoNet<D == 15 ? 3 : 15, D == 15 ? 4 : 16, D == 15 ? 1 : 4>;  // (CT) the Decoupled pair's other half: its forward pass
+  __shared__ const float* src1[CT ? 64 : 1];
+  __shared__ float osm[CT ? Other::SM : 4];
   const int lane = threadIdx.x;
   const int QH = a.hidden;
+  int IN = D + A, xcol = 0, acol = D;  // the critic's width, agent k's observation and action columns in its row
+  if constexpr (CT) { IN = a.in_dim; xcol = a.col_own; acol = a.acol_own; }
   float a2[4][4][4];
   {
     float a2t[4][4][4];
@@ -140,9 +168,16 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
 #pragma unroll
     for (int e = 0; e < 64; ++e) w2ts[64 * e + lane] = a2t[e >> 4][(e >> 2) & 3][e & 3];
   }
-  twinq_fill_small(w1s, svec, a.q, D + A, QH, lane);
+  twinq_fill_small(w1s, svec, a.q, IN, QH, lane);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? a.q.fc1_w[lane * (D + A) + D + j] : 0.0f;
+  for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? a.q.fc1_w[lane * IN + acol + j] : 0.0f;
+  if constexpr (CT) {
+    if (!a.action_other) {
+      PpoArgs p{};
+      p.w = a.other;
+      Other::fill(osm, p, lane);
+    }
+  }
   const float bias3 = a.q.fc3_b[0];
   Net net;
   net.zero();
@@ -154,7 +189,7 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
   }
   for (int i = lane; i < 64 * XS; i += 64) xs[i] = (i % XS == D) ? 1.0f : 0.0f;  // the ones column; the rest of the padding stays zero
   for (int i = lane; i < 64 * HS; i += 64) hs[i] = (i % HS == H) ? 1.0f : 0.0f;
-  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns >= D + A stay zero
+  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns >= IN stay zero
   __syncthreads();
   float nominal[A];
 #pragma unroll
@@ -170,9 +205,26 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
     int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
     i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
     src[lane] = active ? a.obs + i * D : nullptr;
+    if constexpr (CT) src1[lane] = active ? a.obs_other + i * a.od_other : nullptr;
     __syncthreads();
     ppo_stage<D, XS>(xs, src, lane);
+    if constexpr (CT) stage_rows(qs, kMgX, src1, a.od_other, a.col_other, lane);
     __syncthreads();
+    if constexpr (CT) {  // the other agent's action: a value only
+      float* qa = qs + lane * kMgX + a.acol_other;
+      if (a.action_other) {
+        for (int f = 0; f < a.ad_other; ++f) qa[f] = active ? a.action_other[(row0 + lane) * a.ad_other + f] : 0.0f;
+      } else {
+        constexpr int OD = D == 15 ? 3 : 15, OA = D == 15 ? 1 : 4;
+        constexpr int OH = D == 15 ? 4 : 16;
+        float xo[OD], g1[OH], g2[OH], mo[OA];
+#pragma unroll
+        for (int k = 0; k < OD; ++k) xo[k] = qs[lane * kMgX + a.col_other + k];
+        Other::forward(osm, xo, g1, g2, mo);
+#pragma unroll
+        for (int f = 0; f < OA; ++f) qa[f] = fminf(fmaxf(mo[f], -a.max_action), a.max_action);
+      }
+    }
     float x[D], h1[H], h2[H], mu[A], m[A], dm[A];
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
@@ -180,13 +232,13 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
     // the critic's phase needs the registers: x waits in its tile (and in qs), pi's activations in the two tiles that are free
     // until the first backward pass
 #pragma unroll
-    for (int k = 0; k < D; ++k) qs[lane * kMgX + k] = x[k];
+    for (int k = 0; k < D; ++k) qs[lane * kMgX + xcol + k] = x[k];
 #pragma unroll
     for (int u = 0; u < H; ++u) { hs[lane * HS + u] = h1[u]; ds[lane * kPpoDelta + u] = h2[u]; }
 #pragma unroll
     for (int j = 0; j < A; ++j) {
       m[j] = fminf(fmaxf(mu[j], -a.max_action), a.max_action);
-      qs[lane * kMgX + D + j] = m[j];
+      qs[lane * kMgX + acol + j] = m[j];
       if (active && fabsf(mu[j]) > a.max_action) st[1] += 1.0;
     }
     __syncthreads();
@@ -239,7 +291,7 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
     }
     if (a.lam_S != 0.0f || a.lam_T != 0.0f) {
 #pragma unroll
-      for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + k];
+      for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + xcol + k];
     }
     float dmu[A];
 #pragma unroll
@@ -261,6 +313,13 @@ __global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) {
     P[Y::O_ST + lane] = s;
   }
 }
+
+template <int D, int H, int A>
+__global__ __launch_bounds__(64) void dpg_actor_kernel(const DpgArgs a) { dpg_walk<D, H, A, false>(a); }
+
+// Agent k of two under one centralized critic (qr_ctde_dpg_actor_grad): <15, 16, 4> for k = 0, <3, 4, 1> for k = 1.
+template <int D, int H, int A>
+__global__ __launch_bounds__(64) void ctde_dpg_actor_kernel(const CtdeDpgArgs a) { dpg_walk<D, H, A, true>(a); }
 
 struct DpgReduceArgs {
   const double* partials;   // [n_parts][np]

@@ -49,11 +49,12 @@
 //   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk;
 //                  the centralized (CTDE) critic of two agents (qr_ctde_twinq_target, qr_ctde_sac_target, qr_ctde_twinq_grad): the walks' two-agent forms, ctde_twinq_kernel
-//   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel
+//   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel;
+//                  agent k's actor half under the centralized (CTDE) critic (qr_ctde_dpg_actor_grad): the same walk's two-agent form, ctde_dpg_actor_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
-//   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad and qr_dpg_actor_grad),
+//   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad) and target_launch (the four target entries)
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
@@ -479,6 +480,55 @@ static int do_dpg_actor(const QrActor* p, const QrQCritic* c, const QrTransition
                            g->workspace_bytes, g->max_workgroups, kDpgNP, kernel, dpg_reduce_kernel, 16, stream);
 }
 
+// qr_dpg_actor_grad's launcher, grid, partial vector and reduction for agent k of two under one centralized critic.  actor_grad_launch
+// fits: it is given agent k's actor, and what is this entry's own arrives in its classes — the other actor's form first (KIND comes
+// first there too), the widths, the pair's sizes and `agent` in sizes_ok, the form's pointers in supplied_ok, the other actor's
+// tensors among `own` for the alignment.  The table's first place (the 23-wide actor) is empty: 23 + 1 + 4 + 1 > 28, refused above.
+static int do_ctde_dpg_actor(const QrActor* p0, const QrActor* p1, const QrQCritic* c, const QrCtdeTransitions* b, const QrCtdeDpgGrad* g, void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  const QrActor* const p[2] = {p0, p1};
+  for (int m = 0; m < 2; ++m)
+    if (p[m] && (p[m]->squash != QR_ACTOR_TANH_MEAN || p[m]->log_std_w || p[m]->log_std_b)) return QR_E_KIND;
+  if (p0 && p1 && g->action_other) return QR_E_KIND;
+  if (g->agent != 0 && g->agent != 1) return QR_E_SIZE;
+  const int k = g->agent;
+  const QrActor *own = p[k], *other = p[1 - k];
+  bool sizes_ok = twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) && c->reserved0 == 0 && ctde_widths_ok(c, b->obs_dim, b->action_dim) &&
+                  b->batch >= 1 && b->rows >= 1 && g->max_workgroups >= 0 && g->reserved0 == 0 && g->reserved1 == 0 && nonneg_finite(g->max_action) &&
+                  nonneg_finite(g->lam_T) && nonneg_finite(g->lam_S) && nonneg_finite(g->lam_M);
+  if (own) sizes_ok = sizes_ok && actor_size(own->obs_dim, own->hidden_dim, own->action_dim) == 1 + k && own->obs_dim == b->obs_dim[k] && own->action_dim == b->action_dim[k];
+  if (other) sizes_ok = sizes_ok && actor_size(other->obs_dim, other->hidden_dim, other->action_dim) == 2 - k && other->obs_dim == b->obs_dim[1 - k] &&
+                        other->action_dim == b->action_dim[1 - k];
+  if (!sizes_ok) return QR_E_SIZE;
+  if (!own) return QR_E_NULL;
+  const bool other_ok = other ? other->fc1_w && other->fc1_b && other->fc2_w && other->fc2_b && other->mean_w && other->mean_b : g->action_other != nullptr;
+  const bool supplied_ok = other_ok && c->fc1_w && c->fc1_b && c->fc2_w && c->fc2_b && c->fc3_w && c->fc3_b && g->stats && b->obs[0] && b->obs[1] &&  // (Q2 is not read)
+                           !(g->lam_T != 0.0f && !b->obs_next[k]) && !(g->lam_S != 0.0f && !g->noise) && !(g->lam_M != 0.0f && !g->nominal);
+  CtdeDpgArgs a{};
+  a.q = MlpNetW{c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b};
+  a.obs = b->obs[k]; a.obs_next = g->lam_T != 0.0f ? b->obs_next[k] : nullptr; a.index = b->index;
+  a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
+  a.partials = static_cast<double*>(g->workspace);
+  a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim; a.max_action = g->max_action;
+  a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
+  if (other) a.other = ActorW{other->fc1_w, other->fc1_b, other->fc2_w, other->fc2_b, other->mean_w, other->mean_b, other->mean_b, nullptr, nullptr, QR_ACTOR_TANH_MEAN};  // (log_std: as in actor_grad_launch)
+  a.obs_other = b->obs[1 - k]; a.action_other = other ? nullptr : g->action_other;
+  a.od_other = b->obs_dim[1 - k]; a.ad_other = b->action_dim[1 - k];
+  a.col_own = k ? b->obs_dim[0] : 0; a.col_other = k ? 0 : b->obs_dim[0];
+  a.acol_own = c->obs_dim + (k ? b->action_dim[0] : 0); a.acol_other = c->obs_dim + (k ? 0 : b->action_dim[0]);
+  a.in_dim = c->obs_dim + c->action_dim;
+  DpgReduceArgs r{};
+  r.stats = g->stats; r.B = (double)b->batch; r.BA = r.B * own->action_dim; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
+  float* const grads[6] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b};
+  static void (*const kernel[3])(CtdeDpgArgs) = {nullptr, ctde_dpg_actor_kernel<15, 16, 4>, ctde_dpg_actor_kernel<3, 4, 1>};
+  const float *o1 = other ? other->fc1_w : nullptr, *o2 = other ? other->fc1_b : nullptr, *o3 = other ? other->fc2_w : nullptr,
+              *o4 = other ? other->fc2_b : nullptr, *o5 = other ? other->mean_w : nullptr, *o6 = other ? other->mean_b : nullptr;
+  return actor_grad_launch(own, a, r, false, true, supplied_ok,
+                           {c->fc1_w, c->fc1_b, c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, g->stats, g->noise, g->nominal, b->obs[0], b->obs[1],
+                            b->obs_next[k], g->action_other, o1, o2, o3, o4, o5, o6}, grads, 6,
+                           g->workspace_bytes, g->max_workgroups, kDpgNP, kernel, dpg_reduce_kernel, 16, stream);
+}
+
 constexpr int kSacNP[3] = {SacLayout<23, 16, 4>::NP, SacLayout<15, 16, 4>::NP, SacLayout<3, 4, 1>::NP};
 
 // (actor_grad_launch does not fit: it takes the tanh-of-mean form with six or seven tensors and no second critic; the order of the
@@ -577,6 +627,16 @@ int64_t qr_dpg_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_
   const int size = qr::actor_size(obs_dim, hidden_dim, action_dim);
   if (size < 0 || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
   return qr::ppo_grid(batch, max_workgroups) * qr::kDpgNP[size] * (int64_t)sizeof(double);
+}
+
+int qr_ctde_dpg_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic, const QrCtdeTransitions* batch,
+                           const QrCtdeDpgGrad* grad, void* stream) {
+  return qr::do_ctde_dpg_actor(actor_0, actor_1, critic, batch, grad, stream);
+}
+
+int64_t qr_ctde_dpg_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups) {
+  if ((agent != 0 && agent != 1) || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * qr::kDpgNP[1 + agent] * (int64_t)sizeof(double);
 }
 
 int qr_soft_update(const QrSoftUpdate* update, void* stream) { return qr::do_soft_update(update, stream); }

@@ -13,6 +13,10 @@ twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
 The critic half also exists for ONE centralized (CTDE) twin critic over the two agents of a Decoupled buffer (td3.py:124-137, 157-158):
 `td3_target_ctde` (qr_ctde_twinq_target), `twinq_grad_ctde` (qr_ctde_twinq_grad) and `td3_critic_loss_ctde` on live modules.  The
 critic's row [obs_0 | obs_1 | act_0 | act_1] is formed inside the kernels from the agents' tensors; nothing is concatenated.
+So does agent k's actor half under that critic (td3.py:180-196): `dpg_actor_grad_ctde` (qr_ctde_dpg_actor_grad) and, on live modules,
+`td3_actor_loss_ctde` — the other agent's actor runs forward only inside the kernel (or its action is supplied), and only agent k's
+six gradients are produced.  A written-out CTDE iteration is `td3_critic_loss_ctde`, optimiser, `td3_actor_loss_ctde`, optimiser,
+`soft_update`, with no autograd in it.
 """
 from __future__ import annotations
 
@@ -520,11 +524,7 @@ def td3_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
     are cached on the buffer.  The optimiser step follows on these .grad tensors (`optim.DeviceAdamW`, or torch's), then
     `soft_update`."""
     layers = [actor_module.fc1, actor_module.fc2, actor_module.fc3]
-    grads = {}
-    for n, p in zip(_lib.DPG_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
+    grads = _actor_grads(actor_module)
     actor = ActorParams(*(t.data for l in layers for t in (l.weight, l.bias)), None)
     critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
     B = buffer.capacity if index is None else index.numel()
@@ -538,6 +538,157 @@ def td3_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
     _, stats = dpg_actor_grad(actor, critic, buffer.obs[k], buffer.obs_next[k], index, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                               max_action=max_action, noise=noise, nominal=nominal, grads=grads, stats=own_stats if stats is None else stats,
                               workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def dpg_actor_workspace_bytes_ctde(k: int, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `dpg_actor_grad_ctde` call needs for agent k (qr_ctde_dpg_actor_workspace_bytes): `dpg_actor_workspace_bytes`'
+    figure for CTDE_ACTOR_DIMS[k]."""
+    n = _lib.load().qr_ctde_dpg_actor_workspace_bytes(int(k), int(critic_hidden), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_ctde_dpg_actor_workspace_bytes")
+    return int(n)
+
+
+def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action, noise, nominal):
+    """`dpg_actor_grad_ctde`'s checks up to the outputs: returns (shapes of agent k's tensors, B, rows, the four widths, obs_next[k])."""
+    dev = critic.device
+    D, A, H = critic.dims
+    if k not in (0, 1):
+        raise ValueError(f"{what}: k must be 0 or 1 (two agents), got {k}")
+    o = 1 - k
+    actors = tuple(actors) if actors is not None else ()
+    if len(actors) != 2 or actors[k] is None:
+        raise ValueError(f"{what}: actors must be a pair, one entry per agent; agent {k}'s is required")
+    if (actors[o] is None) == (action_other is None):
+        raise ValueError(f"{what}: give either agent {o}'s actor or action_other, not " + ("both" if action_other is not None else "neither"))
+    obs = tuple(obs) if obs is not None else ()
+    if len(obs) != 2:
+        raise ValueError(f"{what}: obs must be a pair, one tensor per agent")
+    for m in range(2):
+        if obs[m] is None or obs[m].dim() != 2 or obs[m].shape[1] < 1:
+            raise ValueError(f"{what}: obs[{m}] must be a contiguous float32 [rows, width] tensor on {dev}")
+    od = [x.shape[1] for x in obs]
+    rows = _rows(obs[0], od[0], dev, what, "obs[0]")
+    if _rows(obs[1], od[1], dev, what, "obs[1]") != rows:
+        raise ValueError(f"{what}: obs[1] must have obs[0]'s {rows} rows")
+    _check_index(index, dev, what)
+    B = rows if index is None else index.numel()
+    ad = [0, 0]
+    ad[k] = actors[k].dims[2]
+    if action_other is not None:
+        if action_other.dtype != torch.float32 or action_other.device != dev or action_other.dim() != 2 or action_other.shape[0] != B \
+                or action_other.shape[1] < 1 or not action_other.is_contiguous():
+            raise ValueError(f"{what}: action_other must be a contiguous float32 [{B}, width] tensor on {dev}")
+        ad[o] = action_other.shape[1]
+    else:
+        ad[o] = actors[o].dims[2]
+    if sum(od) != D or sum(ad) != A:
+        raise ValueError(f"{what}: the widths of obs {od[0]}+{od[1]} / action {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
+    form = (_lib.ACTOR_TANH_MEAN, False, "the actors must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
+    shapes = None
+    for m in (k, o):
+        if actors[m] is None:
+            continue
+        s = _check_actor(actors[m], od[m], ad[m], dev, what, *form)
+        if actors[m].dims != CTDE_ACTOR_DIMS[m]:
+            raise ValueError(f"{what}: actor {m} must have the sizes {CTDE_ACTOR_DIMS[m]} (obs, hidden, action), got {actors[m].dims}")
+        shapes = s if m == k else shapes
+    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
+        if not 0.0 <= float(v) < float("inf"):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    nxt = None
+    if lam_T != 0:
+        nxt = tuple(obs_next)[k] if obs_next is not None and len(tuple(obs_next)) == 2 else None
+        if nxt is None:
+            raise ValueError(f"{what}: obs_next must be a pair whose entry {k} is given when lam_T != 0")
+        if _rows(nxt, od[k], dev, what, f"obs_next[{k}]") != rows:
+            raise ValueError(f"{what}: obs_next[{k}] must have obs's {rows} rows")
+    if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
+        raise ValueError(f"{what}: noise [{od[k]}] is required when lam_S != 0, nominal [{ad[k]}] when lam_M != 0")
+    _vector(noise, od[k], dev, what, "noise")
+    _vector(nominal, ad[k], dev, what, "nominal")
+    return shapes, B, rows, od, ad, nxt
+
+
+def dpg_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index: Optional[torch.Tensor] = None, *, k: int = 0,
+                        action_other: Optional[torch.Tensor] = None, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6,
+                        max_action: float = 1.0, noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None,
+                        grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                        max_workgroups: int = 0):
+    """Agent k's TD3 actor loss under the centralized (CTDE) critic of two agents and its gradients (qr_ctde_dpg_actor_grad; td3.py:180-196
+    without the equivariant term, with algos/policy_regularization.py), c = clamp to +-max_action, i = index[j], a_m = c(pi_m(obs[m][i])):
+        loss_k = -mean_j Q1([obs[0][i] | obs[1][i] | a_0 | a_1]) + lam_T mse(a_k, c(pi_k(obs_next[k][i])))
+                 + lam_S mse(a_k, c(pi_k(obs[k][i] + noise))) + lam_M mse(a_k, nominal)
+    — no autograd, nothing concatenated.  actors: the pair of `ActorParams` of the sizes CTDE_ACTOR_DIMS; the other agent's runs forward
+    only inside the kernel and gets NO gradient (the reference leaves one in its .grad, which that agent zeroes before reading).  Or
+    actors[1 - k] None with action_other float32 [B, A_other] by minibatch position, used as it is (no clamp): then the other agent's
+    widths are free as long as all four add up to the critic's.  obs, obs_next: pairs of contiguous float32 [rows, D_m]; obs_next[k] is
+    needed when lam_T != 0, obs_next[1 - k] never.  noise [D_k], nominal [A_k], index, grads, stats, workspace, max_workgroups and
+    the return value (grads of agent k's six tensors, stats [4]): `dpg_actor_grad`'s."""
+    what = "dpg_actor_grad_ctde"
+    dev = critic.device
+    shapes, B, rows, od, ad, nxt = _ctde_actor_launch(what, actors, critic, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action,
+                                                      noise, nominal)
+    grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
+                                            lambda: dpg_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups), size_given=False)
+    if workspace is None:
+        return grads, stats
+    b = _lib.ctde_transitions(obs=obs, obs_next=(nxt, None) if k == 0 else (None, nxt), index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad)
+    g = _lib.ctde_dpg_grad_args(grads, stats, noise if lam_S != 0 else None, nominal if lam_M != 0 else None, workspace, agent=k,
+                                action_other=action_other, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
+    q = critic.as_c()
+    p = [None if a is None else a.as_c() for a in actors]
+    for c in p:
+        if c is not None:
+            c.log_std = None
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_ctde_dpg_actor_grad(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
+                                                torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ctde_dpg_actor_grad")
+    return grads, stats
+
+
+def _actor_grads(actor_module) -> dict:
+    """The live actor's six .grad tensors by name, made where there is none."""
+    grads = {}
+    for n, p in zip(_lib.DPG_GRAD_NAMES, (t for l in (actor_module.fc1, actor_module.fc2, actor_module.fc3) for t in (l.weight, l.bias))):
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        grads[n] = p.grad
+    return grads
+
+
+def td3_actor_loss_ctde(actor_modules, critic_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                        lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, noise: Optional[torch.Tensor] = None,
+                        nominal: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """`td3_actor_loss` for agent k of a two-agent `buffer` under the centralized (CTDE) critic: `dpg_actor_grad_ctde` on the two live
+    actors (attributes fc1, fc2, fc3) and `critic_module` (MLP_Critic_CTDE, of which Q1 is read); fills
+    `actor_modules[k].fc{1,2,3}.{weight,bias}.grad` in place, as `loss.backward()` after `zero_grad()` leaves them, and does not touch
+    `actor_modules[1 - k]` (neither its tensors nor its .grad).  noise, nominal: agent k's.  Returns stats (stats[0] = the loss).  The
+    workspace and stats are cached on the buffer under a key of their own: from the second call on with an unchanged B nothing is
+    allocated.  The optimiser step stays the caller's."""
+    what = "td3_actor_loss_ctde"
+    if not isinstance(buffer, ReplayBuffer) or buffer.n_agents != 2:
+        raise ValueError(f"{what}: buffer must be a two-agent ReplayBuffer")
+    if k not in (0, 1):
+        raise ValueError(f"{what}: k must be 0 or 1 (two agents), got {k}")
+    actor_modules = tuple(actor_modules)
+    if len(actor_modules) != 2:
+        raise ValueError(f"{what}: actor_modules must be the pair of both agents' actors")
+    grads = _actor_grads(actor_modules[k])
+    actors = [ActorParams(*(t.data for l in (m.fc1, m.fc2, m.fc3) for t in (l.weight, l.bias)), None) for m in actor_modules]
+    critic = QCriticParams.from_module(critic_module, sum(buffer.action_dims))
+    B = buffer.capacity if index is None else index.numel()
+    key = ("actor_ctde", k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = dpg_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.float32, device=dev))
+    workspace, own_stats = hit
+    _, stats = dpg_actor_grad_ctde(actors, critic, buffer.obs, buffer.obs_next, index, k=k, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                                   max_action=max_action, noise=noise, nominal=nominal, grads=grads, stats=own_stats if stats is None else stats,
+                                   workspace=workspace, max_workgroups=max_workgroups)
     return stats
 
 

@@ -501,6 +501,28 @@ def qr_ctde_twinq_grad(critic: List[torch.Tensor], obs0: torch.Tensor, obs1: tor
                     grads=dict(zip(_lib.TWINQ_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_ctde_dpg_actor_grad", mutates_args=("grads", "stats"))
+def qr_ctde_dpg_actor_grad(actor0: List[torch.Tensor], actor1: List[torch.Tensor], critic: List[torch.Tensor], agent: int, obs0: torch.Tensor,
+                           obs1: torch.Tensor, obs_next: Optional[torch.Tensor], index: Optional[torch.Tensor], action_other: Optional[torch.Tensor],
+                           noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor, lam_T: float,
+                           lam_S: float, lam_M: float, max_action: float, max_workgroups: int = 0) -> None:
+    """Agent `agent`'s TD3 actor loss under the centralized critic of two agents and its six gradients (qr_ctde_dpg_actor_grad).  actor0,
+    actor1: six tensors each, fc1_w .. fc3_b; the other agent's may be an empty list with action_other.  critic: the centralized twin
+    critic's twelve; obs_next: agent `agent`'s own; grads: that agent's six.  Everything else as td3.dpg_actor_grad_ctde."""
+    from .policy import ActorParams
+    from .td3 import dpg_actor_grad_ctde
+    _gpu(stats)
+    if len(actor0) not in (0, 6) or len(actor1) not in (0, 6) or len(grads) != 6:
+        raise ValueError("a TD3 actor and its gradients are 6 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b")
+    pair = [ActorParams(*a, None) if a else None for a in (actor0, actor1)]
+    if agent not in (0, 1) or pair[agent] is None:
+        raise ValueError("agent must be 0 or 1 and that agent's actor given")
+    a_other = action_other.shape[-1] if action_other is not None else (pair[1 - agent].dims[2] if pair[1 - agent] is not None else 0)
+    dpg_actor_grad_ctde(pair, _qcritic_params(critic, pair[agent].dims[2] + a_other), (obs0, obs1), (obs_next, None) if agent == 0 else (None, obs_next),
+                        index, k=agent, action_other=action_other, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action, noise=noise,
+                        nominal=nominal, grads=dict(zip(_lib.DPG_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_actor_grad", mutates_args=("grads", "stats", "alpha_grad"))
 def qr_sac_actor_grad(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs: torch.Tensor, obs_next: Optional[torch.Tensor],
                       index: Optional[torch.Tensor], eps: Optional[torch.Tensor], eps_reg: Optional[torch.Tensor], eps_next: Optional[torch.Tensor],

@@ -824,6 +824,57 @@ int qr_ctde_twinq_grad(const QrQCritic* critic, const QrCtdeTransitions* batch, 
 /* Bytes of workspace qr_ctde_twinq_grad needs (in_dim = the four widths' sum, >= 4): qr_twinq_workspace_bytes's figure. */
 int64_t qr_ctde_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t batch, int32_t max_workgroups);
 
+/* The actor half of one TD3 minibatch update for agent k of TWO agents under ONE centralized twin critic (the CTDE branch of
+ * TD3.train, algos/td3/td3.py:180-196, without the equivariant term, with algos/policy_regularization.py), read from the two agents'
+ * buffers in place, without autograd.  With j the minibatch position, i = index[j], c(.) = clamp to +-max_action and m = 0, 1:
+ *     a_m     = c(pi_m(obs_m[i]))                             pi = tanh(fc3(relu(fc2(relu(fc1 x)))))     (MLP_Actor_TD3)
+ *     loss_k  = -(1/B) sum_j Q1([obs_0[i] | obs_1[i] | a_0 | a_1])
+ *               + lam_T mse(a_k, c(pi_k(obs_next_k[i]))) + lam_S mse(a_k, c(pi_k(obs_k[i] + noise))) + lam_M mse(a_k, nominal)
+ * and loss_k.backward()'s gradients for agent k's six actor tensors: through all three evaluations of pi_k and through Q1 into a_k
+ * alone, dQ/da_k = fc1_w[:, D + off_k .. D + off_k + action_dim[k])^T dz1 with D = obs_dim[0] + obs_dim[1], off_0 = 0 and
+ * off_1 = action_dim[0].  The other agent's action enters Q1 as a VALUE only.  (In the reference that agent's actor receives a .grad
+ * from this backward pass too; it zeroes it in its own zero_grad() before anything reads it, and neither clip_grad_norm_ nor agent k's
+ * optimiser touches it.  Here no gradient for agent 1-k exists and nothing of that actor is written.)
+ * noise [obs_dim[k]] (ONE row, broadcast), nominal [action_dim[k]], the coefficients and mse are qr_dpg_actor_grad's: a lam_* equal
+ * to 0 skips that term's passes and reads none of its inputs.
+ *   agent: k, 0 or 1.  Agent k's actor is a QrActor of the QR_ACTOR_TANH_MEAN form of the Decoupled wrapper's size for that place:
+ *   (15,16,4) for agent 0, (3,4,1) for agent 1, equal to the batch's obs_dim[k] and action_dim[k]; its log_std is not read.
+ *   The other agent's action, one of two forms:
+ *     both actors given, action_other NULL: the pair has exactly the sizes (15,16,4) and (3,4,1) and the batch their widths; pi_{1-k}
+ *       runs forward only inside the kernel and its output is clamped.
+ *     the actor of agent 1-k NULL, action_other [batch][action_dim[1-k]] float32 by minibatch position: used as it is (no clamp);
+ *       the other agent's obs_dim and action_dim are free as long as the four widths add up to the critic's (<= 28).
+ *     Both actors AND action_other: QR_E_KIND (the form is ambiguous), reported with the other QR_E_KIND causes, before any size.
+ *   critic: a QrQCritic with the summed widths; only fc1 .. fc3 (Q1) are read, fc4 .. fc6 may be NULL.
+ *   batch: a QrCtdeTransitions, of which obs[0], obs[1], index and, with lam_T != 0, obs_next[k] are read.
+ * Outputs, overwritten: agent k's six gradient tensors and stats [4] = loss_k, the mean of Q1, the share of agent k's B x action_dim[k]
+ * components of pi_k(obs_k) with |pi| > max_action (an exact count), and lam_T L_T + lam_S L_S + lam_M L_M.
+ * Two launches, the partial vectors, the float64 reduction in a fixed order and the grid rule are qr_dpg_actor_grad's: the same inputs
+ * and grid give the same bits (no atomics); grid = min(ceil(batch / 64), max_workgroups), max_workgroups = 0: 1024. */
+typedef struct QrCtdeDpgGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *mean_w, *mean_b, *stats;
+  const float* noise;      const float* nominal;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_ctde_dpg_actor_workspace_bytes(...); 8-byte aligned */
+  float lam_T, lam_S, lam_M, max_action;
+  int32_t max_workgroups, reserved0;
+  int32_t agent, reserved1;                           /* k; reserved1 must be 0 */
+  const float* action_other;
+} QrCtdeDpgGrad;
+/* In this order: QR_E_NULL for a NULL critic, batch or grad struct; QR_E_KIND for an actor (either) with squash != QR_ACTOR_TANH_MEAN
+ * or a log_std head, or both actors together with action_other; QR_E_SIZE for agent outside 0..1, critic widths outside their ranges,
+ * widths < 1, widths that do not add up to the critic's or exceed 28, reserved fields != 0, agent k's actor not of its place's size or
+ * different from the batch's widths, in the both-actors form a pair other than (15,16,4), (3,4,1), batch < 1, rows < 1,
+ * max_workgroups < 0, a negative or non-finite max_action or lam_*; QR_E_NULL for agent k's actor NULL, the other actor and
+ * action_other both NULL, a NULL actor weight (agent k's; the other's where it is given), Q1 weight, obs[0], obs[1], output or
+ * workspace pointer (index optional; obs_next[k], noise, nominal as above); QR_E_ALIGN for a float pointer that is not 4-byte aligned
+ * or an index / workspace pointer that is not 8-byte aligned; QR_E_SIZE for a workspace that is too small.  Nothing is launched on an
+ * error. */
+int qr_ctde_dpg_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic, const QrCtdeTransitions* batch,
+                           const QrCtdeDpgGrad* grad, void* stream);
+/* Bytes of workspace qr_ctde_dpg_actor_grad needs for agent 0 (the (15,16,4) actor) or 1 (the (3,4,1) actor), this critic width, batch
+ * and max_workgroups: qr_dpg_actor_workspace_bytes' figure for that actor.  QR_E_SIZE (< 0) where the entry would refuse them. */
+int64_t qr_ctde_dpg_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

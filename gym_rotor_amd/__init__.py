@@ -17,6 +17,7 @@ from .td3 import td3_critic_loss_ctde, td3_target_ctde, twinq_grad_ctde  # noqa:
 from .td3 import dpg_actor_grad_ctde, dpg_actor_workspace_bytes_ctde, td3_actor_loss_ctde  # noqa: F401
 from .sac import sac_actor_grad, sac_actor_loss, sac_actor_workspace_bytes, sac_critic_loss, sac_target  # noqa: F401
 from .sac import sac_critic_loss_ctde, sac_target_ctde  # noqa: F401
+from .sac import sac_actor_grad_ctde, sac_actor_loss_ctde, sac_actor_workspace_bytes_ctde  # noqa: F401
 from .evaluate import EvalResult, PopulationResult, evaluate_policy, evaluate_population  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)
 

@@ -38,7 +38,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target",
            "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes",
            "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
-           "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes")
+           "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
+           "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -256,6 +257,11 @@ class QrCtdeDpgGrad(C.Structure):
     _fields_ = QrDpgGrad._fields_ + [("agent", C.c_int32), ("reserved1", C.c_int32), ("action_other", C.c_void_p)]
 
 
+class QrCtdeSacActorGrad(C.Structure):
+    _fields_ = QrSacActorGrad._fields_ + [("agent", C.c_int32), ("reserved1", C.c_int32), ("eps_logp", C.c_void_p), ("eps_other", C.c_void_p),
+                                          ("action_other", C.c_void_p)]
+
+
 def _pair(x):
     x = (None, None) if x is None else x
     return (C.c_void_p * 2)(ptr(x[0]), ptr(x[1]))
@@ -291,6 +297,15 @@ def ctde_dpg_grad_args(grads, stats, noise, nominal, workspace, *, agent, action
     d = dpg_grad_args(grads, stats, noise, nominal, workspace, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
     g = QrCtdeDpgGrad(*[getattr(d, n) for n, _ in QrDpgGrad._fields_])
     g.agent, g.reserved1, g.action_other = int(agent), 0, ptr(action_other)
+    return g
+
+
+def ctde_sac_actor_grad_args(grads, stats, workspace, *, agent, action_other, eps_logp, eps_other, **kw) -> QrCtdeSacActorGrad:
+    """QrCtdeSacActorGrad of one qr_ctde_sac_actor_grad launch: sac_actor_grad_args' fields (kw; eps = agent k's first draw), the agent k,
+    its second draw, the other agent's draw and the other agent's action (each or None)."""
+    d = sac_actor_grad_args(grads, stats, workspace, **kw)
+    g = QrCtdeSacActorGrad(*[getattr(d, n) for n, _ in QrSacActorGrad._fields_])
+    g.agent, g.reserved1, g.eps_logp, g.eps_other, g.action_other = int(agent), 0, ptr(eps_logp), ptr(eps_other), ptr(action_other)
     return g
 
 
@@ -463,6 +478,10 @@ def load():
     lib.qr_ctde_dpg_actor_grad.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeDpgGrad), C.c_void_p]
     lib.qr_ctde_dpg_actor_workspace_bytes.restype = C.c_int64
     lib.qr_ctde_dpg_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_ctde_sac_actor_grad.restype = C.c_int
+    lib.qr_ctde_sac_actor_grad.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeSacActorGrad), C.c_void_p]
+    lib.qr_ctde_sac_actor_workspace_bytes.restype = C.c_int64
+    lib.qr_ctde_sac_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

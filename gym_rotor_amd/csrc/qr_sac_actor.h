@@ -5,6 +5,8 @@
 //       loss = mean_j (alpha logp_j - min(Q1, Q2)(obs[i], a_j)) + lam_T mse(r, rn) + lam_S mse(r, rp) + lam_M mse(r, nominal)
 //   with FOUR independent samples of pi (the loss pass; the regulariser's own sample r; on obs_next; on obs + noise), its gradients for
 //   MLP_Actor_SAC's eight tensors, and what alpha's own update needs, -(target_entropy + mean_j logp_j).
+//   ctde_sac_actor_kernel + sac_actor_reduce_kernel (qr_ctde_sac_actor_grad)   the same for agent k of two under ONE centralized (CTDE)
+//   twin critic (sac.py:175-203): the other agent's action as a value, logp from a second sample of agent k; a FOURTH copy of the walk.
 // The pieces are shared: the actor's layers, MFMA weight gradients, delta tile and emit are PpoNet's static pieces (qr_ppo.h), a critic's
 // forward pass and dQ/da are dpg_q1_half (qr_td3_actor.h), the reduction is reduce16_entries / block_sum_column.  New here:
 //   - the two-headed passes (SacNet): forward keeps the pre-tanh mean and log_std_linear's output; backward puts dmean in columns
@@ -40,6 +42,20 @@ struct SacActorArgs {
   float alpha, max_action;
   float lam_T, lam_S, lam_M;         // only their being zero is read here (wave-uniform branches)
   float inv_b, c_T, c_S, c_M;        // 1 / B and 2 lam / (B A): the per-row factors of the gradient
+};
+
+// The centralized (CTDE) form for agent k of two (qr_ctde_sac_actor_grad): SacActorArgs' members are agent k's (w = pi_k, obs / obs_next /
+// noise / nominal its own, eps[0] its first draw), q = the centralized twin critic whose row is [obs_0 | obs_1 | a_0 | a_1].
+struct CtdeSacActorArgs : SacActorArgs {
+  ActorW other;                      // pi_{1-k}, both heads, forward only; read when action_other is NULL
+  const float* obs_other;            // [>= rows][od_other]
+  const float* action_other;         // [B][ad_other] by minibatch position, used as it is, or NULL: tanh of pi_{1-k}'s sample
+  const float* eps_other;            // [B][ad_other] by minibatch position: the other agent's draw, or NULL: zeros
+  const float* eps_logp;             // [B][A] by minibatch position: agent k's SECOND draw (logp), or NULL: one sample, drawn with eps[0]
+  int32_t od_other, ad_other;        // the other agent's widths
+  int32_t col_own, col_other;        // first column of each agent's observation in the critic's row
+  int32_t acol_own, acol_other;      // first column of each agent's action: D + off_k, D + off_{1-k}
+  int32_t in_dim;                    // the row's width, <= 28
 };
 
 // One workgroup's partial vector: PpoLayout's six weight and bias tensors, log_std_linear's two, then the seven sums of `stats`:
@@ -392,6 +408,272 @@ __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
     P[Y::O_ST + lane] = s;
   }
 }
+
+// Agent k of two under one centralized twin critic (qr_ctde_sac_actor_grad): <15, 16, 4> for k = 0, <3, 4, 1> for k = 1.
+// sac_actor_kernel's walk in its two-agent form, as dpg_walk's CT form (qr_td3_actor.h).  The critics' tile takes the other
+// agent's observation rows at their columns (stage_rows, a second pointer array) and its action: supplied by minibatch position, or
+// pi_{1-k} forward only on the lane's own row from LDS (SacNet::forward of the pair's other size), sampled with eps_other, tanh, no
+// clamp, before agent k's own pass so that it holds no register across the critics' phase.  Agent k's observation and action go to
+// their own columns, `was` is fc1_w's columns of a_k, the critics' row is in_dim wide.  With eps_logp the reference's SECOND sample
+// of pi_k carries the entropy term: it shares the loss pass's forward (same row, same mean and raw log_std), its deltas (ga = 0,
+// gl = alpha / B) are formed right after it and wait in LDS (park) across the critics' phase, then add to the first sample's (whose
+// gl is then 0) before the ONE backward pass; logp and alpha's gradient are the second sample's.  Without it: the one-agent arithmetic.
+// The other agent's action is a VALUE: no gradient for agent 1-k is produced and nothing of that actor is written (the reference's
+// backward pass leaves one in that actor's .grad, which that agent zeroes before anything reads it; include/quadrotor_hip.h).
+// This body is a FOURTH copy of the tile walk: as ONE force-inlined function with the form as a compile-time argument, dpg_walk's
+// way, the one-agent kernels came out with 24 and 48 bytes more scratch per lane, so sac_actor_kernel above is
+// textually the parent's and a fix to its walk has to be made here too.
+template <int D, int H, int A>
+__global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorArgs a) {
+  using Net = PpoNet<D, H, A>;
+  using SN = SacNet<D, H, A>;
+  using PY = PpoLayout<D, H, A>;
+  using Y = SacLayout<D, H, A>;
+  constexpr int XS = Net::XS, HS = Net::HS;
+  __shared__ float sm[Net::SM], sl[SN::SL];
+  __shared__ float xs[64 * XS], hs[64 * HS], ds[64 * kPpoDelta];
+  __shared__ __attribute__((aligned(8))) float qs[64 * kMgX];  // the critics' input tile; at the end: the lanes' sums (float64)
+  __shared__ float w1s[TwinQL1::SIZE], w2ts[64 * 64], svec[kTqVec], was[64 * 4], dq[2][64 * kDpgQ];
+  __shared__ const float* src[64];
+  static_assert(64 * Y::NS * sizeof(double) <= sizeof(float) * 64 * kMgX, "the sums fit the critics' tile");
+  constexpr int OD = D == 15 ? 3 : 15, OH = D == 15 ? 4 : 16, OA = D == 15 ? 1 : 4;  // the Decoupled pair's other half
+  using ONet = PpoNet<OD, OH, OA>;
+  using OSN = SacNet<OD, OH, OA>;
+  __shared__ const float* src1[64];
+  __shared__ float osm[ONet::SM], osl[OSN::SL];
+  __shared__ float park[2 * A * 64];  // the second sample's dmean, dls: [2 A][64 lanes]
+  static_assert(sizeof(sm) + sizeof(sl) + sizeof(xs) + sizeof(hs) + sizeof(ds) + sizeof(qs) + sizeof(w1s) + sizeof(w2ts) + sizeof(svec) +
+                        sizeof(was) + sizeof(dq) + sizeof(src) + sizeof(src1) + sizeof(osm) + sizeof(osl) + sizeof(park) <= 64 * 1024 - 64,
+                "static LDS stays under 64 KB");
+  const int lane = threadIdx.x;
+  const int QH = a.hidden;
+  const int IN = a.in_dim, xcol = a.col_own, acol = a.acol_own;  // the critics' width, agent k's observation and action columns in their row
+  const bool two = a.eps_logp != nullptr;                        // the entropy term comes from a second sample
+  SN net;
+  net.zero();
+  {
+    PpoArgs p{};
+    p.w = a.w;
+    p.noise = a.noise;
+    Net::fill(sm, p, lane);
+    SN::fill(sl, a.w, lane);
+  }
+  if (!a.action_other) {
+    PpoArgs p{};
+    p.w = a.other;
+    ONet::fill(osm, p, lane);
+    OSN::fill(osl, a.other, lane);
+  }
+  for (int i = lane; i < 64 * XS; i += 64) xs[i] = (i % XS == D) ? 1.0f : 0.0f;  // the ones column; the rest of the padding stays zero
+  for (int i = lane; i < 64 * HS; i += 64) hs[i] = (i % HS == H) ? 1.0f : 0.0f;
+  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns >= IN stay zero
+  __syncthreads();
+  const float alpha = a.alpha_dev ? a.alpha_dev[0] : a.alpha;
+  const bool any_reg = a.lam_T != 0.0f || a.lam_S != 0.0f || a.lam_M != 0.0f;
+  float nominal[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) nominal[j] = a.nominal ? a.nominal[j] : 0.0f;
+  double st[Y::NS];
+#pragma unroll
+  for (int q = 0; q < Y::NS; ++q) st[q] = 0.0;
+
+  const int64_t tiles = (a.B + 63) / 64;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t row0 = tile * 64;
+    const bool active = row0 + lane < a.B;
+    int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
+    i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
+    auto noise_row = [&](int which, float (&e)[A]) {  // by minibatch position; NULL: zeros through the same code
+      const float* p = a.eps[which];
+#pragma unroll
+      for (int j = 0; j < A; ++j) e[j] = (p && active) ? p[(row0 + lane) * A + j] : 0.0f;
+    };
+    src[lane] = active ? a.obs + i * D : nullptr;
+    src1[lane] = active ? a.obs_other + i * a.od_other : nullptr;
+    __syncthreads();
+    ppo_stage<D, XS>(xs, src, lane);
+    stage_rows(qs, kMgX, src1, a.od_other, a.col_other, lane);
+    __syncthreads();
+    {  // the other agent's action: a value only
+      float* qa = qs + lane * kMgX + a.acol_other;
+      if (a.action_other) {
+        for (int f = 0; f < a.ad_other; ++f) qa[f] = active ? a.action_other[(row0 + lane) * a.ad_other + f] : 0.0f;
+      } else {
+        float xo[OD], g1[OH], g2[OH], mo[OA], lo[OA], eo[OA];
+#pragma unroll
+        for (int k = 0; k < OD; ++k) xo[k] = qs[lane * kMgX + a.col_other + k];
+        OSN::forward(osm, osl, xo, g1, g2, mo, lo);
+#pragma unroll
+        for (int f = 0; f < OA; ++f) eo[f] = (a.eps_other && active) ? a.eps_other[(row0 + lane) * OA + f] : 0.0f;
+        SacRow<OA> so;
+        so.sample(mo, lo, eo);
+#pragma unroll
+        for (int f = 0; f < OA; ++f) qa[f] = so.act[f];  // no clamp, as agent k's own
+      }
+    }
+
+    // ---- the loss pass
+    {
+      float x[D], h1[H], h2[H], mean[A], lsr[A], e[A];
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
+      SN::forward(sm, sl, x, h1, h2, mean, lsr);
+      noise_row(0, e);
+      SacRow<A> s;
+      s.sample(mean, lsr, e);
+      if (active) {
+        if (!two) st[1] += (double)s.logp;
+#pragma unroll
+        for (int j = 0; j < A; ++j) st[5] += s.in[j] ? 0.0 : 1.0;
+      }
+      if (two) {  // the second sample of the same forward pass: logp, and its deltas into LDS
+        float e2[A], g0[A], dm2[A], dl2[A];
+#pragma unroll
+        for (int j = 0; j < A; ++j) { e2[j] = active ? a.eps_logp[(row0 + lane) * A + j] : 0.0f; g0[j] = 0.0f; }
+        SacRow<A> s2;
+        s2.sample(mean, lsr, e2);
+        if (active) st[1] += (double)s2.logp;
+        s2.deltas(g0, alpha * a.inv_b, active, dm2, dl2);
+#pragma unroll
+        for (int j = 0; j < A; ++j) { park[j * 64 + lane] = dm2[j]; park[(A + j) * 64 + lane] = dl2[j]; }
+      }
+      // the critics' phase needs the registers: x waits in its tile (and in qs), pi's activations in the two tiles that are free
+      // until the backward pass
+#pragma unroll
+      for (int k = 0; k < D; ++k) qs[lane * kMgX + xcol + k] = x[k];
+#pragma unroll
+      for (int u = 0; u < H; ++u) { hs[lane * HS + u] = h1[u]; ds[lane * kPpoDelta + u] = h2[u]; }
+#pragma unroll
+      for (int j = 0; j < A; ++j) qs[lane * kMgX + acol + j] = s.act[j];  // no clamp on the loss pass's action
+#pragma unroll 1
+      for (int n = 0; n < 2; ++n) {
+        __syncthreads();  // the previous critic's reads are done
+        float a2[4][4][4];
+        {
+          float a2t[4][4][4];
+          load_fc2(a2, a2t, a.q[n].fc2_w, QH, lane);
+#pragma unroll
+          for (int k = 0; k < 64; ++k) w2ts[64 * k + lane] = a2t[k >> 4][(k >> 2) & 3][k & 3];
+        }
+        twinq_fill_small(w1s, svec, a.q[n], IN, QH, lane);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? a.q[n].fc1_w[lane * IN + acol + j] : 0.0f;
+        const float bias3 = a.q[n].fc3_b[0];
+        __syncthreads();
+#pragma unroll 1
+        for (int half = 0; half < 2; ++half)
+          dpg_q1_half<A>(a2, lds_here(w2ts), qs + 32 * half * kMgX, lds_here(w1s), lds_here(svec), was, dq[n] + 32 * half * kDpgQ, bias3, lane);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < H; ++u) { h1[u] = hs[lane * HS + u]; h2[u] = ds[lane * kPpoDelta + u]; }
+      // min(Q1, Q2): a row's gradient goes to the smaller critic; torch gives each half on an exact tie
+      const float q1 = dq[0][lane * kDpgQ + 4], q2 = dq[1][lane * kDpgQ + 4];
+      const float w2 = q2 < q1 ? 1.0f : (q2 == q1 ? 0.5f : 0.0f);
+      if (active) {
+        st[0] += (double)fminf(q1, q2);
+        st[6] += q2 < q1 ? 1.0 : 0.0;
+      }
+      float ga[A], dmean[A], dls[A];
+#pragma unroll
+      for (int j = 0; j < A; ++j) {
+        const float d1 = dq[0][lane * kDpgQ + j], d2 = dq[1][lane * kDpgQ + j];
+        const float d = w2 == 1.0f ? d2 : (w2 == 0.0f ? d1 : 0.5f * d1 + 0.5f * d2);
+        ga[j] = -a.inv_b * d;  // d(-mean min Q) / da
+      }
+      s.deltas(ga, two ? 0.0f : alpha * a.inv_b, active, dmean, dls);
+      if (two) {
+#pragma unroll
+        for (int j = 0; j < A; ++j) { dmean[j] += park[j * 64 + lane]; dls[j] += park[(A + j) * 64 + lane]; }
+      }
+      net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier)
+    }
+
+    // ---- policy_regularization: its own sample r and the three smoothness terms
+    if (any_reg) {
+      float x[D], h1[H], h2[H], mean[A], lsr[A], e[A], r[A], gr[A];
+#pragma unroll
+      for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
+      SN::forward(sm, sl, x, h1, h2, mean, lsr);
+      noise_row(1, e);
+      SacRow<A> s;
+      s.sample(mean, lsr, e);
+#pragma unroll
+      for (int j = 0; j < A; ++j) {
+        r[j] = fminf(fmaxf(s.act[j], -a.max_action), a.max_action);
+        gr[j] = 0.0f;
+      }
+      if (a.lam_M != 0.0f) {
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float d = r[j] - nominal[j];
+          if (active) st[4] += (double)(d * d);
+          gr[j] = fmaf(a.c_M, d, gr[j]);
+        }
+      }
+      // a smoothness pass on other input rows y: the difference enters both ends — gr for r's pass, -c d for y's own, here
+      auto other = [&](const float (&y)[D], int which, float c, double& sum) {
+        float g1[H], g2[H], mo[A], lo[A], eo[A], go[A], dmo[A], dlo[A];
+        SN::forward(sm, sl, y, g1, g2, mo, lo);
+        noise_row(which, eo);
+        SacRow<A> so;
+        so.sample(mo, lo, eo);
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float d = r[j] - fminf(fmaxf(so.act[j], -a.max_action), a.max_action);
+          if (active) sum += (double)(d * d);
+          gr[j] = fmaf(c, d, gr[j]);
+          go[j] = fabsf(so.act[j]) <= a.max_action ? -c * d : 0.0f;
+        }
+        so.deltas(go, 0.0f, active, dmo, dlo);
+        net.backward(sm, sl, xs, hs, ds, g1, g2, dmo, dlo, lane);
+      };
+      if (a.lam_S != 0.0f) {
+        float y[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { y[k] = xs[lane * XS + k] + sm[Net::O_NOISE + k]; xs[lane * XS + k] = y[k]; }
+        other(y, 3, a.c_S, st[3]);
+      }
+      if (a.lam_T != 0.0f) {
+        src[lane] = active ? a.obs_next + i * D : nullptr;
+        __syncthreads();
+        ppo_stage<D, XS>(xs, src, lane);
+        __syncthreads();
+        float y[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) y[k] = xs[lane * XS + k];
+        other(y, 2, a.c_T, st[2]);
+      }
+      if (a.lam_S != 0.0f || a.lam_T != 0.0f) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + xcol + k];
+      }
+      float ga[A], dmean[A], dls[A];
+#pragma unroll
+      for (int j = 0; j < A; ++j) ga[j] = fabsf(s.act[j]) <= a.max_action ? gr[j] : 0.0f;
+      s.deltas(ga, 0.0f, active, dmean, dls);
+      net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier: the tiles are free for the next rows)
+    }
+  }
+
+  double* P = a.partials + (int64_t)blockIdx.x * Y::NP;
+  Net::template emit<D, Net::NB1>(P + PY::O_W1, P + PY::O_B1, net.acc1, H, lane);
+  Net::template emit<H, Net::NBH>(P + PY::O_W2, P + PY::O_B2, net.acc2, H, lane);
+  Net::template emit<H, Net::NBH>(P + PY::O_W3, P + PY::O_B3, net.acc3, A, lane);
+  SN::emit_head2(P + Y::O_LW, P + Y::O_LB, net.acc3, lane);
+  // the per-lane sums: across the lanes in lane order
+  double* red = reinterpret_cast<double*>(qs);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < Y::NS; ++q) red[lane * Y::NS + q] = st[q];
+  __syncthreads();
+  if (lane < Y::NS) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += red[l * Y::NS + lane];
+    P[Y::O_ST + lane] = s;
+  }
+}
+
 
 struct SacActorReduceArgs {
   const double* partials;   // [n_parts][np]

@@ -52,10 +52,12 @@
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel;
 //                  agent k's actor half under the centralized (CTDE) critic (qr_ctde_dpg_actor_grad): the same walk's two-agent form, ctde_dpg_actor_kernel
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
-//   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel
+//   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel;
+//                  agent k's actor half under the centralized (CTDE) twin critic (qr_ctde_sac_actor_grad): ctde_sac_actor_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
-//                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad) and target_launch (the four target entries)
+//                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
+//                  sac_actor_launch (qr_sac_actor_grad and qr_ctde_sac_actor_grad)
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -531,6 +533,55 @@ static int do_ctde_dpg_actor(const QrActor* p0, const QrActor* p1, const QrQCrit
 
 constexpr int kSacNP[3] = {SacLayout<23, 16, 4>::NP, SacLayout<15, 16, 4>::NP, SacLayout<3, 4, 1>::NP};
 
+// What qr_sac_actor_grad and qr_ctde_sac_actor_grad check last, fill and launch alike: the alignment, the workspace's size, the
+// fields of `a` and of the reduction that come from the actor p (the one that gets gradients), the critic and QrSacActorGrad's members,
+// and the two launches on ppo_grid's grid.  The caller has made its KIND, SIZE and NULL checks, filled a.obs, a.obs_next, a.index, a.B,
+// a.rows and the fields of its own form, and hands its own float pointers for the alignment and its kernels per actor size.
+template <class Args>
+static int sac_actor_launch(const QrActor* p, const QrQCritic* c, const QrSacActorGrad* g, Args& a, std::initializer_list<const void*> own,
+                            void (*const kernel[3])(Args), void* stream) {
+  float* const grads[8] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b};
+  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->log_std_w, p->log_std_b, c->fc1_w, c->fc1_b,
+                                c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b, g->fc1_w,
+                                g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b, g->stats, g->eps, g->eps_reg,
+                                g->eps_next, g->eps_pert, g->noise, g->nominal, g->alpha_dev, g->alpha_grad};
+  for (const void* q : floats)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  for (const void* q : own)
+    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(a.index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
+  const int size = actor_size(p->obs_dim, p->hidden_dim, p->action_dim);
+  const int64_t grid = ppo_grid(a.B, g->max_workgroups);
+  const int np = kSacNP[size];
+  if (g->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
+
+  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
+  const double B = (double)a.B, ba = B * A;
+  // (PpoNet::fill copies action_dim floats from log_std into a slot this kernel never reads; mean_b is such an array)
+  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->mean_b, p->log_std_w, p->log_std_b, QR_ACTOR_TANH_SAMPLE};
+  twinq_nets(a.q, c);
+  const bool any = g->lam_T != 0.0f || g->lam_S != 0.0f || g->lam_M != 0.0f;
+  a.eps[0] = g->eps; a.eps[1] = any ? g->eps_reg : nullptr; a.eps[2] = g->lam_T != 0.0f ? g->eps_next : nullptr;
+  a.eps[3] = g->lam_S != 0.0f ? g->eps_pert : nullptr;
+  a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
+  a.alpha_dev = g->alpha_dev; a.partials = static_cast<double*>(g->workspace);
+  a.hidden = c->hidden_dim; a.alpha = g->alpha; a.max_action = g->max_action;
+  a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
+  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * a.lam_T / ba); a.c_S = (float)(2.0 * a.lam_S / ba); a.c_M = (float)(2.0 * a.lam_M / ba);
+  SacActorReduceArgs r{};
+  const int sizes[8] = {H * D, H, H * H, H, A * H, A, A * H, A};
+  r.partials = a.partials;
+  for (int k = 0; k < 8; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
+  r.stats = g->stats; r.alpha_grad = g->alpha_grad; r.alpha_dev = g->alpha_dev; r.n_parts = (int32_t)grid; r.np = np; r.B = B; r.BA = ba;
+  r.alpha = g->alpha; r.target_entropy = g->target_entropy; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
+
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(kernel[size], dim3((unsigned)grid), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(sac_actor_reduce_kernel, dim3((unsigned)((r.off[8] + 15) / 16 + 1)), dim3(256), 0, s, r);
+  return (int)hipGetLastError();
+}
+
 // (actor_grad_launch does not fit: it takes the tanh-of-mean form with six or seven tensors and no second critic; the order of the
 //  checks is its own — KIND, SIZE, NULL, ALIGN, the workspace's SIZE — and the grid is ppo_grid's)
 static int do_sac_actor(const QrActor* p, const QrQCritic* c, const QrTransitions* b, const QrSacActorGrad* g, void* stream) {
@@ -550,45 +601,63 @@ static int do_sac_actor(const QrActor* p, const QrQCritic* c, const QrTransition
   if (!g->stats || !g->workspace || !b->obs || (g->lam_T != 0.0f && !b->obs_next) || (g->lam_S != 0.0f && !g->noise) ||
       (g->lam_M != 0.0f && !g->nominal))
     return QR_E_NULL;
-  const void* const floats[] = {p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->log_std_w, p->log_std_b, c->fc1_w, c->fc1_b,
-                                c->fc2_w, c->fc2_b, c->fc3_w, c->fc3_b, c->fc4_w, c->fc4_b, c->fc5_w, c->fc5_b, c->fc6_w, c->fc6_b, g->fc1_w,
-                                g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b, g->stats, g->eps, g->eps_reg,
-                                g->eps_next, g->eps_pert, g->noise, g->nominal, g->alpha_dev, g->alpha_grad, b->obs, b->obs_next};
-  for (const void* q : floats)
-    if (reinterpret_cast<uintptr_t>(q) & 3u) return QR_E_ALIGN;
-  if ((reinterpret_cast<uintptr_t>(b->index) | reinterpret_cast<uintptr_t>(g->workspace)) & 7u) return QR_E_ALIGN;
-  const int64_t grid = ppo_grid(b->batch, g->max_workgroups);
-  const int np = kSacNP[size];
-  if (g->workspace_bytes < grid * np * (int64_t)sizeof(double)) return QR_E_SIZE;
-
-  const int D = p->obs_dim, H = p->hidden_dim, A = p->action_dim;
-  const double B = (double)b->batch, ba = B * A;
   SacActorArgs a{};
-  // (PpoNet::fill copies action_dim floats from log_std into a slot this kernel never reads; mean_b is such an array)
-  a.w = ActorW{p->fc1_w, p->fc1_b, p->fc2_w, p->fc2_b, p->mean_w, p->mean_b, p->mean_b, p->log_std_w, p->log_std_b, QR_ACTOR_TANH_SAMPLE};
-  twinq_nets(a.q, c);
-  const bool any = g->lam_T != 0.0f || g->lam_S != 0.0f || g->lam_M != 0.0f;
-  a.obs = b->obs; a.obs_next = g->lam_T != 0.0f ? b->obs_next : nullptr; a.index = b->index;
-  a.eps[0] = g->eps; a.eps[1] = any ? g->eps_reg : nullptr; a.eps[2] = g->lam_T != 0.0f ? g->eps_next : nullptr;
-  a.eps[3] = g->lam_S != 0.0f ? g->eps_pert : nullptr;
-  a.noise = g->lam_S != 0.0f ? g->noise : nullptr; a.nominal = g->lam_M != 0.0f ? g->nominal : nullptr;
-  a.alpha_dev = g->alpha_dev; a.partials = static_cast<double*>(g->workspace);
-  a.B = b->batch; a.rows = b->rows; a.hidden = c->hidden_dim; a.alpha = g->alpha; a.max_action = g->max_action;
-  a.lam_T = g->lam_T; a.lam_S = g->lam_S; a.lam_M = g->lam_M;
-  a.inv_b = (float)(1.0 / B); a.c_T = (float)(2.0 * a.lam_T / ba); a.c_S = (float)(2.0 * a.lam_S / ba); a.c_M = (float)(2.0 * a.lam_M / ba);
-  SacActorReduceArgs r{};
-  const int sizes[8] = {H * D, H, H * H, H, A * H, A, A * H, A};
-  r.partials = a.partials;
-  for (int k = 0; k < 8; ++k) { r.grad[k] = grads[k]; r.off[k + 1] = r.off[k] + sizes[k]; }
-  r.stats = g->stats; r.alpha_grad = g->alpha_grad; r.alpha_dev = g->alpha_dev; r.n_parts = (int32_t)grid; r.np = np; r.B = B; r.BA = ba;
-  r.alpha = g->alpha; r.target_entropy = g->target_entropy; r.lam_T = g->lam_T; r.lam_S = g->lam_S; r.lam_M = g->lam_M;
-
+  a.obs = b->obs; a.obs_next = g->lam_T != 0.0f ? b->obs_next : nullptr; a.index = b->index; a.B = b->batch; a.rows = b->rows;
   static void (*const kernel[3])(SacActorArgs) = {sac_actor_kernel<23, 16, 4>, sac_actor_kernel<15, 16, 4>, sac_actor_kernel<3, 4, 1>};
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(kernel[size], dim3((unsigned)grid), dim3(64), 0, s, a);
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(sac_actor_reduce_kernel, dim3((unsigned)((r.off[8] + 15) / 16 + 1)), dim3(256), 0, s, r);
-  return (int)hipGetLastError();
+  return sac_actor_launch(p, c, g, a, {b->obs, b->obs_next}, kernel, stream);
+}
+
+// qr_sac_actor_grad's launcher, grid, partial vector and reduction for agent k of two under one centralized twin critic.  The checks
+// come in qr_ctde_dpg_actor_grad's order with SAC's actor form; the grad struct's leading members are QrSacActorGrad's (checked below),
+// so sac_actor_launch reads them as one.  The table's first place (the 23-wide actor) is empty: 23 + 1 + 4 + 1 > 28, refused above.
+static_assert(offsetof(QrCtdeSacActorGrad, reserved0) == offsetof(QrSacActorGrad, reserved0) &&
+              offsetof(QrCtdeSacActorGrad, workspace_bytes) == offsetof(QrSacActorGrad, workspace_bytes) &&
+              offsetof(QrCtdeSacActorGrad, agent) == sizeof(QrSacActorGrad), "QrCtdeSacActorGrad begins with QrSacActorGrad's members");
+static int do_ctde_sac_actor(const QrActor* p0, const QrActor* p1, const QrQCritic* c, const QrCtdeTransitions* b, const QrCtdeSacActorGrad* g,
+                             void* stream) {
+  if (!c || !b || !g) return QR_E_NULL;
+  const QrActor* const p[2] = {p0, p1};
+  for (int m = 0; m < 2; ++m)
+    if (p[m] && (p[m]->squash != QR_ACTOR_TANH_SAMPLE || !p[m]->log_std_w || !p[m]->log_std_b)) return QR_E_KIND;
+  if (p0 && p1 && g->action_other) return QR_E_KIND;
+  if (g->agent != 0 && g->agent != 1) return QR_E_SIZE;
+  const int k = g->agent;
+  const QrActor *own = p[k], *other = p[1 - k];
+  bool sizes_ok = twinq_sizes_ok(c->obs_dim, c->action_dim, c->hidden_dim) && c->reserved0 == 0 && ctde_widths_ok(c, b->obs_dim, b->action_dim) &&
+                  b->batch >= 1 && b->rows >= 1 && g->max_workgroups >= 0 && g->reserved0 == 0 && g->reserved1 == 0 && nonneg_finite(g->alpha) &&
+                  nonneg_finite(g->max_action) && nonneg_finite(g->lam_T) && nonneg_finite(g->lam_S) && nonneg_finite(g->lam_M) &&
+                  g->target_entropy >= -3.0e38f && g->target_entropy <= 3.0e38f;
+  if (own) sizes_ok = sizes_ok && actor_size(own->obs_dim, own->hidden_dim, own->action_dim) == 1 + k && own->obs_dim == b->obs_dim[k] && own->action_dim == b->action_dim[k];
+  if (other) sizes_ok = sizes_ok && actor_size(other->obs_dim, other->hidden_dim, other->action_dim) == 2 - k && other->obs_dim == b->obs_dim[1 - k] &&
+                        other->action_dim == b->action_dim[1 - k];
+  if (!sizes_ok) return QR_E_SIZE;
+  if (!own) return QR_E_NULL;
+  if (other ? !other->fc1_w || !other->fc1_b || !other->fc2_w || !other->fc2_b || !other->mean_w || !other->mean_b : !g->action_other) return QR_E_NULL;
+  if (int rc = twinq_critic_check(c)) return rc;
+  if (!own->fc1_w || !own->fc1_b || !own->fc2_w || !own->fc2_b || !own->mean_w || !own->mean_b) return QR_E_NULL;
+  float* const grads[8] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std_w, g->log_std_b};
+  for (float* q : grads)
+    if (!q) return QR_E_NULL;
+  if (!g->stats || !g->workspace || !b->obs[0] || !b->obs[1] || (g->lam_T != 0.0f && !b->obs_next[k]) || (g->lam_S != 0.0f && !g->noise) ||
+      (g->lam_M != 0.0f && !g->nominal))
+    return QR_E_NULL;
+  CtdeSacActorArgs a{};
+  a.obs = b->obs[k]; a.obs_next = g->lam_T != 0.0f ? b->obs_next[k] : nullptr; a.index = b->index; a.B = b->batch; a.rows = b->rows;
+  // (log_std: as in sac_actor_launch)
+  if (other) a.other = ActorW{other->fc1_w, other->fc1_b, other->fc2_w, other->fc2_b, other->mean_w, other->mean_b, other->mean_b, other->log_std_w,
+                              other->log_std_b, QR_ACTOR_TANH_SAMPLE};
+  a.obs_other = b->obs[1 - k]; a.action_other = other ? nullptr : g->action_other; a.eps_other = other ? g->eps_other : nullptr;
+  a.eps_logp = g->eps_logp;
+  a.od_other = b->obs_dim[1 - k]; a.ad_other = b->action_dim[1 - k];
+  a.col_own = k ? b->obs_dim[0] : 0; a.col_other = k ? 0 : b->obs_dim[0];
+  a.acol_own = c->obs_dim + (k ? b->action_dim[0] : 0); a.acol_other = c->obs_dim + (k ? 0 : b->action_dim[0]);
+  a.in_dim = c->obs_dim + c->action_dim;
+  static void (*const kernel[3])(CtdeSacActorArgs) = {nullptr, ctde_sac_actor_kernel<15, 16, 4>, ctde_sac_actor_kernel<3, 4, 1>};
+  const float *o1 = other ? other->fc1_w : nullptr, *o2 = other ? other->fc1_b : nullptr, *o3 = other ? other->fc2_w : nullptr,
+              *o4 = other ? other->fc2_b : nullptr, *o5 = other ? other->mean_w : nullptr, *o6 = other ? other->mean_b : nullptr,
+              *o7 = other ? other->log_std_w : nullptr, *o8 = other ? other->log_std_b : nullptr;
+  return sac_actor_launch(own, c, reinterpret_cast<const QrSacActorGrad*>(g), a,
+                          {b->obs[0], b->obs[1], b->obs_next[k], g->eps_logp, g->eps_other, g->action_other, o1, o2, o3, o4, o5, o6, o7, o8}, kernel, stream);
 }
 
 static int do_soft_update(const QrSoftUpdate* u, void* stream) {
@@ -654,6 +723,16 @@ int64_t qr_sac_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_
   const int size = qr::actor_size(obs_dim, hidden_dim, action_dim);
   if (size < 0 || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
   return qr::ppo_grid(batch, max_workgroups) * qr::kSacNP[size] * (int64_t)sizeof(double);
+}
+
+int qr_ctde_sac_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic, const QrCtdeTransitions* batch,
+                           const QrCtdeSacActorGrad* grad, void* stream) {
+  return qr::do_ctde_sac_actor(actor_0, actor_1, critic, batch, grad, stream);
+}
+
+int64_t qr_ctde_sac_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups) {
+  if ((agent != 0 && agent != 1) || critic_hidden_dim < 1 || critic_hidden_dim > 64 || batch < 1 || max_workgroups < 0) return QR_E_SIZE;
+  return qr::ppo_grid(batch, max_workgroups) * qr::kSacNP[1 + agent] * (int64_t)sizeof(double);
 }
 
 int qr_twinq_target(const QrActor* actor_target, const QrQCritic* critic_target, const QrTransitions* batch, const QrTd3Target* target,

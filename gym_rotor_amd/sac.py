@@ -13,6 +13,9 @@ updater class is built here.
 
 The critic half also exists for ONE centralized (CTDE) twin critic over the two agents of a Decoupled buffer (sac.py:136-144, 156-157):
 `sac_target_ctde` (qr_ctde_sac_target) and, on live modules, `sac_critic_loss_ctde`; the regression is `td3.twinq_grad_ctde`.
+So does agent k's actor half under that critic (sac.py:175-203): `sac_actor_grad_ctde` (qr_ctde_sac_actor_grad) and, on live modules,
+`sac_actor_loss_ctde`, which replaces both actors' samples, two `torch.cat`, both critics, min, the second sample of agent k, the three
+regulariser samples and autograd through all of it.
 """
 from __future__ import annotations
 
@@ -24,8 +27,8 @@ import torch
 
 from . import _lib
 from .policy import ActorParams, QCriticParams, _grad_outputs, _vector
-from .td3 import (ReplayBuffer, _check_actor, _check_index, _critic_update_state, _pair_of, _rows, _target, _target_ctde, twinq_grad,
-                  twinq_grad_ctde)
+from .td3 import (ReplayBuffer, _check_actor, _check_index, _critic_update_state, _ctde_actor_launch, _pair_of, _rows, _target, _target_ctde,
+                  twinq_grad, twinq_grad_ctde)
 
 
 def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
@@ -280,4 +283,129 @@ def sac_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
                               max_action=max_action, eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert, noise=noise,
                               nominal=nominal, alpha_grad=None if log_alpha is None else log_alpha.grad, target_entropy=target_entropy,
                               grads=grads, stats=own_stats if stats is None else stats, workspace=workspace, max_workgroups=max_workgroups)
+    return stats
+
+
+def sac_actor_workspace_bytes_ctde(k: int, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
+    """Bytes of workspace one `sac_actor_grad_ctde` call needs for agent k (qr_ctde_sac_actor_workspace_bytes): `sac_actor_workspace_bytes`'
+    figure for td3.CTDE_ACTOR_DIMS[k]."""
+    n = _lib.load().qr_ctde_sac_actor_workspace_bytes(int(k), int(critic_hidden), int(batch), int(max_workgroups))
+    _lib.check(n if n < 0 else 0, "qr_ctde_sac_actor_workspace_bytes")
+    return int(n)
+
+
+def sac_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index: Optional[torch.Tensor] = None, *, k: int = 0,
+                        action_other: Optional[torch.Tensor] = None, alpha: Union[float, torch.Tensor] = 0.2, lam_T: float = 0.4,
+                        lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, eps: Optional[torch.Tensor] = None,
+                        eps_logp: Optional[torch.Tensor] = None, eps_other: Optional[torch.Tensor] = None, eps_reg: Optional[torch.Tensor] = None,
+                        eps_next: Optional[torch.Tensor] = None, eps_pert: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                        nominal: Optional[torch.Tensor] = None, alpha_grad: Optional[torch.Tensor] = None, target_entropy: Optional[float] = None,
+                        grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                        max_workgroups: int = 0):
+    """Agent k's SAC actor loss under the centralized (CTDE) twin critic of two agents and its gradients (qr_ctde_sac_actor_grad;
+    sac.py:175-203 without the spectral-norm term, with algos/policy_regularization.py), i = index[j], sample and c as `sac_actor_grad`'s:
+        a_k = sample(pi_k, obs[k][i], eps[j]).a;   a_o = sample(pi_o, obs[o][i], eps_other[j]).a      (o = 1 - k; no clamp)
+        logp_j = sample(pi_k, obs[k][i], eps_logp[j]).logp                                            (a SECOND sample of agent k)
+        L0 = mean_j (alpha logp_j - min(Q1, Q2)([obs[0][i] | obs[1][i] | a_0 | a_1]))
+        loss_k = L0 + lam_T mse(r, rn) + lam_S mse(r, rp) + lam_M mse(r, nominal)                     (r, rn, rp: agent k's, `sac_actor_grad`'s)
+    — no autograd, nothing concatenated.  eps_logp None: ONE sample, logp and a_k both from eps (eps_logp given as zeros is not that
+    form: it is a second sample at the mean).  actors: the pair of `ActorParams.from_sac_module` of the sizes td3.CTDE_ACTOR_DIMS; the
+    other agent's runs forward only inside the kernel and gets NO gradient (the reference leaves one in its .grad, which that agent
+    zeroes before reading).  Or actors[1 - k] None with action_other float32 [B, A_other] by minibatch position, used as it is: then
+    eps_other is not read and the other agent's widths are free as long as all four add up to the critic's.  obs, obs_next: pairs of
+    contiguous float32 [rows, D_m]; obs_next[k] is needed when lam_T != 0, obs_next[1 - k] never.  eps, eps_logp, eps_reg, eps_next,
+    eps_pert [B, A_k], eps_other [B, A_other]: float32 draws by minibatch position, None: zeros.  noise [D_k], nominal [A_k], alpha,
+    alpha_grad, target_entropy (None: -A_k), index, grads, stats, workspace, max_workgroups and the return value (grads of agent k's
+    eight tensors, stats [6]): `sac_actor_grad`'s; stats[2] and alpha_grad come from the sample that carries logp."""
+    what = "sac_actor_grad_ctde"
+    dev = critic.device
+    form = (_lib.ACTOR_TANH_SAMPLE, True, "the actors must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
+    shapes, B, rows, od, ad, nxt = _ctde_actor_launch(what, actors, critic, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action,
+                                                      noise, nominal, form)
+    a, alpha_dev = alpha, None
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
+            raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
+        alpha_dev, a = a, 0.0
+    elif not 0.0 <= float(a) < float("inf"):
+        raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
+    te = -float(ad[k]) if target_entropy is None else float(target_entropy)
+    if not -float("inf") < te < float("inf"):
+        raise ValueError(f"{what}: target_entropy must be finite, got {target_entropy}")
+    if alpha_grad is not None and (alpha_grad.dtype != torch.float32 or alpha_grad.device != dev or alpha_grad.numel() != 1):
+        raise ValueError(f"{what}: alpha_grad must be a float32 tensor of one element on {dev}")
+    for name, x, w in (("eps", eps, ad[k]), ("eps_logp", eps_logp, ad[k]), ("eps_other", eps_other, ad[1 - k]), ("eps_reg", eps_reg, ad[k]),
+                       ("eps_next", eps_next, ad[k]), ("eps_pert", eps_pert, ad[k])):
+        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, w) or not x.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {w}] tensor on {dev}")
+    shapes = {n: shapes[n] for n in _lib.SAC_ACTOR_GRAD_NAMES}
+    grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
+                                            lambda: sac_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups), size_given=False,
+                                            n_stats=_lib.SAC_ACTOR_STATS)
+    if workspace is None:
+        if alpha_grad is not None:
+            alpha_grad.zero_()
+        return grads, stats
+    b = _lib.ctde_transitions(obs=obs, obs_next=(nxt, None) if k == 0 else (None, nxt), index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad)
+    g = _lib.ctde_sac_actor_grad_args(grads, stats, workspace, agent=k, action_other=action_other, eps_logp=eps_logp,
+                                      eps_other=eps_other if action_other is None else None, eps=eps, eps_reg=eps_reg, eps_next=eps_next,
+                                      eps_pert=eps_pert, noise=noise if lam_S != 0 else None, nominal=nominal if lam_M != 0 else None,
+                                      alpha_dev=alpha_dev, alpha_grad=alpha_grad, alpha=a, target_entropy=te, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                                      max_action=max_action, max_workgroups=max_workgroups)
+    q = critic.as_c()
+    p = [None if c is None else c.as_c() for c in actors]
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_ctde_sac_actor_grad(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
+                                                torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ctde_sac_actor_grad")
+    return grads, stats
+
+
+def sac_actor_loss_ctde(actor_modules, critic_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
+                        log_alpha: Optional[torch.Tensor] = None, target_entropy: Optional[float] = None, alpha: Union[float, torch.Tensor] = 0.2,
+                        lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, eps: Optional[torch.Tensor] = None,
+                        eps_logp: Optional[torch.Tensor] = None, eps_other: Optional[torch.Tensor] = None, eps_reg: Optional[torch.Tensor] = None,
+                        eps_next: Optional[torch.Tensor] = None, eps_pert: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                        nominal: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> torch.Tensor:
+    """`sac_actor_loss` for agent k of a two-agent `buffer` under the centralized (CTDE) twin critic: `sac_actor_grad_ctde` on the two live
+    actors (attributes fc1, fc2, mean_linear, log_std_linear) and `critic_module` (MLP_Critic_CTDE, fc1 .. fc6); fills agent k's eight
+    `.grad` tensors in place, as `loss.backward()` after `zero_grad()` leaves them, and `log_alpha.grad` when log_alpha is given.  Of
+    `actor_modules[1 - k]` only the eight tensors' data are read: no attribute of it is set, neither its tensors nor its .grad are
+    touched.  The draws, noise, nominal: `sac_actor_grad_ctde`'s.  Returns stats [6] (stats[0] = the loss).  The workspace and stats are
+    cached on the buffer under a key of their own: from the second call on with an unchanged B nothing is allocated.  The optimiser
+    steps stay the caller's."""
+    what = "sac_actor_loss_ctde"
+    if not isinstance(buffer, ReplayBuffer) or buffer.n_agents != 2:
+        raise ValueError(f"{what}: buffer must be a two-agent ReplayBuffer")
+    if k not in (0, 1):
+        raise ValueError(f"{what}: k must be 0 or 1 (two agents), got {k}")
+    actor_modules = tuple(actor_modules)
+    if len(actor_modules) != 2:
+        raise ValueError(f"{what}: actor_modules must be the pair of both agents' actors")
+    m = actor_modules[k]
+    params = [t for l in (m.fc1, m.fc2, m.mean_linear, m.log_std_linear) for t in (l.weight, l.bias)]
+    if log_alpha is not None:
+        if log_alpha.numel() != 1:
+            raise ValueError(f"{what}: log_alpha must have one element")
+        params.append(log_alpha)
+    for p in params:
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+    grads = {n: p.grad for n, p in zip(_lib.SAC_ACTOR_GRAD_NAMES, params)}
+    actors = [ActorParams.from_sac_module(a) for a in actor_modules]
+    critic = QCriticParams.from_module(critic_module, sum(buffer.action_dims))
+    B = buffer.capacity if index is None else index.numel()
+    key = ("sac_actor_ctde", k, B, int(max_workgroups))
+    hit = buffer._cache.get(key)
+    if hit is None:
+        dev = critic.device
+        need = sac_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups) // 8 if B else 0
+        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev),
+                                    torch.empty(_lib.SAC_ACTOR_STATS, dtype=torch.float32, device=dev))
+    workspace, own_stats = hit
+    _, stats = sac_actor_grad_ctde(actors, critic, buffer.obs, buffer.obs_next, index, k=k, alpha=alpha, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
+                                   max_action=max_action, eps=eps, eps_logp=eps_logp, eps_other=eps_other, eps_reg=eps_reg, eps_next=eps_next,
+                                   eps_pert=eps_pert, noise=noise, nominal=nominal, alpha_grad=None if log_alpha is None else log_alpha.grad,
+                                   target_entropy=target_entropy, grads=grads, stats=own_stats if stats is None else stats, workspace=workspace,
+                                   max_workgroups=max_workgroups)
     return stats

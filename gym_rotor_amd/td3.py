@@ -549,8 +549,13 @@ def dpg_actor_workspace_bytes_ctde(k: int, critic_hidden: int, batch: int, max_w
     return int(n)
 
 
-def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action, noise, nominal):
-    """`dpg_actor_grad_ctde`'s checks up to the outputs: returns (shapes of agent k's tensors, B, rows, the four widths, obs_next[k])."""
+_TD3_FORM = (_lib.ACTOR_TANH_MEAN, False, "the actors must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
+
+
+def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action, noise, nominal,
+                       form=_TD3_FORM):
+    """`dpg_actor_grad_ctde`'s and `sac.sac_actor_grad_ctde`'s checks up to the outputs (form: what `_check_actor` asks of both actors):
+    returns (shapes of agent k's tensors, B, rows, the four widths, obs_next[k])."""
     dev = critic.device
     D, A, H = critic.dims
     if k not in (0, 1):
@@ -584,7 +589,6 @@ def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, 
         ad[o] = actors[o].dims[2]
     if sum(od) != D or sum(ad) != A:
         raise ValueError(f"{what}: the widths of obs {od[0]}+{od[1]} / action {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
-    form = (_lib.ACTOR_TANH_MEAN, False, "the actors must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
     shapes = None
     for m in (k, o):
         if actors[m] is None:

@@ -543,6 +543,34 @@ def qr_sac_actor_grad(actor: List[torch.Tensor], critic: List[torch.Tensor], act
                    target_entropy=target_entropy, grads=dict(zip(_lib.SAC_ACTOR_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_ctde_sac_actor_grad", mutates_args=("grads", "stats", "alpha_grad"))
+def qr_ctde_sac_actor_grad(actor0: List[torch.Tensor], actor1: List[torch.Tensor], critic: List[torch.Tensor], agent: int, obs0: torch.Tensor,
+                           obs1: torch.Tensor, obs_next: Optional[torch.Tensor], index: Optional[torch.Tensor], action_other: Optional[torch.Tensor],
+                           eps: Optional[torch.Tensor], eps_logp: Optional[torch.Tensor], eps_other: Optional[torch.Tensor],
+                           eps_reg: Optional[torch.Tensor], eps_next: Optional[torch.Tensor], eps_pert: Optional[torch.Tensor],
+                           noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor,
+                           alpha_grad: Optional[torch.Tensor], alpha: float, target_entropy: float, lam_T: float, lam_S: float, lam_M: float,
+                           max_action: float, alpha_dev: Optional[torch.Tensor] = None, max_workgroups: int = 0) -> None:
+    """Agent `agent`'s SAC actor loss under the centralized twin critic of two agents and its eight gradients (qr_ctde_sac_actor_grad).
+    actor0, actor1: eight tensors each, fc1_w .. log_std_b; the other agent's may be an empty list with action_other.  critic: the
+    centralized twin critic's twelve; obs_next: agent `agent`'s own; grads: that agent's eight; stats float32 [6]; alpha_dev wins over
+    alpha.  Everything else as sac.sac_actor_grad_ctde."""
+    from .policy import ActorParams
+    from .sac import sac_actor_grad_ctde
+    _gpu(stats)
+    if len(actor0) not in (0, 8) or len(actor1) not in (0, 8) or len(grads) != 8:
+        raise ValueError("a SAC actor and its gradients are 8 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std_w, log_std_b")
+    pair = [ActorParams(*a[:6], None, a[6], a[7], _lib.ACTOR_TANH_SAMPLE) if a else None for a in (actor0, actor1)]
+    if agent not in (0, 1) or pair[agent] is None:
+        raise ValueError("agent must be 0 or 1 and that agent's actor given")
+    a_other = action_other.shape[-1] if action_other is not None else (pair[1 - agent].dims[2] if pair[1 - agent] is not None else 0)
+    sac_actor_grad_ctde(pair, _qcritic_params(critic, pair[agent].dims[2] + a_other), (obs0, obs1), (obs_next, None) if agent == 0 else (None, obs_next),
+                        index, k=agent, action_other=action_other, alpha=alpha if alpha_dev is None else alpha_dev, lam_T=lam_T, lam_S=lam_S,
+                        lam_M=lam_M, max_action=max_action, eps=eps, eps_logp=eps_logp, eps_other=eps_other, eps_reg=eps_reg, eps_next=eps_next,
+                        eps_pert=eps_pert, noise=noise, nominal=nominal, alpha_grad=alpha_grad, target_entropy=target_entropy,
+                        grads=dict(zip(_lib.SAC_ACTOR_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # functional wrappers over a QuadVecEnv's own buffers
 # ----------------------------------------------------------------------------------------------------------------

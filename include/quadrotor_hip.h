@@ -875,6 +875,65 @@ int qr_ctde_dpg_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const
  * and max_workgroups: qr_dpg_actor_workspace_bytes' figure for that actor.  QR_E_SIZE (< 0) where the entry would refuse them. */
 int64_t qr_ctde_dpg_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups);
 
+/* The actor half of one SAC minibatch update for agent k of TWO agents under ONE centralized twin critic (the CTDE branch of
+ * SAC.train, algos/sac/sac.py:175-203, without the spectral-norm term, with algos/policy_regularization.py), read from the two agents'
+ * buffers in place, without autograd.  sample(.), c(.), the reg passes, mse and the gates are qr_sac_actor_grad's; m = 0, 1:
+ *     a_m     = sample(pi_m, obs_m[i], eps_m[j]).a                     (no clamp; eps_k = eps, eps_{1-k} = eps_other)
+ *     logp_j  = sample(pi_k, obs_k[i], eps_logp[j]).logp               (a SECOND sample of agent k, sac.py:180)
+ *     L0      = mean_j ( alpha * logp_j - min(Q1, Q2)([obs_0[i] | obs_1[i] | a_0 | a_1]) )
+ *     loss_k  = L0 + lam_T mse(r, rn) + lam_S mse(r, rp) + lam_M mse(r, nominal)      (r, rn, rp: agent k's, from eps_reg, eps_next, eps_pert)
+ *     alpha_grad = -(target_entropy + mean_j logp_j)                   (logp of the SECOND sample)
+ * and loss_k.backward()'s gradients for agent k's eight actor tensors.  The Q term reaches pi_k through a_k, the first sample:
+ * dQ/da_k = fc1_w[:, D + off_k .. D + off_k + action_dim[k])^T dz1 of the selected critic, D = obs_dim[0] + obs_dim[1], off_0 = 0,
+ * off_1 = action_dim[0]; the entropy term through the second sample.  Both samples share one forward pass (the same row gives the same
+ * mean and raw log_std) and their deltas add before one backward pass.  eps_logp NULL: ONE sample, drawn with eps — logp and a from
+ * the same sample, exactly as qr_sac_actor_grad; eps_logp given as zeros is NOT that form.  The other agent's action enters both critics
+ * as a VALUE only.  (In the reference that agent's actor receives a .grad from this backward pass too; it zeroes it in its own
+ * zero_grad() before anything reads it.  Here no gradient for agent 1-k exists and nothing of that actor is written.)
+ *   QrSacActorGrad's members keep their meaning for agent k (noise [obs_dim[k]], nominal [action_dim[k]], eps = agent k's first draw).
+ *   agent: k, 0 or 1.  Agent k's actor is a QrActor of the QR_ACTOR_TANH_SAMPLE form with the log_std head, of the Decoupled wrapper's
+ *   size for that place: (15,16,4) for agent 0, (3,4,1) for agent 1, equal to the batch's obs_dim[k] and action_dim[k].
+ *   The other agent's action, one of two forms:
+ *     both actors given, action_other NULL: the pair has exactly the sizes (15,16,4) and (3,4,1) and the batch their widths; pi_{1-k}
+ *       runs forward only inside the kernel, sampled with eps_other [batch][action_dim[1-k]] (NULL: zeros), tanh, no clamp.
+ *     the actor of agent 1-k NULL, action_other [batch][action_dim[1-k]] float32 by minibatch position: used as it is; eps_other is
+ *       not read; the other agent's obs_dim and action_dim are free as long as the four widths add up to the critic's (<= 28).
+ *     Both actors AND action_other: QR_E_KIND (the form is ambiguous), reported with the other QR_E_KIND causes, before any size.
+ *   critic: a QrQCritic with the summed widths; both networks are read.
+ *   batch: a QrCtdeTransitions, of which obs[0], obs[1], index and, with lam_T != 0, obs_next[k] are read.
+ * Outputs, overwritten: agent k's eight gradient tensors, stats [6] as qr_sac_actor_grad's (stats[2] = the mean logp that enters the
+ * loss: the second sample's where eps_logp is given; stats[4] counts agent k's raw log_std) and, where not NULL, alpha_grad.
+ * Two launches, the partial vectors (qr_sac_actor_grad's for agent k's actor size), the float64 reduction in a fixed order and the grid
+ * rule are qr_sac_actor_grad's: the same inputs and grid give the same bits (no atomics). */
+typedef struct QrCtdeSacActorGrad {
+  float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *mean_w, *mean_b, *log_std_w, *log_std_b, *stats;
+  const float *eps, *eps_reg, *eps_next, *eps_pert;
+  const float* noise;      const float* nominal;
+  const float* alpha_dev;  float* alpha_grad;
+  void* workspace;         int64_t workspace_bytes;   /* >= qr_ctde_sac_actor_workspace_bytes(...); 8-byte aligned */
+  float alpha, target_entropy;
+  float lam_T, lam_S, lam_M, max_action;
+  int32_t max_workgroups, reserved0;
+  int32_t agent, reserved1;                           /* k; reserved1 must be 0 */
+  const float* eps_logp;
+  const float* eps_other;
+  const float* action_other;
+} QrCtdeSacActorGrad;
+/* In this order: QR_E_NULL for a NULL critic, batch or grad struct; QR_E_KIND for an actor (either) with squash !=
+ * QR_ACTOR_TANH_SAMPLE or without the log_std head, or both actors together with action_other; QR_E_SIZE for agent outside 0..1, critic
+ * widths outside their ranges, widths < 1, widths that do not add up to the critic's or exceed 28, reserved fields != 0, agent k's
+ * actor not of its place's size or different from the batch's widths, in the both-actors form a pair other than (15,16,4), (3,4,1),
+ * batch < 1, rows < 1, max_workgroups < 0, a negative or non-finite alpha, max_action or lam_*, a non-finite target_entropy; QR_E_NULL
+ * for agent k's actor NULL, the other actor and action_other both NULL, a NULL actor weight (agent k's; the other's where it is given),
+ * critic weight, obs[0], obs[1], output or workspace pointer (index, the draws, alpha_dev and alpha_grad optional; obs_next[k], noise,
+ * nominal as in qr_sac_actor_grad); QR_E_ALIGN for a float pointer that is not 4-byte aligned or an index / workspace pointer that is
+ * not 8-byte aligned; QR_E_SIZE for a workspace that is too small.  Nothing is launched or written on an error. */
+int qr_ctde_sac_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const QrQCritic* critic, const QrCtdeTransitions* batch,
+                           const QrCtdeSacActorGrad* grad, void* stream);
+/* Bytes of workspace qr_ctde_sac_actor_grad needs for agent 0 (the (15,16,4) actor) or 1 (the (3,4,1) actor), this critic width, batch
+ * and max_workgroups: qr_sac_actor_workspace_bytes' figure for that actor.  QR_E_SIZE (< 0) where the entry would refuse them. */
+int64_t qr_ctde_sac_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

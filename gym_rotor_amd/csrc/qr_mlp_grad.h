@@ -454,11 +454,12 @@ __device__ __forceinline__ int reduce16_entries(const double* partials, int n_pa
   return s == 0 && valid ? e : -1;
 }
 
-// which of the six tensors entry e belongs to
-__device__ __forceinline__ int entry_tensor(int e, const int32_t (&off)[7]) {
+// which of the N tensors entry e belongs to (off: their N starts, then the sums': six tensors for PPO and TD3, eight for SAC)
+template <int N>
+__device__ __forceinline__ int entry_tensor(int e, const int32_t (&off)[N + 1]) {
   int k = 0;
 #pragma unroll
-  for (int j = 1; j < 6; ++j)
+  for (int j = 1; j < N; ++j)
     if (e >= off[j]) k = j;
   return k;
 }
@@ -469,7 +470,7 @@ __device__ __forceinline__ void reduce16_store(const double* partials, int n_par
                                                double* red, Adjust&& adjust) {
   const int e = reduce16_entries(partials, n_parts, np, off[6], red);
   if (e < 0) return;
-  const int k = entry_tensor(e, off);
+  const int k = entry_tensor<6>(e, off);
   float* dst = grad[0];
 #pragma unroll
   for (int j = 1; j < 6; ++j)

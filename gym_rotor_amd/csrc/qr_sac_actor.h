@@ -6,7 +6,7 @@
 //   with FOUR independent samples of pi (the loss pass; the regulariser's own sample r; on obs_next; on obs + noise), its gradients for
 //   MLP_Actor_SAC's eight tensors, and what alpha's own update needs, -(target_entropy + mean_j logp_j).
 //   ctde_sac_actor_kernel + sac_actor_reduce_kernel (qr_ctde_sac_actor_grad)   the same for agent k of two under ONE centralized (CTDE)
-//   twin critic (sac.py:175-203): the other agent's action as a value, logp from a second sample of agent k; a FOURTH copy of the walk.
+//   twin critic (sac.py:175-203): the other agent's action as a value, logp from a second sample of agent k; the same walk blocks.
 // The pieces are shared: the actor's layers, MFMA weight gradients, delta tile and emit are PpoNet's static pieces (qr_ppo.h), a critic's
 // forward pass and dQ/da are dpg_q1_half (qr_td3_actor.h), the reduction is reduce16_entries / block_sum_column.  New here:
 //   - the two-headed passes (SacNet): forward keeps the pre-tanh mean and log_std_linear's output; backward puts dmean in columns
@@ -15,8 +15,9 @@
 //   - the second critic: Q1 and Q2 run one after the other through ONE set of LDS arrays and ONE resident fc2_w, refilled from L2 per
 //     tile (a second set does not fit under 64 KB of LDS beside the actor's tiles);
 //   - the selection min(Q1, Q2) per row, with torch's half-and-half on an exact tie.
-// The tile walk — prologue, gather, smoothness block, epilogue — is a THIRD copy of ppo_actor_kernel's and dpg_actor_kernel's (qr_td3_actor.h
-// says why the second is one): a fix to one walk has to be made in all three.
+// The tile walk is separate from ppo_actor_kernel's and dpg_walk's (qr_td3_actor.h says why those two are apart), but the two kernels
+// here are built from ONE set of force-inlined blocks — sac_prologue, sac_row_index / sac_noise_row, sac_critics, sac_select,
+// sac_regularize, sac_epilogue — so a fix to a block reaches both.  Each kernel keeps its own __shared__ arrays and the glue between the blocks.
 // 1 - a^2 and a come from t = exp(-2|u|) as in qr_sac.h (never from the rounded a), -eps^2/2 from eps.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -201,6 +202,190 @@ struct SacRow {
   }
 };
 
+// ---- The blocks of the tile walk that sac_actor_kernel and ctde_sac_actor_kernel are both built from.  Each is force-inlined into
+// the kernel that owns the __shared__ arrays and takes them as plain pointers.  The one-agent kernel passes the critics' row as the
+// constants IN = D + A, xcol = 0, acol = D; the CTDE kernel reads them from its arguments.
+
+// Before the first tile: zero accumulators, pi's two LDS blocks, the tiles' constant columns (ends with a barrier), then the
+// launch's scalars.
+template <int D, int H, int A>
+__device__ __forceinline__ void sac_prologue(SacNet<D, H, A>& net, const SacActorArgs& a, float* sm, float* sl, float* xs, float* hs, float* qs,
+                                             int lane, float& alpha, bool& any_reg, float (&nominal)[A], double (&st)[SacLayout<D, H, A>::NS]) {
+  using Net = PpoNet<D, H, A>;
+  constexpr int XS = Net::XS, HS = Net::HS;
+  net.zero();
+  {
+    PpoArgs p{};
+    p.w = a.w;
+    p.noise = a.noise;
+    Net::fill(sm, p, lane);
+    SacNet<D, H, A>::fill(sl, a.w, lane);
+  }
+  for (int i = lane; i < 64 * XS; i += 64) xs[i] = (i % XS == D) ? 1.0f : 0.0f;  // the ones column; the rest of the padding stays zero
+  for (int i = lane; i < 64 * HS; i += 64) hs[i] = (i % HS == H) ? 1.0f : 0.0f;
+  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns past the critics' row stay zero
+  __syncthreads();
+  alpha = a.alpha_dev ? a.alpha_dev[0] : a.alpha;
+  any_reg = a.lam_T != 0.0f || a.lam_S != 0.0f || a.lam_M != 0.0f;
+#pragma unroll
+  for (int j = 0; j < A; ++j) nominal[j] = a.nominal ? a.nominal[j] : 0.0f;
+#pragma unroll
+  for (int q = 0; q < SacLayout<D, H, A>::NS; ++q) st[q] = 0.0;
+}
+
+// The replay-buffer row of minibatch position pos: never a read outside the buffer
+__device__ __forceinline__ int64_t sac_row_index(const int64_t* index, int64_t rows, int64_t pos, bool active) {
+  const int64_t i = active ? (index ? index[pos] : pos) : 0;
+  return i < 0 ? 0 : (i >= rows ? rows - 1 : i);
+}
+
+// One row of a draw, by minibatch position; NULL: zeros through the same code
+template <int A>
+__device__ __forceinline__ void sac_noise_row(const float* p, int64_t pos, bool active, float (&e)[A]) {
+#pragma unroll
+  for (int j = 0; j < A; ++j) e[j] = (p && active) ? p[pos * A + j] : 0.0f;
+}
+
+// The critics' phase: for Q1 then Q2, refill the critic's LDS arrays and the resident fc2_w, then Q and dQ/da of the rows in qs per
+// half tile into dq[n].  IN: the critics' row width; acol: agent k's action columns in it.  Starts and ends with a barrier.
+template <int A>
+__device__ __forceinline__ void sac_critics(const MlpNetW (&q)[2], int IN, int acol, int QH, const float* qs, float* w1s, float* w2ts,
+                                            float* svec, float* was, float* dq, int lane) {
+#pragma unroll 1
+  for (int n = 0; n < 2; ++n) {
+    __syncthreads();  // the previous critic's reads are done
+    float a2[4][4][4];
+    {
+      float a2t[4][4][4];
+      load_fc2(a2, a2t, q[n].fc2_w, QH, lane);
+#pragma unroll
+      for (int k = 0; k < 64; ++k) w2ts[64 * k + lane] = a2t[k >> 4][(k >> 2) & 3][k & 3];
+    }
+    twinq_fill_small(w1s, svec, q[n], IN, QH, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? q[n].fc1_w[lane * IN + acol + j] : 0.0f;
+    const float bias3 = q[n].fc3_b[0];
+    __syncthreads();
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half)
+      dpg_q1_half<A>(a2, lds_here(w2ts), qs + 32 * half * kMgX, lds_here(w1s), lds_here(svec), was, dq + (n * 64 + 32 * half) * kDpgQ, bias3, lane);
+  }
+  __syncthreads();
+}
+
+// min(Q1, Q2): a row's gradient goes to the smaller critic; torch gives each half on an exact tie.  ga = d(-mean min Q) / da
+template <int A, int NS>
+__device__ __forceinline__ void sac_select(const float* dq, float inv_b, bool active, int lane, double (&st)[NS], float (&ga)[A]) {
+  const float* dq1 = dq + 64 * kDpgQ;
+  const float q1 = dq[lane * kDpgQ + 4], q2 = dq1[lane * kDpgQ + 4];
+  const float w2 = q2 < q1 ? 1.0f : (q2 == q1 ? 0.5f : 0.0f);
+  if (active) {
+    st[0] += (double)fminf(q1, q2);
+    st[6] += q2 < q1 ? 1.0 : 0.0;
+  }
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    const float d1 = dq[lane * kDpgQ + j], d2 = dq1[lane * kDpgQ + j];
+    const float d = w2 == 1.0f ? d2 : (w2 == 0.0f ? d1 : 0.5f * d1 + 0.5f * d2);
+    ga[j] = -inv_b * d;
+  }
+}
+
+// policy_regularization: its own sample r on the tile's rows (in xs) and the three smoothness terms.  i: the lane's replay-buffer
+// row, pos: its minibatch position; xs is restored from columns [xcol, xcol + D) of qs.  Ends with a barrier.
+template <int D, int H, int A>
+__device__ __forceinline__ void sac_regularize(SacNet<D, H, A>& net, const SacActorArgs& a, const float* sm, const float* sl, float* xs, float* hs,
+                                               float* ds, const float* qs, const float** src, int xcol, const float (&nominal)[A],
+                                               double (&st)[SacLayout<D, H, A>::NS], int64_t i, int64_t pos, bool active, int lane) {
+  using Net = PpoNet<D, H, A>;
+  using SN = SacNet<D, H, A>;
+  constexpr int XS = Net::XS;
+  float x[D], h1[H], h2[H], mean[A], lsr[A], e[A], r[A], gr[A];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
+  SN::forward(sm, sl, x, h1, h2, mean, lsr);
+  sac_noise_row(a.eps[1], pos, active, e);
+  SacRow<A> s;
+  s.sample(mean, lsr, e);
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    r[j] = fminf(fmaxf(s.act[j], -a.max_action), a.max_action);
+    gr[j] = 0.0f;
+  }
+  if (a.lam_M != 0.0f) {
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+      const float d = r[j] - nominal[j];
+      if (active) st[4] += (double)(d * d);
+      gr[j] = fmaf(a.c_M, d, gr[j]);
+    }
+  }
+  // a smoothness pass on other input rows y: the difference enters both ends — gr for r's pass, -c d for y's own, here
+  auto other = [&](const float (&y)[D], int which, float c, double& sum) {
+    float g1[H], g2[H], mo[A], lo[A], eo[A], go[A], dmo[A], dlo[A];
+    SN::forward(sm, sl, y, g1, g2, mo, lo);
+    sac_noise_row(a.eps[which], pos, active, eo);
+    SacRow<A> so;
+    so.sample(mo, lo, eo);
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+      const float d = r[j] - fminf(fmaxf(so.act[j], -a.max_action), a.max_action);
+      if (active) sum += (double)(d * d);
+      gr[j] = fmaf(c, d, gr[j]);
+      go[j] = fabsf(so.act[j]) <= a.max_action ? -c * d : 0.0f;
+    }
+    so.deltas(go, 0.0f, active, dmo, dlo);
+    net.backward(sm, sl, xs, hs, ds, g1, g2, dmo, dlo, lane);
+  };
+  if (a.lam_S != 0.0f) {
+    float y[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) { y[k] = xs[lane * XS + k] + sm[Net::O_NOISE + k]; xs[lane * XS + k] = y[k]; }
+    other(y, 3, a.c_S, st[3]);
+  }
+  if (a.lam_T != 0.0f) {
+    src[lane] = active ? a.obs_next + i * D : nullptr;
+    __syncthreads();
+    ppo_stage<D, XS>(xs, src, lane);
+    __syncthreads();
+    float y[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) y[k] = xs[lane * XS + k];
+    other(y, 2, a.c_T, st[2]);
+  }
+  if (a.lam_S != 0.0f || a.lam_T != 0.0f) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + xcol + k];
+  }
+  float ga[A], dmean[A], dls[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) ga[j] = fabsf(s.act[j]) <= a.max_action ? gr[j] : 0.0f;
+  s.deltas(ga, 0.0f, active, dmean, dls);
+  net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier: the tiles are free for the next rows)
+}
+
+// After the last tile: the workgroup's ONE partial vector P — the eight tensors' accumulators, then the per-lane sums added across
+// the lanes in lane order through red (64 x NS doubles of LDS that nothing else reads any more).
+template <int D, int H, int A>
+__device__ __forceinline__ void sac_epilogue(const SacNet<D, H, A>& net, double* P, double* red, const double (&st)[SacLayout<D, H, A>::NS], int lane) {
+  using Net = PpoNet<D, H, A>;
+  using PY = PpoLayout<D, H, A>;
+  using Y = SacLayout<D, H, A>;
+  Net::template emit<D, Net::NB1>(P + PY::O_W1, P + PY::O_B1, net.acc1, H, lane);
+  Net::template emit<H, Net::NBH>(P + PY::O_W2, P + PY::O_B2, net.acc2, H, lane);
+  Net::template emit<H, Net::NBH>(P + PY::O_W3, P + PY::O_B3, net.acc3, A, lane);
+  SacNet<D, H, A>::emit_head2(P + Y::O_LW, P + Y::O_LB, net.acc3, lane);
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < Y::NS; ++q) red[lane * Y::NS + q] = st[q];
+  __syncthreads();
+  if (lane < Y::NS) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += red[l * Y::NS + lane];
+    P[Y::O_ST + lane] = s;
+  }
+}
+
 // One wavefront per workgroup owns 64-row tiles of the minibatch and walks them grid-stride.  Per tile, in this order:
 //   the loss pass   gather the obs rows (index) through the LDS tile, forward (lane = row), sample with eps[0]; [obs | a] into the
 //                   critic's tile; for Q1 then Q2: refill the critic's LDS arrays and the resident fc2_w, then Q and dQ/da per half
@@ -213,7 +398,6 @@ template <int D, int H, int A>
 __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
   using Net = PpoNet<D, H, A>;
   using SN = SacNet<D, H, A>;
-  using PY = PpoLayout<D, H, A>;
   using Y = SacLayout<D, H, A>;
   constexpr int XS = Net::XS, HS = Net::HS;
   __shared__ float sm[Net::SM], sl[SN::SL];
@@ -223,40 +407,17 @@ __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
   __shared__ const float* src[64];
   static_assert(64 * Y::NS * sizeof(double) <= sizeof(float) * 64 * kMgX, "the sums fit the critics' tile");
   const int lane = threadIdx.x;
-  const int QH = a.hidden;
   SN net;
-  net.zero();
-  {
-    PpoArgs p{};
-    p.w = a.w;
-    p.noise = a.noise;
-    Net::fill(sm, p, lane);
-    SN::fill(sl, a.w, lane);
-  }
-  for (int i = lane; i < 64 * XS; i += 64) xs[i] = (i % XS == D) ? 1.0f : 0.0f;  // the ones column; the rest of the padding stays zero
-  for (int i = lane; i < 64 * HS; i += 64) hs[i] = (i % HS == H) ? 1.0f : 0.0f;
-  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns >= D + A stay zero
-  __syncthreads();
-  const float alpha = a.alpha_dev ? a.alpha_dev[0] : a.alpha;
-  const bool any_reg = a.lam_T != 0.0f || a.lam_S != 0.0f || a.lam_M != 0.0f;
-  float nominal[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) nominal[j] = a.nominal ? a.nominal[j] : 0.0f;
+  float alpha, nominal[A];
+  bool any_reg;
   double st[Y::NS];
-#pragma unroll
-  for (int q = 0; q < Y::NS; ++q) st[q] = 0.0;
+  sac_prologue(net, a, sm, sl, xs, hs, qs, lane, alpha, any_reg, nominal, st);
 
   const int64_t tiles = (a.B + 63) / 64;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t row0 = tile * 64;
     const bool active = row0 + lane < a.B;
-    int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
-    i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
-    auto noise_row = [&](int which, float (&e)[A]) {  // by minibatch position; NULL: zeros through the same code
-      const float* p = a.eps[which];
-#pragma unroll
-      for (int j = 0; j < A; ++j) e[j] = (p && active) ? p[(row0 + lane) * A + j] : 0.0f;
-    };
+    const int64_t i = sac_row_index(a.index, a.rows, row0 + lane, active);
     src[lane] = active ? a.obs + i * D : nullptr;
     __syncthreads();
     ppo_stage<D, XS>(xs, src, lane);
@@ -268,7 +429,7 @@ __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
 #pragma unroll
       for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
       SN::forward(sm, sl, x, h1, h2, mean, lsr);
-      noise_row(0, e);
+      sac_noise_row(a.eps[0], row0 + lane, active, e);
       SacRow<A> s;
       s.sample(mean, lsr, e);
       if (active) {
@@ -284,129 +445,19 @@ __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
       for (int u = 0; u < H; ++u) { hs[lane * HS + u] = h1[u]; ds[lane * kPpoDelta + u] = h2[u]; }
 #pragma unroll
       for (int j = 0; j < A; ++j) qs[lane * kMgX + D + j] = s.act[j];  // no clamp on the loss pass's action
-#pragma unroll 1
-      for (int n = 0; n < 2; ++n) {
-        __syncthreads();  // the previous critic's reads are done
-        float a2[4][4][4];
-        {
-          float a2t[4][4][4];
-          load_fc2(a2, a2t, a.q[n].fc2_w, QH, lane);
-#pragma unroll
-          for (int k = 0; k < 64; ++k) w2ts[64 * k + lane] = a2t[k >> 4][(k >> 2) & 3][k & 3];
-        }
-        twinq_fill_small(w1s, svec, a.q[n], D + A, QH, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? a.q[n].fc1_w[lane * (D + A) + D + j] : 0.0f;
-        const float bias3 = a.q[n].fc3_b[0];
-        __syncthreads();
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half)
-          dpg_q1_half<A>(a2, lds_here(w2ts), qs + 32 * half * kMgX, lds_here(w1s), lds_here(svec), was, dq[n] + 32 * half * kDpgQ, bias3, lane);
-      }
-      __syncthreads();
+      sac_critics<A>(a.q, D + A, D, a.hidden, qs, w1s, w2ts, svec, was, dq[0], lane);
 #pragma unroll
       for (int u = 0; u < H; ++u) { h1[u] = hs[lane * HS + u]; h2[u] = ds[lane * kPpoDelta + u]; }
-      // min(Q1, Q2): a row's gradient goes to the smaller critic; torch gives each half on an exact tie
-      const float q1 = dq[0][lane * kDpgQ + 4], q2 = dq[1][lane * kDpgQ + 4];
-      const float w2 = q2 < q1 ? 1.0f : (q2 == q1 ? 0.5f : 0.0f);
-      if (active) {
-        st[0] += (double)fminf(q1, q2);
-        st[6] += q2 < q1 ? 1.0 : 0.0;
-      }
       float ga[A], dmean[A], dls[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) {
-        const float d1 = dq[0][lane * kDpgQ + j], d2 = dq[1][lane * kDpgQ + j];
-        const float d = w2 == 1.0f ? d2 : (w2 == 0.0f ? d1 : 0.5f * d1 + 0.5f * d2);
-        ga[j] = -a.inv_b * d;  // d(-mean min Q) / da
-      }
+      sac_select(dq[0], a.inv_b, active, lane, st, ga);
       s.deltas(ga, alpha * a.inv_b, active, dmean, dls);
       net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier)
     }
 
-    // ---- policy_regularization: its own sample r and the three smoothness terms
-    if (any_reg) {
-      float x[D], h1[H], h2[H], mean[A], lsr[A], e[A], r[A], gr[A];
-#pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
-      SN::forward(sm, sl, x, h1, h2, mean, lsr);
-      noise_row(1, e);
-      SacRow<A> s;
-      s.sample(mean, lsr, e);
-#pragma unroll
-      for (int j = 0; j < A; ++j) {
-        r[j] = fminf(fmaxf(s.act[j], -a.max_action), a.max_action);
-        gr[j] = 0.0f;
-      }
-      if (a.lam_M != 0.0f) {
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float d = r[j] - nominal[j];
-          if (active) st[4] += (double)(d * d);
-          gr[j] = fmaf(a.c_M, d, gr[j]);
-        }
-      }
-      // a smoothness pass on other input rows y: the difference enters both ends — gr for r's pass, -c d for y's own, here
-      auto other = [&](const float (&y)[D], int which, float c, double& sum) {
-        float g1[H], g2[H], mo[A], lo[A], eo[A], go[A], dmo[A], dlo[A];
-        SN::forward(sm, sl, y, g1, g2, mo, lo);
-        noise_row(which, eo);
-        SacRow<A> so;
-        so.sample(mo, lo, eo);
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float d = r[j] - fminf(fmaxf(so.act[j], -a.max_action), a.max_action);
-          if (active) sum += (double)(d * d);
-          gr[j] = fmaf(c, d, gr[j]);
-          go[j] = fabsf(so.act[j]) <= a.max_action ? -c * d : 0.0f;
-        }
-        so.deltas(go, 0.0f, active, dmo, dlo);
-        net.backward(sm, sl, xs, hs, ds, g1, g2, dmo, dlo, lane);
-      };
-      if (a.lam_S != 0.0f) {
-        float y[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) { y[k] = xs[lane * XS + k] + sm[Net::O_NOISE + k]; xs[lane * XS + k] = y[k]; }
-        other(y, 3, a.c_S, st[3]);
-      }
-      if (a.lam_T != 0.0f) {
-        src[lane] = active ? a.obs_next + i * D : nullptr;
-        __syncthreads();
-        ppo_stage<D, XS>(xs, src, lane);
-        __syncthreads();
-        float y[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) y[k] = xs[lane * XS + k];
-        other(y, 2, a.c_T, st[2]);
-      }
-      if (a.lam_S != 0.0f || a.lam_T != 0.0f) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + k];
-      }
-      float ga[A], dmean[A], dls[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) ga[j] = fabsf(s.act[j]) <= a.max_action ? gr[j] : 0.0f;
-      s.deltas(ga, 0.0f, active, dmean, dls);
-      net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier: the tiles are free for the next rows)
-    }
+    if (any_reg) sac_regularize(net, a, sm, sl, xs, hs, ds, qs, src, 0, nominal, st, i, row0 + lane, active, lane);
   }
 
-  double* P = a.partials + (int64_t)blockIdx.x * Y::NP;
-  Net::template emit<D, Net::NB1>(P + PY::O_W1, P + PY::O_B1, net.acc1, H, lane);
-  Net::template emit<H, Net::NBH>(P + PY::O_W2, P + PY::O_B2, net.acc2, H, lane);
-  Net::template emit<H, Net::NBH>(P + PY::O_W3, P + PY::O_B3, net.acc3, A, lane);
-  SN::emit_head2(P + Y::O_LW, P + Y::O_LB, net.acc3, lane);
-  // the per-lane sums: across the lanes in lane order
-  double* red = reinterpret_cast<double*>(qs);
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < Y::NS; ++q) red[lane * Y::NS + q] = st[q];
-  __syncthreads();
-  if (lane < Y::NS) {
-    double s = 0.0;
-    for (int l = 0; l < 64; ++l) s += red[l * Y::NS + lane];
-    P[Y::O_ST + lane] = s;
-  }
+  sac_epilogue(net, a.partials + (int64_t)blockIdx.x * Y::NP, reinterpret_cast<double*>(qs), st, lane);
 }
 
 // Agent k of two under one centralized twin critic (qr_ctde_sac_actor_grad): <15, 16, 4> for k = 0, <3, 4, 1> for k = 1.
@@ -420,14 +471,14 @@ __global__ __launch_bounds__(64) void sac_actor_kernel(const SacActorArgs a) {
 // gl is then 0) before the ONE backward pass; logp and alpha's gradient are the second sample's.  Without it: the one-agent arithmetic.
 // The other agent's action is a VALUE: no gradient for agent 1-k is produced and nothing of that actor is written (the reference's
 // backward pass leaves one in that actor's .grad, which that agent zeroes before anything reads it; include/quadrotor_hip.h).
-// This body is a FOURTH copy of the tile walk: as ONE force-inlined function with the form as a compile-time argument, dpg_walk's
-// way, the one-agent kernels came out with 24 and 48 bytes more scratch per lane, so sac_actor_kernel above is
-// textually the parent's and a fix to its walk has to be made here too.
+// Shared with sac_actor_kernel: every block above.  This kernel's own: the other agent's staging and action, the second sample with
+// its park tile, the choice of gl, and the glue of the loss pass, which differs in every other line (xcol, acol, `two`).  The walk as
+// ONE force-inlined function, dpg_walk's way, cost the one-agent kernels 24 and 48 bytes of scratch per lane; block
+// by block all five instantiations stay at or below their registers, LDS and scratch from before the blocks were shared.
 template <int D, int H, int A>
 __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorArgs a) {
   using Net = PpoNet<D, H, A>;
   using SN = SacNet<D, H, A>;
-  using PY = PpoLayout<D, H, A>;
   using Y = SacLayout<D, H, A>;
   constexpr int XS = Net::XS, HS = Net::HS;
   __shared__ float sm[Net::SM], sl[SN::SL];
@@ -446,48 +497,25 @@ __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorAr
                         sizeof(was) + sizeof(dq) + sizeof(src) + sizeof(src1) + sizeof(osm) + sizeof(osl) + sizeof(park) <= 64 * 1024 - 64,
                 "static LDS stays under 64 KB");
   const int lane = threadIdx.x;
-  const int QH = a.hidden;
-  const int IN = a.in_dim, xcol = a.col_own, acol = a.acol_own;  // the critics' width, agent k's observation and action columns in their row
-  const bool two = a.eps_logp != nullptr;                        // the entropy term comes from a second sample
-  SN net;
-  net.zero();
-  {
-    PpoArgs p{};
-    p.w = a.w;
-    p.noise = a.noise;
-    Net::fill(sm, p, lane);
-    SN::fill(sl, a.w, lane);
-  }
-  if (!a.action_other) {
+  const int xcol = a.col_own, acol = a.acol_own;  // agent k's observation and action columns in the critics' row
+  const bool two = a.eps_logp != nullptr;         // the entropy term comes from a second sample
+  if (!a.action_other) {                          // (before the prologue's barrier)
     PpoArgs p{};
     p.w = a.other;
     ONet::fill(osm, p, lane);
     OSN::fill(osl, a.other, lane);
   }
-  for (int i = lane; i < 64 * XS; i += 64) xs[i] = (i % XS == D) ? 1.0f : 0.0f;  // the ones column; the rest of the padding stays zero
-  for (int i = lane; i < 64 * HS; i += 64) hs[i] = (i % HS == H) ? 1.0f : 0.0f;
-  for (int i = lane; i < 64 * kMgX; i += 64) qs[i] = 0.0f;                       // columns >= IN stay zero
-  __syncthreads();
-  const float alpha = a.alpha_dev ? a.alpha_dev[0] : a.alpha;
-  const bool any_reg = a.lam_T != 0.0f || a.lam_S != 0.0f || a.lam_M != 0.0f;
-  float nominal[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) nominal[j] = a.nominal ? a.nominal[j] : 0.0f;
+  SN net;
+  float alpha, nominal[A];
+  bool any_reg;
   double st[Y::NS];
-#pragma unroll
-  for (int q = 0; q < Y::NS; ++q) st[q] = 0.0;
+  sac_prologue(net, a, sm, sl, xs, hs, qs, lane, alpha, any_reg, nominal, st);
 
   const int64_t tiles = (a.B + 63) / 64;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t row0 = tile * 64;
     const bool active = row0 + lane < a.B;
-    int64_t i = active ? (a.index ? a.index[row0 + lane] : row0 + lane) : 0;
-    i = i < 0 ? 0 : (i >= a.rows ? a.rows - 1 : i);  // never a read outside the buffer
-    auto noise_row = [&](int which, float (&e)[A]) {  // by minibatch position; NULL: zeros through the same code
-      const float* p = a.eps[which];
-#pragma unroll
-      for (int j = 0; j < A; ++j) e[j] = (p && active) ? p[(row0 + lane) * A + j] : 0.0f;
-    };
+    const int64_t i = sac_row_index(a.index, a.rows, row0 + lane, active);
     src[lane] = active ? a.obs + i * D : nullptr;
     src1[lane] = active ? a.obs_other + i * a.od_other : nullptr;
     __syncthreads();
@@ -503,7 +531,7 @@ __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorAr
 #pragma unroll
         for (int k = 0; k < OD; ++k) xo[k] = qs[lane * kMgX + a.col_other + k];
         OSN::forward(osm, osl, xo, g1, g2, mo, lo);
-#pragma unroll
+#pragma unroll  // (not through sac_noise_row<OA>: that moved <3,4,1>'s scratch from 1504 to 1520 bytes per lane, the parent's being 1512)
         for (int f = 0; f < OA; ++f) eo[f] = (a.eps_other && active) ? a.eps_other[(row0 + lane) * OA + f] : 0.0f;
         SacRow<OA> so;
         so.sample(mo, lo, eo);
@@ -518,7 +546,7 @@ __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorAr
 #pragma unroll
       for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
       SN::forward(sm, sl, x, h1, h2, mean, lsr);
-      noise_row(0, e);
+      sac_noise_row(a.eps[0], row0 + lane, active, e);
       SacRow<A> s;
       s.sample(mean, lsr, e);
       if (active) {
@@ -545,42 +573,11 @@ __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorAr
       for (int u = 0; u < H; ++u) { hs[lane * HS + u] = h1[u]; ds[lane * kPpoDelta + u] = h2[u]; }
 #pragma unroll
       for (int j = 0; j < A; ++j) qs[lane * kMgX + acol + j] = s.act[j];  // no clamp on the loss pass's action
-#pragma unroll 1
-      for (int n = 0; n < 2; ++n) {
-        __syncthreads();  // the previous critic's reads are done
-        float a2[4][4][4];
-        {
-          float a2t[4][4][4];
-          load_fc2(a2, a2t, a.q[n].fc2_w, QH, lane);
-#pragma unroll
-          for (int k = 0; k < 64; ++k) w2ts[64 * k + lane] = a2t[k >> 4][(k >> 2) & 3][k & 3];
-        }
-        twinq_fill_small(w1s, svec, a.q[n], IN, QH, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) was[4 * lane + j] = (lane < QH && j < A) ? a.q[n].fc1_w[lane * IN + acol + j] : 0.0f;
-        const float bias3 = a.q[n].fc3_b[0];
-        __syncthreads();
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half)
-          dpg_q1_half<A>(a2, lds_here(w2ts), qs + 32 * half * kMgX, lds_here(w1s), lds_here(svec), was, dq[n] + 32 * half * kDpgQ, bias3, lane);
-      }
-      __syncthreads();
+      sac_critics<A>(a.q, a.in_dim, acol, a.hidden, qs, w1s, w2ts, svec, was, dq[0], lane);
 #pragma unroll
       for (int u = 0; u < H; ++u) { h1[u] = hs[lane * HS + u]; h2[u] = ds[lane * kPpoDelta + u]; }
-      // min(Q1, Q2): a row's gradient goes to the smaller critic; torch gives each half on an exact tie
-      const float q1 = dq[0][lane * kDpgQ + 4], q2 = dq[1][lane * kDpgQ + 4];
-      const float w2 = q2 < q1 ? 1.0f : (q2 == q1 ? 0.5f : 0.0f);
-      if (active) {
-        st[0] += (double)fminf(q1, q2);
-        st[6] += q2 < q1 ? 1.0 : 0.0;
-      }
       float ga[A], dmean[A], dls[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) {
-        const float d1 = dq[0][lane * kDpgQ + j], d2 = dq[1][lane * kDpgQ + j];
-        const float d = w2 == 1.0f ? d2 : (w2 == 0.0f ? d1 : 0.5f * d1 + 0.5f * d2);
-        ga[j] = -a.inv_b * d;  // d(-mean min Q) / da
-      }
+      sac_select(dq[0], a.inv_b, active, lane, st, ga);
       s.deltas(ga, two ? 0.0f : alpha * a.inv_b, active, dmean, dls);
       if (two) {
 #pragma unroll
@@ -589,89 +586,10 @@ __global__ __launch_bounds__(64) void ctde_sac_actor_kernel(const CtdeSacActorAr
       net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier)
     }
 
-    // ---- policy_regularization: its own sample r and the three smoothness terms
-    if (any_reg) {
-      float x[D], h1[H], h2[H], mean[A], lsr[A], e[A], r[A], gr[A];
-#pragma unroll
-      for (int k = 0; k < D; ++k) x[k] = xs[lane * XS + k];
-      SN::forward(sm, sl, x, h1, h2, mean, lsr);
-      noise_row(1, e);
-      SacRow<A> s;
-      s.sample(mean, lsr, e);
-#pragma unroll
-      for (int j = 0; j < A; ++j) {
-        r[j] = fminf(fmaxf(s.act[j], -a.max_action), a.max_action);
-        gr[j] = 0.0f;
-      }
-      if (a.lam_M != 0.0f) {
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float d = r[j] - nominal[j];
-          if (active) st[4] += (double)(d * d);
-          gr[j] = fmaf(a.c_M, d, gr[j]);
-        }
-      }
-      // a smoothness pass on other input rows y: the difference enters both ends — gr for r's pass, -c d for y's own, here
-      auto other = [&](const float (&y)[D], int which, float c, double& sum) {
-        float g1[H], g2[H], mo[A], lo[A], eo[A], go[A], dmo[A], dlo[A];
-        SN::forward(sm, sl, y, g1, g2, mo, lo);
-        noise_row(which, eo);
-        SacRow<A> so;
-        so.sample(mo, lo, eo);
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float d = r[j] - fminf(fmaxf(so.act[j], -a.max_action), a.max_action);
-          if (active) sum += (double)(d * d);
-          gr[j] = fmaf(c, d, gr[j]);
-          go[j] = fabsf(so.act[j]) <= a.max_action ? -c * d : 0.0f;
-        }
-        so.deltas(go, 0.0f, active, dmo, dlo);
-        net.backward(sm, sl, xs, hs, ds, g1, g2, dmo, dlo, lane);
-      };
-      if (a.lam_S != 0.0f) {
-        float y[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) { y[k] = xs[lane * XS + k] + sm[Net::O_NOISE + k]; xs[lane * XS + k] = y[k]; }
-        other(y, 3, a.c_S, st[3]);
-      }
-      if (a.lam_T != 0.0f) {
-        src[lane] = active ? a.obs_next + i * D : nullptr;
-        __syncthreads();
-        ppo_stage<D, XS>(xs, src, lane);
-        __syncthreads();
-        float y[D];
-#pragma unroll
-        for (int k = 0; k < D; ++k) y[k] = xs[lane * XS + k];
-        other(y, 2, a.c_T, st[2]);
-      }
-      if (a.lam_S != 0.0f || a.lam_T != 0.0f) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) xs[lane * XS + k] = qs[lane * kMgX + xcol + k];
-      }
-      float ga[A], dmean[A], dls[A];
-#pragma unroll
-      for (int j = 0; j < A; ++j) ga[j] = fabsf(s.act[j]) <= a.max_action ? gr[j] : 0.0f;
-      s.deltas(ga, 0.0f, active, dmean, dls);
-      net.backward(sm, sl, xs, hs, ds, h1, h2, dmean, dls, lane);  // (ends with a barrier: the tiles are free for the next rows)
-    }
+    if (any_reg) sac_regularize(net, a, sm, sl, xs, hs, ds, qs, src, xcol, nominal, st, i, row0 + lane, active, lane);
   }
 
-  double* P = a.partials + (int64_t)blockIdx.x * Y::NP;
-  Net::template emit<D, Net::NB1>(P + PY::O_W1, P + PY::O_B1, net.acc1, H, lane);
-  Net::template emit<H, Net::NBH>(P + PY::O_W2, P + PY::O_B2, net.acc2, H, lane);
-  Net::template emit<H, Net::NBH>(P + PY::O_W3, P + PY::O_B3, net.acc3, A, lane);
-  SN::emit_head2(P + Y::O_LW, P + Y::O_LB, net.acc3, lane);
-  // the per-lane sums: across the lanes in lane order
-  double* red = reinterpret_cast<double*>(qs);
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < Y::NS; ++q) red[lane * Y::NS + q] = st[q];
-  __syncthreads();
-  if (lane < Y::NS) {
-    double s = 0.0;
-    for (int l = 0; l < 64; ++l) s += red[l * Y::NS + lane];
-    P[Y::O_ST + lane] = s;
-  }
+  sac_epilogue(net, a.partials + (int64_t)blockIdx.x * Y::NP, reinterpret_cast<double*>(qs), st, lane);
 }
 
 
@@ -695,10 +613,7 @@ __global__ __launch_bounds__(256) void sac_actor_reduce_kernel(const SacActorRed
   if (blockIdx.x + 1 < gridDim.x) {
     const int e = reduce16_entries(o.partials, o.n_parts, o.np, o.off[8], red);
     if (e >= 0) {
-      int k = 0;
-#pragma unroll
-      for (int j = 1; j < 8; ++j)
-        if (e >= o.off[j]) k = j;
+      const int k = entry_tensor<8>(e, o.off);
       float* dst = o.grad[0];
 #pragma unroll
       for (int j = 1; j < 8; ++j)

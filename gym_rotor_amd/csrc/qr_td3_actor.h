@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void dpg_reduce_kernel(const DpgReduceArgs o) 
   if (blockIdx.x + 1 < gridDim.x) {
     const int e = reduce16_entries(o.partials, o.n_parts, o.np, o.off[6], red);
     if (e >= 0) {
-      const int k = entry_tensor(e, o.off);
+      const int k = entry_tensor<6>(e, o.off);
       float* dst = o.grad[0];
 #pragma unroll
       for (int j = 1; j < 6; ++j)

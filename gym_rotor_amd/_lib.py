@@ -39,7 +39,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes",
            "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
-           "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes")
+           "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
+           "qr_replay_add", "qr_replay_sample")
 
 
 class QrCoeffs(C.Structure):
@@ -309,6 +310,43 @@ def ctde_sac_actor_grad_args(grads, stats, workspace, *, agent, action_other, ep
     return g
 
 
+REPLAY_MAX_WIDTH = 4096   # qr_replay_add: widest observation or action row
+REPLAY_BUFFER_NAMES = ("obs", "obs_next", "act", "rwd", "done")   # an agent's five buffer tensors (ReplayBuffer.tensors), in QrReplayAdd's order
+
+
+class QrReplayAdd(C.Structure):
+    _fields_ = [("obs", C.c_void_p * 2), ("final_obs", C.c_void_p * 2), ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("truncated", C.c_void_p), ("buf_obs", C.c_void_p * 2), ("buf_obs_next", C.c_void_p * 2), ("buf_action", C.c_void_p * 2),
+                ("buf_reward", C.c_void_p * 2), ("buf_done", C.c_void_p * 2), ("state", C.c_void_p), ("count", C.c_int64), ("capacity", C.c_int64),
+                ("n_envs", C.c_int64), ("n_steps", C.c_int32), ("n_agents", C.c_int32), ("obs_dim", C.c_int32 * 2), ("action_dim", C.c_int32 * 2),
+                ("col_offset", C.c_int32 * 2), ("action_row", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class QrReplaySample(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("status", C.c_void_p), ("state", C.c_void_p), ("n", C.c_int64), ("batch", C.c_int64),
+                ("seed", C.c_uint64), ("draw", C.c_uint64)]
+
+
+def replay_add_args(buffers, obs, final_obs, action, reward, done, truncated, *, state, count, capacity, n_steps, n_envs, obs_dims, action_dims,
+                    col_offsets, action_row) -> QrReplayAdd:
+    """QrReplayAdd of one qr_replay_add launch: buffers = one {name: tensor} over REPLAY_BUFFER_NAMES per agent (one or two); obs a list
+    per agent, final_obs one or None; state: the device counters or None."""
+    r = QrReplayAdd()
+    for k, b in enumerate(buffers):
+        r.obs[k], r.final_obs[k] = ptr(obs[k]), (None if final_obs is None else ptr(final_obs[k]))
+        r.buf_obs[k], r.buf_obs_next[k], r.buf_action[k], r.buf_reward[k], r.buf_done[k] = (ptr(b[n]) for n in REPLAY_BUFFER_NAMES)
+        r.obs_dim[k], r.action_dim[k], r.col_offset[k] = int(obs_dims[k]), int(action_dims[k]), int(col_offsets[k])
+    r.action, r.reward, r.done, r.truncated, r.state = ptr(action), ptr(reward), ptr(done), ptr(truncated), ptr(state)
+    r.count, r.capacity, r.n_envs, r.n_steps, r.n_agents = int(count), int(capacity), int(n_envs), int(n_steps), len(buffers)
+    r.action_row, r.reserved0 = int(action_row), 0
+    return r
+
+
+def replay_sample_args(index, status, state, *, n, batch, seed, draw) -> QrReplaySample:
+    """QrReplaySample of one qr_replay_sample launch; status, state: device tensors or None."""
+    return QrReplaySample(ptr(index), ptr(status), ptr(state), int(n), int(batch), int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1))
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -482,6 +520,10 @@ def load():
     lib.qr_ctde_sac_actor_grad.argtypes = [P(QrActor), P(QrActor), P(QrQCritic), P(QrCtdeTransitions), P(QrCtdeSacActorGrad), C.c_void_p]
     lib.qr_ctde_sac_actor_workspace_bytes.restype = C.c_int64
     lib.qr_ctde_sac_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
+    lib.qr_replay_add.restype = C.c_int
+    lib.qr_replay_add.argtypes = [P(QrReplayAdd), C.c_void_p]
+    lib.qr_replay_sample.restype = C.c_int
+    lib.qr_replay_sample.argtypes = [P(QrReplaySample), C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -54,10 +54,12 @@
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel;
 //                  agent k's actor half under the centralized (CTDE) twin critic (qr_ctde_sac_actor_grad): ctde_sac_actor_kernel
+//   qr_replay.h    the replay buffer's append and its minibatch indices (qr_replay_add, qr_replay_sample): replay_add_kernel, replay_sample_kernel,
+//                  replay_advance_kernel (the opt-in device counters)
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
-//                  sac_actor_launch (qr_sac_actor_grad and qr_ctde_sac_actor_grad)
+//                  sac_actor_launch (qr_sac_actor_grad and qr_ctde_sac_actor_grad), do_replay_add and do_replay_sample
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -82,6 +84,7 @@
 #include "qr_td3_actor.h"
 #include "qr_sac.h"
 #include "qr_sac_actor.h"
+#include "qr_replay.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -683,9 +686,71 @@ static int do_soft_update(const QrSoftUpdate* u, void* stream) {
                      reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
+
+// ceil(2^32 / w) for w >= 2: what replay_add_kernel splits a tile offset into (row, column) with
+static uint32_t replay_magic(int32_t w) { return w >= 2 ? 0xFFFFFFFFu / (uint32_t)w + 1u : 0u; }
+
+static int do_replay_add(const QrReplayAdd* r, void* stream) {
+  if (!r) return QR_E_NULL;
+  if (r->n_agents < 1 || r->n_agents > 2 || r->reserved0 != 0 || r->capacity < 1 || r->n_steps < 1 || r->n_envs < 1) return QR_E_SIZE;
+  if (r->n_envs > r->capacity || (int64_t)r->n_steps * r->n_envs > r->capacity) return QR_E_SIZE;
+  if (!r->state && (r->count < 0 || r->count >= r->capacity)) return QR_E_SIZE;
+  if (r->action_row < 1) return QR_E_SIZE;
+  for (int k = 0; k < r->n_agents; ++k) {
+    if (r->obs_dim[k] < 1 || r->obs_dim[k] > kReplayMaxWidth || r->action_dim[k] < 1 || r->action_dim[k] > kReplayMaxWidth) return QR_E_SIZE;
+    if (r->col_offset[k] < 0 || (int64_t)r->col_offset[k] + r->action_dim[k] > r->action_row) return QR_E_SIZE;
+  }
+  if (!r->action || !r->reward || !r->done) return QR_E_NULL;
+  for (int k = 0; k < r->n_agents; ++k)
+    if (!r->obs[k] || !r->buf_obs[k] || !r->buf_obs_next[k] || !r->buf_action[k] || !r->buf_reward[k] || !r->buf_done[k]) return QR_E_NULL;
+  if (r->n_agents == 2 && (r->final_obs[0] == nullptr) != (r->final_obs[1] == nullptr)) return QR_E_NULL;
+  uintptr_t bits = reinterpret_cast<uintptr_t>(r->action) | reinterpret_cast<uintptr_t>(r->reward);
+  for (int k = 0; k < r->n_agents; ++k)
+    for (const void* p : {(const void*)r->obs[k], (const void*)r->final_obs[k], (const void*)r->buf_obs[k], (const void*)r->buf_obs_next[k],
+                          (const void*)r->buf_action[k], (const void*)r->buf_reward[k], (const void*)r->buf_done[k]})
+      bits |= reinterpret_cast<uintptr_t>(p);
+  if ((bits & 3u) || (reinterpret_cast<uintptr_t>(r->state) & 7u)) return QR_E_ALIGN;
+  const bool two = r->n_agents == 2;
+  ReplayAddArgs a{};
+  a.obs0 = r->obs[0]; a.final0 = r->final_obs[0];
+  a.b_obs0 = r->buf_obs[0]; a.b_next0 = r->buf_obs_next[0]; a.b_act0 = r->buf_action[0]; a.b_rwd0 = r->buf_reward[0]; a.b_done0 = r->buf_done[0];
+  a.D0 = r->obs_dim[0]; a.A0 = r->action_dim[0]; a.col0 = r->col_offset[0]; a.next0 = r->n_envs * r->obs_dim[0];
+  a.mD0 = replay_magic(a.D0); a.mA0 = replay_magic(a.A0);
+  if (two) {
+    a.obs1 = r->obs[1]; a.final1 = r->final_obs[1];
+    a.b_obs1 = r->buf_obs[1]; a.b_next1 = r->buf_obs_next[1]; a.b_act1 = r->buf_action[1]; a.b_rwd1 = r->buf_reward[1]; a.b_done1 = r->buf_done[1];
+    a.D1 = r->obs_dim[1]; a.A1 = r->action_dim[1]; a.col1 = r->col_offset[1]; a.next1 = r->n_envs * r->obs_dim[1];
+    a.mD1 = replay_magic(a.D1); a.mA1 = replay_magic(a.A1);
+  }
+  a.action = r->action; a.reward = r->reward; a.done = r->done; a.truncated = r->truncated;
+  a.state = r->state; a.count = r->count; a.capacity = r->capacity; a.rows = (int64_t)r->n_steps * r->n_envs;
+  a.action_row = r->action_row; a.n_agents = r->n_agents;
+  const int64_t tiles = (a.rows + kReplayTile - 1) / kReplayTile;
+  hipLaunchKernelGGL(replay_add_kernel, dim3((unsigned)(tiles < kReplayCols ? tiles : kReplayCols), (unsigned)(kReplaySegments * r->n_agents)),
+                     dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  if (r->state) hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), r->state, a.rows, r->capacity, (int64_t)0);
+  return (int)hipGetLastError();
+}
+
+static int do_replay_sample(const QrReplaySample* s, void* stream) {
+  if (!s) return QR_E_NULL;
+  if (s->batch < 1 || s->batch > s->n || s->n > 0x7FFFFFFFll) return QR_E_SIZE;
+  if (!s->index) return QR_E_NULL;
+  if (((reinterpret_cast<uintptr_t>(s->index) | reinterpret_cast<uintptr_t>(s->state)) & 7u) || (reinterpret_cast<uintptr_t>(s->status) & 3u)) return QR_E_ALIGN;
+  const ReplaySampleArgs a{s->index, s->status, s->state, s->n, s->batch, s->seed, s->draw};
+  hipLaunchKernelGGL(replay_sample_kernel, dim3((unsigned)((s->batch + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  if (s->state) hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), s->state, (int64_t)0, (int64_t)1, (int64_t)1);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_replay_add(const QrReplayAdd* add, void* stream) { return qr::do_replay_add(add, stream); }
+
+int qr_replay_sample(const QrReplaySample* sample, void* stream) { return qr::do_replay_sample(sample, stream); }
 
 int qr_dpg_actor_grad(const QrActor* actor, const QrQCritic* critic, const QrTransitions* batch, const QrDpgGrad* grad, void* stream) {
   return qr::do_dpg_actor(actor, critic, batch, grad, stream);

@@ -17,6 +17,11 @@ So does agent k's actor half under that critic (td3.py:180-196): `dpg_actor_grad
 `td3_actor_loss_ctde` — the other agent's actor runs forward only inside the kernel (or its action is supplied), and only agent k's
 six gradients are produced.  A written-out CTDE iteration is `td3_critic_loss_ctde`, optimiser, `td3_actor_loss_ctde`, optimiser,
 `soft_update`, with no autograd in it.
+
+The data side matches: `ReplayBuffer.append` writes a whole horizon into the ring in one launch (`replay_add`: qr_replay_add), and
+`ReplayBuffer.sample_index` draws a minibatch's distinct rows in O(B) (`replay_sample`: qr_replay_sample) — a keyed permutation of
+[0, current_size) in integers, not a permutation of the whole buffer.  `use_device_state()` moves the three counters into device
+memory, so an iteration that appends and samples can be captured in a graph once and replayed.
 """
 from __future__ import annotations
 
@@ -33,9 +38,10 @@ class ReplayBuffer:
     """The reference's `ReplayBuffer` (algos/replay_buffer.py) for TD3 / SAC as flat device tensors per agent k:
         obs[k], obs_next[k] [capacity, D_k]   act[k] [capacity, A_k]   rwd[k], done[k] [capacity] float32 (done: 0.0 / 1.0)
     `count` (the next row to write) and `current_size` follow the reference's ring rule, one transition at a time:
-    count = (count + 1) % capacity, current_size = min(current_size + 1, capacity)."""
+    count = (count + 1) % capacity, current_size = min(current_size + 1, capacity).
+    seed: the 64-bit key of `sample_index`'s draws (`seed(s)` changes it); `draw` counts them."""
 
-    def __init__(self, capacity: int, obs_dims: Sequence[int], action_dims: Sequence[int], device):
+    def __init__(self, capacity: int, obs_dims: Sequence[int], action_dims: Sequence[int], device, seed: int = 0):
         self.capacity = int(capacity)
         self.obs_dims, self.action_dims = [int(d) for d in obs_dims], [int(a) for a in action_dims]
         if self.capacity < 1 or len(self.obs_dims) != len(self.action_dims) or not self.obs_dims:
@@ -49,6 +55,10 @@ class ReplayBuffer:
         self.rwd = [torch.zeros(n, **f32) for _ in self.obs_dims]
         self.done = [torch.zeros(n, **f32) for _ in self.obs_dims]
         self.count, self.current_size = 0, 0
+        self.draw = 0          # minibatches drawn by sample_index: with the seed, the key of the next one
+        self.seed(seed)
+        self.state = None      # use_device_state(): int64 [3] = (count, current_size, draw) on the device
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)   # qr_replay_sample raises it if a walk hits its cap (it cannot)
         self._cache = {}   # (agent, B, max_workgroups) -> y, workspace, stats of td3_critic_loss; ("actor", ...) -> td3_actor_loss's
 
     @property
@@ -80,6 +90,54 @@ class ReplayBuffer:
                     dst[:n - first].copy_(src[first:])
         self.count = (self.count + n) % self.capacity
         self.current_size = min(self.current_size + n, self.capacity)
+        if self.state is not None:   # the device counters follow: one copy, enqueued
+            self.state.copy_(torch.tensor([self.count, self.current_size, self.draw], dtype=torch.int64), non_blocking=True)
+
+    def seed(self, seed: int) -> None:
+        """The 64-bit key of `sample_index`.  `draw` keeps counting, so no (seed, draw) pair comes twice."""
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"ReplayBuffer: seed must lie in [0, 2^64), got {seed}")
+        self._seed = seed
+
+    def use_device_state(self) -> torch.Tensor:
+        """Keep (count, current_size, draw) in an int64 [3] device tensor as well: from here on `append` and `sample_index` read them
+        there and advance them there with a one-thread launch, so both can be captured in a `torch.cuda.graph` and every replay
+        appends at the advanced position and draws a fresh minibatch.  The host's ints keep advancing by the same rule with every
+        eager call (nothing is synchronised) — capturing counts as one — while replays of a graph advance the tensor only:
+        `pull_device_state()` reads it back.
+        `add` refreshes the tensor from the host's ints.  Returns the tensor."""
+        if self.state is None:
+            self.state = torch.tensor([self.count, self.current_size, self.draw], dtype=torch.int64).to(self.device)
+        return self.state
+
+    def pull_device_state(self) -> None:
+        """Set the host's ints from the device counters (synchronises): after replays of a captured graph."""
+        if self.state is None:
+            raise ValueError("ReplayBuffer: no device state (use_device_state() was not called)")
+        self.count, self.current_size, self.draw = (int(v) for v in self.state.tolist())
+
+    def append(self, storage) -> None:
+        """`add` in ONE launch (qr_replay_add): the same T * N transitions into the same ring rows with the same obs_next and done
+        rule, bit for bit, for all agents and all five tensors, without a temporary."""
+        T, N = storage.T, storage.N
+        n = T * N
+        if n > self.capacity:
+            raise ValueError(f"a horizon of {T} x {N} = {n} transitions does not fit a buffer of {self.capacity}")
+        if storage.n_agents != self.n_agents or [o.shape[-1] for o in storage.obs] != self.obs_dims or list(storage.action_dims) != self.action_dims:
+            raise ValueError("the storage's agents, observation widths or action widths differ from the buffer's")
+        replay_add([self.tensors(k) for k in range(self.n_agents)], storage.obs, storage.final_obs, storage.act_all, storage.reward, storage.done,
+                   storage.truncated, self.count, state=self.state)
+        self.count = (self.count + n) % self.capacity
+        self.current_size = min(self.current_size + n, self.capacity)
+
+    def sample_index(self, batch_size: int, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 [batch_size] pairwise distinct rows below current_size in one O(batch_size) launch (qr_replay_sample): the images of
+        0 .. batch_size - 1 under the permutation of [0, current_size) keyed by (seed, draw); draw then advances.  out: an int64
+        [batch_size] tensor on the buffer's device, written in place — a steady-state call then allocates nothing."""
+        out = replay_sample(self.current_size, batch_size, self._seed, self.draw, out, device=self.status.device, state=self.state, status=self.status)
+        self.draw += 1
+        return out
 
     def sample(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """int64 [batch_size] rows below current_size, without replacement (np.random.choice(current_size, batch_size, replace=False))."""
@@ -91,6 +149,111 @@ class ReplayBuffer:
     def tensors(self, k: int) -> dict:
         """Agent k's five tensors, as `td3_target` / `twinq_grad` take them."""
         return {"obs": self.obs[k], "act": self.act[k], "rwd": self.rwd[k], "obs_next": self.obs_next[k], "done": self.done[k]}
+
+
+def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, truncated: Optional[torch.Tensor],
+               count: int, *, state: Optional[torch.Tensor] = None) -> None:
+    """One collected horizon into the ring of a flat transition buffer in one launch (qr_replay_add).  tensors: per agent (one or two)
+    a dict with obs, obs_next [capacity, D_k], act [capacity, A_k], rwd, done [capacity], contiguous float32 (`ReplayBuffer.tensors(k)`),
+    written in place.  The horizon as `RolloutStorage` holds it: obs a list of [T + 1, N, D_k]; final_obs a list of [T, N, D_k] or None;
+    action [T, N, sum A_k], the agents' columns side by side; reward [T, N, n_agents] float32; done [T, N, n_agents] and truncated
+    [T, N] (or None) bool.  Transition j = t * N + n goes to row (count + j) % capacity; obs_next is final_obs[t, n] where it is given and
+    any agent's done or truncated is set, obs[t + 1, n] elsewhere; done is agent k's own flag as 0.0 / 1.0.  The caller advances its
+    counters: count = (count + T * N) % capacity, current_size = min(current_size + T * N, capacity).  state: the int64 [3] device
+    counters (count, current_size, draw), read on the device instead of `count` and advanced there behind the launch."""
+    what = "replay_add"
+    tensors = [dict(t) for t in tensors]
+    obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
+    if final_obs is not None:
+        final_obs = [final_obs] if isinstance(final_obs, torch.Tensor) else list(final_obs)
+    na = len(tensors)
+    if na not in (1, 2) or len(obs) != na or (final_obs is not None and len(final_obs) != na):
+        raise ValueError(f"{what}: one or two agents, with one obs (and final_obs) tensor per agent; got {na} buffers, {len(obs)} obs")
+    b0 = tensors[0].get("obs")
+    if b0 is None or b0.dim() != 2:
+        raise ValueError(f"{what}: agent 0's buffer obs must be a contiguous float32 [capacity, D] tensor")
+    dev, capacity = b0.device, b0.shape[0]
+    if action is None or action.dim() != 3 or obs[0] is None or obs[0].dim() != 3:
+        raise ValueError(f"{what}: action must be [T, N, A] and obs[k] [T + 1, N, D_k]")
+    T, N, row = action.shape
+    od, ad = [], []
+    for k, t in enumerate(tensors):
+        a = t.get("act")
+        if a is None or a.dim() != 2 or t.get("obs") is None or t["obs"].dim() != 2:
+            raise ValueError(f"{what}: agent {k}'s buffer obs and act must be contiguous float32 [capacity, width] tensors")
+        od.append(t["obs"].shape[1])
+        ad.append(a.shape[1])
+    if sum(ad) != row or min(od + ad) < 1 or max(od + ad) > _lib.REPLAY_MAX_WIDTH:
+        raise ValueError(f"{what}: the buffers' action widths {ad} must add up to the action row's {row}; widths lie in 1..{_lib.REPLAY_MAX_WIDTH}")
+    if T < 1 or N < 1 or T * N > capacity:
+        raise ValueError(f"{what}: a horizon of {T} x {N} = {T * N} transitions does not fit a buffer of {capacity}")
+    def need(x, shape, dtype, name):
+        if x is None or x.dtype != dtype or x.device != dev or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    for k, t in enumerate(tensors):
+        for name, shape in (("obs", (capacity, od[k])), ("obs_next", (capacity, od[k])), ("act", (capacity, ad[k])), ("rwd", (capacity,)), ("done", (capacity,))):
+            need(t.get(name), shape, torch.float32, f"agent {k}'s buffer {name}")
+        need(obs[k], (T + 1, N, od[k]), torch.float32, f"obs[{k}]")
+        if final_obs is not None:
+            need(final_obs[k], (T, N, od[k]), torch.float32, f"final_obs[{k}]")
+    need(action, (T, N, row), torch.float32, "action")
+    need(reward, (T, N, na), torch.float32, "reward")
+    need(done, (T, N, na), torch.bool, "done")
+    if truncated is not None:
+        need(truncated, (T, N), torch.bool, "truncated")
+    _check_state(what, state, dev)
+    count = int(count)
+    if state is None and not 0 <= count < capacity:
+        raise ValueError(f"{what}: count must lie in [0, {capacity}), got {count}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    r = _lib.replay_add_args(tensors, obs, final_obs, action, reward, done, truncated, state=state, count=count if state is None else 0,
+                             capacity=capacity, n_steps=T, n_envs=N, obs_dims=od, action_dims=ad,
+                             col_offsets=[sum(ad[:k]) for k in range(na)], action_row=row)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_replay_add(C.byref(r), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_replay_add")
+
+
+def _check_state(what: str, state, dev):
+    if state is not None and (state.dtype != torch.int64 or state.device != dev or tuple(state.shape) != (3,) or not state.is_contiguous()):
+        raise ValueError(f"{what}: state must be a contiguous int64 [3] tensor (count, current_size, draw) on {dev}")
+
+
+def replay_sample(n: int, batch_size: int, seed: int, draw: int, out: Optional[torch.Tensor] = None, *, device=None,
+                  state: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [batch_size] pairwise distinct rows in [0, n), 1 <= batch_size <= n < 2^31, in one O(batch_size) launch (qr_replay_sample):
+    index[j] is the image of j under the permutation of [0, n) keyed by the 64-bit (seed, draw) — a six-round Feistel network over
+    Philox4x32-10, cycle-walked into [0, n); integers only, so tests/replay_ref.py gives the same indices on the CPU.  Use a (seed, draw)
+    pair once: draw counts the calls.  out: written in place (None: made on `device`, by default the current GPU).  state: the int64 [3]
+    device counters; n = state[1] and draw = state[2] are then read on the device, and state[2] advances behind the launch.  status: an
+    int32 [1] device tensor that the launch sets to 1 should a walk reach its cap (it cannot), or None."""
+    what = "replay_sample"
+    n, B, seed, draw = int(n), int(batch_size), int(seed), int(draw)
+    if n >= 2 ** 31:
+        raise ValueError(f"{what}: n must be below 2^31, got {n}")
+    if not 1 <= B <= n:
+        raise ValueError(f"cannot sample {B} of {n} transitions without replacement")
+    if not 0 <= seed < 2 ** 64 or not 0 <= draw < 2 ** 64:
+        raise ValueError(f"{what}: seed and draw must lie in [0, 2^64)")
+    dev = torch.device("cuda" if out is None else out.device) if device is None else torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if out is not None:
+        if out.dtype != torch.int64 or out.device != dev or tuple(out.shape) != (B,) or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous int64 [{B}] tensor on {dev}")
+    _check_state(what, state, dev)
+    if status is not None and (status.dtype != torch.int32 or status.device != dev or status.numel() != 1):
+        raise ValueError(f"{what}: status must be an int32 tensor of one element on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int64, device=dev)
+    s = _lib.replay_sample_args(out, status, state, n=n, batch=B, seed=seed, draw=draw)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_replay_sample(C.byref(s), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_replay_sample")
+    return out
 
 
 def _agent_tensors(buffer_or_tensors, k: int) -> dict:

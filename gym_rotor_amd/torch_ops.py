@@ -417,6 +417,29 @@ def qr_soft_update(params: List[torch.Tensor], targets: List[torch.Tensor], tau:
     soft_update(list(params), list(targets), tau)
 
 
+@torch.library.custom_op(f"{_NS}::qr_replay_add", mutates_args=("buffers", "state"))
+def qr_replay_add(buffers: List[torch.Tensor], obs: List[torch.Tensor], final_obs: List[torch.Tensor], action: torch.Tensor, reward: torch.Tensor,
+                  done: torch.Tensor, truncated: Optional[torch.Tensor], count: int, state: Optional[torch.Tensor]) -> None:
+    """One horizon into the ring of a flat transition buffer in one launch (qr_replay_add), as td3.replay_add.  buffers: per agent (one
+    or two) its five tensors obs, obs_next, act, rwd, done, one agent after the other; obs: one [T + 1, N, D_k] tensor per agent;
+    final_obs: one [T, N, D_k] per agent, or an empty list; state: the int64 [3] device counters, which win over count."""
+    from .td3 import replay_add
+    _gpu(action)
+    if len(buffers) not in (5, 10):
+        raise ValueError("a replay buffer is 5 tensors per agent: obs, obs_next, act, rwd, done")
+    tensors = [dict(zip(_lib.REPLAY_BUFFER_NAMES, buffers[5 * k:5 * k + 5])) for k in range(len(buffers) // 5)]
+    replay_add(tensors, list(obs), list(final_obs) if final_obs else None, action, reward, done, truncated, count, state=state)
+
+
+@torch.library.custom_op(f"{_NS}::qr_replay_sample", mutates_args=("out", "state", "status"))
+def qr_replay_sample(out: torch.Tensor, n: int, seed: int, draw: int, state: Optional[torch.Tensor], status: Optional[torch.Tensor]) -> None:
+    """out.numel() pairwise distinct rows below n in one O(B) launch (qr_replay_sample), as td3.replay_sample; seed and draw are passed as
+    int64 here (0 <= seed, draw < 2^63).  state: the int64 [3] device counters, whose current_size and draw win over n and draw."""
+    from .td3 import replay_sample
+    _gpu(out)
+    replay_sample(n, out.numel(), seed, draw, out, state=state, status=status)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_target", mutates_args=("y", "action_out", "logp_out"))
 def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
                   done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],

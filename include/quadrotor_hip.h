@@ -934,6 +934,67 @@ int qr_ctde_sac_actor_grad(const QrActor* actor_0, const QrActor* actor_1, const
  * and max_workgroups: qr_sac_actor_workspace_bytes' figure for that actor.  QR_E_SIZE (< 0) where the entry would refuse them. */
 int64_t qr_ctde_sac_actor_workspace_bytes(int32_t agent, int32_t critic_hidden_dim, int64_t batch, int32_t max_workgroups);
 
+/* ---- The replay buffer of TD3 / SAC: append and minibatch indices (algos/replay_buffer.py) ----
+ * The buffer is, per agent k, five flat device tensors of `capacity` rows: obs, obs_next [capacity][obs_dim[k]], action
+ * [capacity][action_dim[k]], reward, done [capacity] float32 (done: 0.0 / 1.0) — what QrTransitions / QrCtdeTransitions read.  Three
+ * counters go with it: count (the next row to write), current_size (the rows that hold a transition) and draw (the minibatches drawn).
+ * They live on the host and are passed by value, or — `state` not NULL — in device memory as int64 state[3] = {count, current_size,
+ * draw}: then both entries read them there and advance them there, with a one-thread launch of its own on the same stream behind the
+ * launch that read them, so a stream (or a captured graph of it) can append and sample any number of times without the host.
+ *
+ * The append of one collected horizon of n_steps x n_envs transitions in ONE launch (plus the counters' where state is given), for one or
+ * two agents.  Transition j = t * n_envs + n goes to ring row (count + j) mod capacity:
+ *     buf_obs[k][row]      = obs[k][t][n]
+ *     buf_obs_next[k][row] = final_obs[k][t][n]  where final_obs is given and any agent's done[t][n][.] or truncated[t][n] is set
+ *                          = obs[k][t + 1][n]    elsewhere
+ *     buf_action[k][row]   = action[t][n][col_offset[k] .. col_offset[k] + action_dim[k])
+ *     buf_reward[k][row]   = reward[t][n][k]        buf_done[k][row] = done[t][n][k] ? 1.0 : 0.0
+ * Values are copied bit for bit; no temporaries are made; rows outside the n_steps * n_envs written ones are not touched.  count is not
+ * advanced on the host's behalf: the caller's next count is (count + n_steps * n_envs) mod capacity, its current_size
+ * min(current_size + n_steps * n_envs, capacity) — which is what the device counters become. */
+typedef struct QrReplayAdd {
+  const float* obs[2];            /* [n_steps + 1][n_envs][obs_dim[k]] */
+  const float* final_obs[2];      /* [n_steps][n_envs][obs_dim[k]]; all NULL: obs_next is obs[t + 1] everywhere */
+  const float* action;            /* [n_steps][n_envs][action_row]: the agents' actions side by side */
+  const float* reward;            /* [n_steps][n_envs][n_agents] */
+  const uint8_t* done;            /* [n_steps][n_envs][n_agents] bool bytes */
+  const uint8_t* truncated;       /* [n_steps][n_envs] bool bytes, or NULL */
+  float* buf_obs[2];      float* buf_obs_next[2];   float* buf_action[2];   float* buf_reward[2];   float* buf_done[2];
+  int64_t* state;                 /* NULL, or device int64[3] = {count, current_size, draw}: read instead of `count`, then advanced */
+  int64_t count;                  /* the next row to write, 0 <= count < capacity (state NULL) */
+  int64_t capacity, n_envs;
+  int32_t n_steps, n_agents;      /* n_agents 1 or 2 */
+  int32_t obs_dim[2], action_dim[2], col_offset[2];   /* 1 .. 4096 each width; col_offset[k] + action_dim[k] <= action_row */
+  int32_t action_row, reserved0;  /* reserved0 must be 0 */
+} QrReplayAdd;
+/* In this order: QR_E_NULL for a NULL struct; QR_E_SIZE for n_agents outside 1..2, reserved0 != 0, capacity < 1, n_steps < 1, n_envs < 1,
+ * n_steps * n_envs > capacity, count outside [0, capacity) where state is NULL, a width outside 1..4096, a column range outside the
+ * action row; QR_E_NULL for a NULL obs, action, reward, done or buffer pointer of an agent in use, or final_obs given for one agent only;
+ * QR_E_ALIGN for a float pointer that is not 4-byte aligned or a state pointer that is not 8-byte aligned.  Nothing is launched or
+ * written on an error.  Members of agent 1 are not read when n_agents is 1. */
+int qr_replay_add(const QrReplayAdd* add, void* stream);
+
+/* `batch` pairwise distinct rows below n, in O(batch) and in integers only: index[j] is the image of j under a keyed pseudo-random
+ * permutation of [0, n), so the same (n, seed, draw) gives the same indices on any device, launch geometry or CPU restatement.
+ *     h    = max(1, ceil(bit_length(n - 1) / 2)),  mask = 2^h - 1
+ *     P(x) : (L, R) = (x >> h, x & mask); six times, r = 0..5: (L, R) <- (R, L xor (F & mask)), F = word 0 of Philox4x32-10 with the
+ *            counter (R, r, draw_lo, draw_hi) under the key (seed_lo, seed_hi); P(x) = L << h | R  — a permutation of [0, 4^h)
+ *     index[j] = the first of P(j), P(P(j)), ... that is below n  (cycle walking: a permutation of [0, n))
+ * The walk starts below n and follows a cycle of P, which has 4^h < 4 n points, so it ends; it is capped at 4^h steps all the same, and a
+ * capped walk stores 0 and sets *status to 1 (status may be NULL; it is never cleared here).  A (seed, draw) pair must not be used
+ * twice: draw counts the calls.  With state, n = state[1] and draw = state[2] are read on the device (the members n and draw are
+ * then only checked), and state[2] is advanced by one behind the launch. */
+typedef struct QrReplaySample {
+  int64_t* index;                 /* [batch], written */
+  int32_t* status;                /* NULL or one device word */
+  int64_t* state;                 /* NULL, or device int64[3] = {count, current_size, draw} */
+  int64_t n, batch;               /* 1 <= batch <= n < 2^31 */
+  uint64_t seed, draw;
+} QrReplaySample;
+/* QR_E_NULL for a NULL struct; QR_E_SIZE for batch < 1, batch > n or n >= 2^31; QR_E_NULL for a NULL index; QR_E_ALIGN for an index or
+ * state pointer that is not 8-byte aligned or a status pointer that is not 4-byte aligned.  Nothing is launched or written on an error. */
+int qr_replay_sample(const QrReplaySample* sample, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

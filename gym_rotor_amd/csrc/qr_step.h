@@ -425,14 +425,28 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   uint32_t rcount_s = 0;  // the tile's position in the in-launch reset stream
   // (Measured and NOT adopted, profiles/r03/ab_load_order_store_policy.txt: requesting parameters and action row first, x and v
   // last, and rebuilding the quaternion behind the action map — 4.47 against 4.46 us per launch at 65 536 envs.)
-  load_state<XV, QW>(a, first, ll, w);
+  // (kHeadOrder) The one-step helper-wave launches: one stepping wave per SIMD, nothing overlaps its instruction stream, and a
+  // wave's loads land in issue order over several hundred nanoseconds (load_state_raw).  There the queue is ordered by FIRST USE —
+  // packed attitude, parameters, action row, rates, x and v (wanted only by the step's final update) — and the head of the step
+  // is pinned in the same order (sched_barrier below): the attitude unpack, the per-launch step size, the action-map constants and
+  // the action map each run behind a partial vmcnt wait while the words behind them are still in flight, instead of behind the
+  // wait for the whole working set.  The arithmetic is the same instructions on the same operands: no result bit moves.
+  // 65 536 envs, Quad-v0: 4.12 -> 3.82 us per launch; the queue's order alone 3.88, the pins alone 4.06 (profiles/r25/ab_head.txt).
+  // Not the instantiations of the larger grids, where SIMDs hold a second stepping wave and a wave's wait is another wave's time
+  // (HREW = false; MAG, the launches with two or more substeps: 131 072 envs x 10 substeps 6.66 -> 6.80 us with it).
+  constexpr bool kHeadOrder = HELP && SINGLE && !POLICY && !TRAJ && HREW && !MAG;
+  QuatPack<T> qin;
+  if constexpr (kHeadOrder) { load_att_packed<QW>(a, ufirst, ll, qin); __builtin_amdgcn_sched_barrier(0); }
+  else load_state<XV, QW>(a, first, ll, w);
   w.nominal = a.params == nullptr;
   {  // (without a params buffer: a descriptor without records, the loads return 0 — no branch between the load batches)
     const SoA<float> prm(a.params, 6, L);
 #pragma unroll
     for (int f = 0; f < 6; ++f) w.prm[f] = prm.load(f, ufirst, ll);
   }
+  if constexpr (kHeadOrder) __builtin_amdgcn_sched_barrier(0);  // (the queue's order is the point: no clustering across the groups)
   if constexpr (!POLICY) load_action_row(a.action + first * A, ll, act_next);
+  if constexpr (kHeadOrder) { __builtin_amdgcn_sched_barrier(0); load_rate_pos_vel<XV, QW>(a, ufirst, ll, w); }
   // The tile's position in the in-launch reset stream: a scalar load.  (Measured alternatives, bench.py at 65 536 envs:
   // a vector load at the end of the wave's load queue 5.71 us, at its front 5.70 us, a load deferred until the working set
   // has been consumed 6.12 us — against 5.42 us, although scalar loads return out of order and the first use of a kernarg
@@ -536,6 +550,25 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
   ActConsts<T> ac;
   if constexpr (kHoistAct) act_consts(w, c, ac);
 
+  //@sec head-unpack
+  // (kHeadOrder) the substep size is the same number in every lane and needs only scalars: its reciprocal chain (v_rcp_f64 and two
+  // Newton steps, all dependent) is formed HERE, in the load wait; then the attitude, behind the wait for its three words alone
+  T hstep = T(0);
+  if constexpr (kHeadOrder) {
+    if constexpr (!ADAPT) {
+      hstep = T(c.dt) * recip(T(ka.substeps));
+      asm volatile("" : "+v"(hstep));
+    }
+    unpack_quat(qin, w.q);
+    {
+      // (ordinary arithmetic floats across a sched_barrier before instruction selection: the values themselves are pinned — the
+      // quaternion is complete at this statement, and the parameter words are first looked at behind it)
+      asm volatile("" : "+v"(w.q[0]), "+v"(w.q[1]), "+v"(w.q[2]), "+v"(w.q[3]));
+      asm volatile("" : "+v"(w.prm[0]), "+v"(w.prm[1]), "+v"(w.prm[2]), "+v"(w.prm[3]), "+v"(w.prm[4]), "+v"(w.prm[5]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
   for (int t = 0; t < n_steps; ++t) {  //@sec action-source
     float act[A];
     if constexpr (POLICY) {
@@ -620,7 +653,9 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
     // ---- action_wrapper ----  //@sec action-map
     Dyn<T> dyn;
     if constexpr (!kHoistAct) act_consts(w, c, ac);
+    if constexpr (kHeadOrder) __builtin_amdgcn_sched_barrier(0);  // (the constants need the parameter words only, the map the action row: see kHeadOrder)
     action_map<KIND, T, X>(act, w, ac, c, dyn);
+    if constexpr (kHeadOrder) __builtin_amdgcn_sched_barrier(0);
     if constexpr (SINGLE && !HELP) {  // (plain one-step launch: the loaded parameters are dead from here on — a re-sampled
 #pragma unroll                        //  env stores the ones it takes from the pool — so their registers need not survive)
       for (int f = 0; f < 6; ++f) w.prm[f] = 0.0f;
@@ -673,7 +708,7 @@ void step_kernel(void* pos_vel, void* att_rate, const float* action, float* para
       if constexpr (HELP && SINGLE) {
         if (nsub >= kPrioSubsteps) __builtin_amdgcn_s_setprio(kStepPrio);
       }
-      integrate_sel<MAG>(w.x, w.v, w.q, w.W, dyn, nsub, T(c.dt) * recip(T(nsub)));
+      integrate_sel<MAG>(w.x, w.v, w.q, w.W, dyn, nsub, kHeadOrder ? hstep : T(c.dt) * recip(T(nsub)));
     }
     renorm_quat(w.q);  //@sec renorm-late-loads-pack
     if constexpr (kLateLoads) {

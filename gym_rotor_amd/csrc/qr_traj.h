@@ -364,6 +364,26 @@ __device__ __forceinline__ void load_state(const Args& a, int64_t first64, unsig
   unpack_quat(p, w.q);
 }
 
+// The same loads in two halves, for the one-step helper-wave launches (qr_step.h: kHeadOrder), whose lone stepping wave starts on
+// the attitude words while the rest of its working set is still landing: the packed attitude at the head of the load queue, the
+// rates, x and v at its end.
+template <typename QW>
+__device__ __forceinline__ void load_att_packed(const Args& a, unsigned first, unsigned lane, QuatPack<QW>& p) {
+  const SoA<QW> ar(a.att_rate, 6, a.ld);
+#pragma unroll
+  for (int f = 0; f < 3; ++f) p.k[f] = ar.load(f, first, lane);
+}
+
+template <typename XV, typename QW>
+__device__ __forceinline__ void load_rate_pos_vel(const Args& a, unsigned first, unsigned lane, Work<QW, XV>& w) {
+  const SoA<XV> pv(a.pos_vel, 6, a.ld);
+  const SoA<QW> ar(a.att_rate, 6, a.ld);
+#pragma unroll
+  for (int f = 0; f < 3; ++f) w.W[f] = ar.load(3 + f, first, lane);
+#pragma unroll
+  for (int f = 0; f < 3; ++f) { w.x[f] = pv.load(f, first, lane); w.v[f] = pv.load(3 + f, first, lane); }
+}
+
 // (the packed attitude is passed in: the step kernel forms it once per env-step, see QuatPack)
 template <typename XV, typename QW, int AUX = 0>
 __device__ __forceinline__ void store_state(const Args& a, int64_t first64, unsigned lane, const Work<QW, XV>& w, const QuatPack<QW>& p) {

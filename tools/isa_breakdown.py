@@ -6,6 +6,7 @@ llvm-symbolizer for the inline stack of every instruction address.  Each instruc
   * the SECTION of step_kernel it was inlined into: the `//@sec <name>` marker comment nearest above the step_kernel line of its
     outermost frame (qr_step.h), and
   * the function called directly from step_kernel at that point (integrate, action_map, quad_done, store_state, ...).
+Column dep1 = VALU instructions that read a register the VALU instruction just before them writes (what a lone wave pays most for).
 Static counts; the per-env-step loop of a multi-step instantiation and the substep loop are marked by their sections.
 
     python tools/isa_breakdown.py [--kind 0|1|2] [--flags TRAJ,ADAPT,POLICY,SINGLE,HELP] [--by-callee] [--elf /tmp/x.elf]
@@ -59,12 +60,12 @@ dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", f"--st
                      capture_output=True, text=True, check=True).stdout
 insts = []   # (addr, mnemonic)
 for l in dis.splitlines():
-    m = re.match(r"\s+(\S+)\s.*//\s*([0-9A-Fa-f]+):", l)
+    m = re.match(r"\s+(\S+)(\s.*)//\s*([0-9A-Fa-f]+):", l)
     if m:
-        insts.append((int(m.group(2), 16), m.group(1)))
+        insts.append((int(m.group(3), 16), m.group(1), m.group(2).strip()))
 if not insts:
     sys.exit("no instructions disassembled")
-sy = subprocess.run([f"{LLVM}/llvm-symbolizer", "--inlines", f"--obj={elf}", "--output-style=LLVM"], input="\n".join(hex(x) for x, _ in insts) + "\n",
+sy = subprocess.run([f"{LLVM}/llvm-symbolizer", "--inlines", f"--obj={elf}", "--output-style=LLVM"], input="\n".join(hex(x[0]) for x in insts) + "\n",
                     capture_output=True, text=True, check=True).stdout
 blocks = [b for b in sy.split("\n\n") if b.strip()]
 assert len(blocks) == len(insts), (len(blocks), len(insts))
@@ -89,8 +90,18 @@ def kind_of(op):
     return "vmem"
 
 
+def vregs(tok):
+    r = set()
+    for m in re.finditer(r"\bv\[(\d+):(\d+)\]", tok):
+        r.update(range(int(m.group(1)), int(m.group(2)) + 1))
+    for m in re.finditer(r"\bv(\d+)\b", tok):
+        r.add(int(m.group(1)))
+    return r
+
+
 tab = collections.OrderedDict()
-for (addr, op), b in zip(insts, blocks):
+prev_dst = set()   # VGPRs written by the previous VALU instruction (dep1: this one reads them, tools/isa_dep_distance.py's distance 1)
+for (addr, op, ops), b in zip(insts, blocks):
     lines = b.strip().splitlines()
     frames = [(lines[k], lines[k + 1]) for k in range(0, len(lines) - 1, 2)]   # innermost first: (function, file:line:col)
     sec, callee = "?", "(step_kernel)"
@@ -106,12 +117,19 @@ for (addr, op), b in zip(insts, blocks):
     key = (sec, callee) if a.by_callee else (sec,)
     row = tab.setdefault(key, collections.Counter())
     row[kind_of(op)] += 1
+    if kind_of(op) == "valu":
+        parts = [x.strip() for x in ops.split(",")]
+        dst = vregs(parts[0]) if parts else set()
+        srcs = set().union(*[vregs(x) for x in parts[1:]]) if len(parts) > 1 else set()
+        if op.startswith(("v_fmac", "v_mac")): srcs |= dst
+        if srcs & prev_dst: row["dep1"] += 1
+        prev_dst = dst
     if op.startswith("v_") and "_f64" in op: row["f64"] += 1
     if re.match(r"v_(rcp|rsq|sqrt|exp|log|sin|cos)_", op): row["trans"] += 1
     if op.startswith("v_readlane") or op.startswith("v_writelane"): row["lane_spill"] += 1
 
 print(f"{name}: {len(insts)} instructions")
-cols = ["valu", "f64", "trans", "lane_spill", "mfma", "salu", "smem", "lds", "vmem", "wait"]
+cols = ["valu", "f64", "dep1", "trans", "lane_spill", "mfma", "salu", "smem", "lds", "vmem", "wait"]
 print("%-44s" % "section" + "".join("%8s" % c for c in cols) + "%8s" % "all")
 tot = collections.Counter()
 for key, row in tab.items():

@@ -33,7 +33,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_default_coeffs", "qr_abi_version", "qr_step_kernel_info", "qr_launch_thresholds",
            "qr_launch_plan", "qr_launch_stats", "qr_instance_table", "qr_touch", "qr_evaluate_actor", "qr_evaluate_population",
            "qr_critic_values", "qr_critic_next_values", "qr_ppo_actor_grad", "qr_ppo_actor_workspace_bytes",
-           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step",
+           "qr_ppo_critic_grad", "qr_ppo_critic_workspace_bytes", "qr_adamw_step", "qr_adamw_polyak_step",
            "qr_twinq_target", "qr_twinq_grad", "qr_twinq_workspace_bytes",
            "qr_dpg_actor_grad", "qr_dpg_actor_workspace_bytes", "qr_soft_update", "qr_sac_target",
            "qr_sac_actor_grad", "qr_sac_actor_workspace_bytes",
@@ -384,6 +384,34 @@ def adamw_group(g: QrAdamWGroup, params, grads, exp_avg, exp_avg_sq, step, stats
     return g
 
 
+POLYAK_MAX_GROUPS, POLYAK_MAX_TENSORS = 7, 16   # qr_adamw_polyak_step: groups per launch, tensors per group (entries: ADAMW_MAX_ENTRIES)
+
+
+class QrAdamWPolyakGroup(C.Structure):
+    _fields_ = [("param", C.c_void_p * 16), ("grad", C.c_void_p * 16), ("target", C.c_void_p * 16), ("count", C.c_int32 * 16),
+                ("n_tensors", C.c_int32), ("reserved0", C.c_int32),
+                ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_void_p), ("stats", C.c_void_p), ("exp_out", C.c_void_p),
+                ("lr", C.c_double), ("eta_min", C.c_double), ("t0", C.c_int64),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("max_norm", C.c_float),
+                ("tau", C.c_double)]
+
+
+def adamw_polyak_group(g: QrAdamWPolyakGroup, params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, *, tau, lr, eta_min, t0, betas,
+                       eps, weight_decay, max_norm):
+    """Fill the QrAdamWPolyakGroup `g` of one step: as adamw_group with 1..16 tensors, plus per parameter its target tensor or None
+    (targets = None: none at all), the exp output (or None) and tau.  Returns g."""
+    g.n_tensors, g.reserved0 = len(params), 0
+    for k, (p, d) in enumerate(zip(params, grads)):
+        g.param[k], g.grad[k], g.count[k] = p.data_ptr(), d.data_ptr(), p.numel()
+        g.target[k] = None if targets is None else ptr(targets[k])
+    for k in range(len(params), 16):
+        g.param[k], g.grad[k], g.target[k], g.count[k] = None, None, None, 0
+    g.exp_avg, g.exp_avg_sq, g.step, g.stats, g.exp_out = exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(), ptr(stats), ptr(exp_out)
+    g.lr, g.eta_min, g.t0, g.tau = float(lr), float(eta_min), int(t0), float(tau)
+    g.beta1, g.beta2, g.eps, g.weight_decay, g.max_norm = float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(max_norm)
+    return g
+
+
 def step_out(out, truncated: bool) -> QrStepOut:
     """QrStepOut over a mapping of output tensors keyed by the member names, `terminated` for the member `done`; a missing or
     None entry is a null pointer.  truncated=False: the env has no step counter, the `truncated` member stays null."""
@@ -486,6 +514,8 @@ def load():
     lib.qr_ppo_critic_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_adamw_step.restype = C.c_int
     lib.qr_adamw_step.argtypes = [P(QrAdamWGroup), C.c_int32, C.c_void_p]
+    lib.qr_adamw_polyak_step.restype = C.c_int
+    lib.qr_adamw_polyak_step.argtypes = [P(QrAdamWPolyakGroup), C.c_int32, C.c_void_p]
     lib.qr_twinq_target.restype = C.c_int
     lib.qr_twinq_target.argtypes = [P(QrActor), P(QrQCritic), P(QrTransitions), P(QrTd3Target), C.c_void_p]
     lib.qr_twinq_grad.restype = C.c_int

@@ -506,4 +506,51 @@ static int do_adamw(const QrAdamWGroup* groups, int32_t n_groups, void* stream) 
   return (int)hipGetLastError();
 }
 
+// qr_adamw_polyak_step: do_adamw's checks in its order, with do_soft_update's for the targets, then ONE launch of n_groups workgroups.
+// Nothing is launched on an error.
+static int do_adamw_polyak(const QrAdamWPolyakGroup* groups, int32_t n_groups, void* stream) {
+  if (!groups) return QR_E_NULL;
+  if (n_groups < 1 || n_groups > kPolyakGroups) return QR_E_SIZE;
+  AdamWPolyakArgs a{};
+  for (int i = 0; i < n_groups; ++i) {
+    const QrAdamWPolyakGroup& g = groups[i];
+    AdamWPolyakGroupArgs& d = a.g[i];
+    if (g.n_tensors < 1 || g.n_tensors > kPolyakTensors || g.reserved0 != 0) return QR_E_SIZE;
+    int64_t total = 0;
+    for (int k = 0; k < g.n_tensors; ++k) {
+      if (g.count[k] < 1) return QR_E_SIZE;
+      total += g.count[k];
+    }
+    if (total > kAdamWMaxEntries) return QR_E_SIZE;
+    const double nonneg[] = {g.lr, g.eta_min, (double)g.eps, (double)g.weight_decay};
+    for (double v : nonneg)
+      if (!(v >= 0.0) || !(v <= 1.79769313486231570e308)) return QR_E_SIZE;
+    if (!(g.beta1 >= 0.0f && g.beta1 < 1.0f) || !(g.beta2 >= 0.0f && g.beta2 < 1.0f) || g.t0 < 0 || g.max_norm != g.max_norm) return QR_E_SIZE;
+    if (!(g.tau >= 0.0 && g.tau <= 1.0) || (g.exp_out && total != 1)) return QR_E_SIZE;
+    if (!g.exp_avg || !g.exp_avg_sq || !g.step) return QR_E_NULL;
+    for (int k = 0; k < g.n_tensors; ++k)
+      if (!g.param[k] || !g.grad[k]) return QR_E_NULL;
+    for (int k = 0; k < g.n_tensors; ++k)
+      if (g.target[k] == g.param[k]) return QR_E_SIZE;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(g.exp_avg) | reinterpret_cast<uintptr_t>(g.exp_avg_sq) | reinterpret_cast<uintptr_t>(g.stats) |
+                     reinterpret_cast<uintptr_t>(g.exp_out);
+    for (int k = 0; k < g.n_tensors; ++k)
+      bits |= reinterpret_cast<uintptr_t>(g.param[k]) | reinterpret_cast<uintptr_t>(g.grad[k]) | reinterpret_cast<uintptr_t>(g.target[k]);
+    if ((bits & 3u) || (reinterpret_cast<uintptr_t>(g.step) & 7u)) return QR_E_ALIGN;
+    for (int k = 0; k < kPolyakTensors; ++k) {
+      const bool used = k < g.n_tensors;
+      d.param[k] = used ? g.param[k] : nullptr;
+      d.grad[k] = used ? g.grad[k] : nullptr;
+      d.target[k] = used ? g.target[k] : nullptr;
+      d.off[k + 1] = d.off[k] + (used ? g.count[k] : 0);
+    }
+    d.exp_avg = g.exp_avg; d.exp_avg_sq = g.exp_avg_sq; d.step = g.step; d.stats = g.stats; d.exp_out = g.exp_out;
+    d.lr = g.lr; d.eta_min = g.eta_min; d.t0 = g.t0;
+    d.beta1 = g.beta1; d.beta2 = g.beta2; d.eps = g.eps; d.weight_decay = g.weight_decay; d.max_norm = g.max_norm;
+    d.tau = (float)g.tau; d.omt = (float)(1.0 - g.tau);
+  }
+  hipLaunchKernelGGL(adamw_polyak_kernel, dim3((unsigned)n_groups), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace qr

@@ -46,7 +46,8 @@
 //   qr_ppo.h       the PPO actor loss and its gradients for one minibatch (qr_ppo_actor_grad): ppo_actor_kernel, ppo_reduce_kernel
 //   qr_mlp_grad.h  what the MLP-critic update kernels share (included by the next and by qr_td3.h): mlp_grad_walk, the gradient kernels' shared tile walk; the half-tile gradient body, the partial vector, the reduction's sums
 //   qr_ppo_critic.h  the PPO critic loss and its gradients for one minibatch (qr_ppo_critic_grad): ppo_critic_kernel, ppo_critic_reduce_kernel
-//   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel
+//   qr_optim.h     gradient-norm clipping, AdamW and the cosine schedule for up to eight parameter groups (qr_adamw_step): adamw_step_kernel;
+//                  the same step for up to sixteen tensors with the soft target update and SAC's exp(log_alpha) fused (qr_adamw_polyak_step): adamw_polyak_kernel
 //   qr_td3.h       the TD3 critic half for one minibatch (qr_twinq_target, qr_twinq_grad): td3_target_kernel, twinq_kernel, twinq_reduce_kernel; target_walk, the target kernels' shared tile walk;
 //                  the centralized (CTDE) critic of two agents (qr_ctde_twinq_target, qr_ctde_sac_target, qr_ctde_twinq_grad): the walks' two-agent forms, ctde_twinq_kernel
 //   qr_td3_actor.h the TD3 actor half for one minibatch and the soft target update (qr_dpg_actor_grad, qr_soft_update): dpg_actor_kernel, dpg_reduce_kernel, soft_update_kernel;
@@ -834,6 +835,10 @@ int64_t qr_twinq_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_t bat
 }
 
 int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream) { return qr::do_adamw(groups, n_groups, stream); }
+
+int qr_adamw_polyak_step(const QrAdamWPolyakGroup* groups, int32_t n_groups, void* stream) {
+  return qr::do_adamw_polyak(groups, n_groups, stream);
+}
 
 int qr_ppo_critic_grad(const QrCritic* critic, const QrCriticBatch* batch, const QrCriticGrad* grad, void* stream) {
   return qr::do_ppo_critic(critic, batch, grad, stream);

@@ -1,6 +1,8 @@
 """The optimiser half of a PPO update on the device: `DeviceAdamW` — gradient-norm clipping, AdamW and the cosine schedule with warm
 restarts in one launch (`qr_adamw_step`), with the step count and the schedule in device memory — and `PpoUpdater`, the K-epoch,
 shuffle and minibatch loop of the reference's `PPO.train` (algos/ppo/ppo.py:148-214) over `actor_loss`, `critic_loss` and those steps.
+`PolyakAdamW` (`qr_adamw_polyak_step`) is the same step for up to sixteen tensors with the soft target update and SAC's
+exp(log_alpha) in the same launch: the optimiser of `offpolicy.Td3Updater` / `offpolicy.SacUpdater`.
 """
 from __future__ import annotations
 
@@ -163,6 +165,159 @@ def adamw_step(params, grads, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, s
     with torch.cuda.device(dev):
         rc = _lib.load().qr_adamw_step(C.byref(g), 1, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "qr_adamw_step")
+
+
+class PolyakAdamW(DeviceAdamW):
+    """`DeviceAdamW` for 1..16 tensors with what TD3.train / SAC.train do right after the optimiser step in the same launch
+    (`qr_adamw_polyak_step`): the soft update of the parameters' target tensors (td3.py:207-211, sac.py:219-221) and, for SAC's
+    one-entry `log_alpha`, alpha = exp(log_alpha) (sac.py:213).  Sixteen tensors hold the reference's twin critic as ONE group: one
+    clip over all twelve tensors and one step counter, as `torch.optim.AdamW(critic.parameters())` has them (td3.py:166-171).
+
+    targets: None, or one tensor (contiguous float32, the parameter's size and device, not the parameter itself) or None per
+    parameter; `step(polyak=True)` leaves target = tau * param + (1 - tau) * target, the bits of `soft_update` run after the step, and
+    `step(polyak=False)` leaves the targets alone (the iterations between TD3's delayed updates).  exp_out: a float32 tensor of one
+    entry that every step leaves at exp(the new parameter); only for one parameter of one entry.  State, hyperparameters,
+    `state_dict` / `load_state_dict` and the deviations from torch are `DeviceAdamW`'s; a group of at most 8 tensors without targets
+    and exp_out gets `DeviceAdamW`'s bits."""
+
+    def __init__(self, params, *, targets=None, tau: float = 0.005, exp_out: Optional[torch.Tensor] = None, lr: float, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 1e-2, max_norm: float = -1.0, t0: int = 0, eta_min: float = 0.0):
+        self.params = list(params)
+        if not 1 <= len(self.params) <= _lib.POLYAK_MAX_TENSORS:
+            raise ValueError(f"PolyakAdamW takes 1..{_lib.POLYAK_MAX_TENSORS} parameter tensors, got {len(self.params)}")
+        self.device = self.params[0].device if isinstance(self.params[0], torch.Tensor) else None
+        for k, p in enumerate(self.params):
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or not p.is_contiguous() or p.numel() < 1:
+                raise ValueError(f"PolyakAdamW: parameter {k} must be a contiguous float32 tensor with at least one entry")
+            if p.device != self.device:
+                raise ValueError(f"PolyakAdamW: parameter {k} is on {p.device}, parameter 0 on {self.device}")
+        self.numel = sum(p.numel() for p in self.params)
+        if self.numel > _lib.ADAMW_MAX_ENTRIES:
+            raise ValueError(f"PolyakAdamW: {self.numel} entries, at most {_lib.ADAMW_MAX_ENTRIES} per optimiser")
+        self.targets = None
+        if targets is not None:
+            self.targets = list(targets)
+            if len(self.targets) != len(self.params):
+                raise ValueError(f"PolyakAdamW: targets holds {len(self.targets)} entries for {len(self.params)} parameters (None where there is none)")
+            for k, (p, t) in enumerate(zip(self.params, self.targets)):
+                if t is None:
+                    continue
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel()
+                        or t.device != self.device):
+                    raise ValueError(f"PolyakAdamW: target {k} must be a contiguous float32 tensor of {p.numel()} entries on {self.device}")
+                if t.data_ptr() == p.data_ptr():
+                    raise ValueError(f"PolyakAdamW: target {k} is its own parameter")
+        self.tau = float(tau)
+        if not 0.0 <= self.tau <= 1.0:
+            raise ValueError(f"PolyakAdamW: tau must lie in [0, 1], got {tau}")
+        if exp_out is not None:
+            if self.numel != 1:
+                raise ValueError(f"PolyakAdamW: exp_out needs a group of one entry, this one has {self.numel}")
+            if (not isinstance(exp_out, torch.Tensor) or exp_out.dtype != torch.float32 or exp_out.numel() != 1 or exp_out.device != self.device
+                    or exp_out.data_ptr() == self.params[0].data_ptr()):
+                raise ValueError(f"PolyakAdamW: exp_out must be a float32 tensor of one entry on {self.device}, not the parameter itself")
+        self.exp_out = exp_out
+        self._set_hyper(dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm, t0=t0, eta_min=eta_min))
+        self.exp_avg = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        self.exp_avg_sq = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.stats = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._group = _lib.QrAdamWPolyakGroup()
+
+    def _set_hyper(self, h):
+        try:
+            super()._set_hyper(h)
+        except ValueError as e:
+            raise ValueError(str(e).replace("DeviceAdamW", "PolyakAdamW")) from None
+
+    def _fill(self, polyak: bool = True) -> _lib.QrAdamWPolyakGroup:
+        """The launch struct of the next step, from the parameters' current .grad tensors."""
+        grads = []
+        for k, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                raise ValueError(f"PolyakAdamW.step: parameter {k} has no .grad")
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device or g.numel() != p.numel():
+                raise ValueError(f"PolyakAdamW.step: the .grad of parameter {k} must be a contiguous float32 tensor of {p.numel()} entries on "
+                                 f"{self.device}")
+            grads.append(g)
+        return _lib.adamw_polyak_group(self._group, self.params, grads, self.targets if polyak else None, self.exp_avg, self.exp_avg_sq,
+                                       self.step_count, self.stats, self.exp_out, tau=self.tau, **self.hyper())
+
+    def step(self, polyak: bool = True) -> None:
+        """One optimiser step (clip, AdamW, schedule), the targets' soft update when `polyak`, and exp_out — one launch."""
+        PolyakAdamW.step_all([(self, polyak)])
+
+    @staticmethod
+    def step_all(opts) -> None:
+        """One step of each of several optimisers on one device in ONE launch (one workgroup each; more than 7: one launch per 7).
+        opts: (optimiser, polyak) pairs, or optimisers (polyak = True).  The result is that of stepping them one by one."""
+        pairs = [o if isinstance(o, tuple) else (o, True) for o in opts]
+        if not pairs:
+            return
+        for o, _ in pairs:
+            if not isinstance(o, PolyakAdamW):
+                raise ValueError("PolyakAdamW.step_all takes PolyakAdamW optimisers (DeviceAdamW.step_all steps the others)")
+        dev = pairs[0][0].device
+        if any(o.device != dev for o, _ in pairs):
+            raise ValueError("PolyakAdamW.step_all: the optimisers must be on one device")
+        if len({id(o) for o, _ in pairs}) != len(pairs):
+            raise ValueError("PolyakAdamW.step_all: an optimiser appears twice")
+        groups = [o._fill(bool(polyak)) for o, polyak in pairs]
+        if dev.type != "cuda":
+            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for i in range(0, len(groups), _lib.POLYAK_MAX_GROUPS):
+                chunk = groups[i:i + _lib.POLYAK_MAX_GROUPS]
+                _lib.check(lib.qr_adamw_polyak_step((_lib.QrAdamWPolyakGroup * len(chunk))(*chunk), len(chunk), stream), "qr_adamw_polyak_step")
+
+
+def adamw_polyak_step(params, grads, targets, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor, stats: Optional[torch.Tensor],
+                      exp_out: Optional[torch.Tensor] = None, *, tau: float = 0.005, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                      weight_decay: float = 1e-2, max_norm: float = -1.0, t0: int = 0, eta_min: float = 0.0) -> None:
+    """One `qr_adamw_polyak_step` launch for ONE group on explicit tensors (what `PolyakAdamW.step` does with its own state and the
+    parameters' .grad): params / grads 1..16 contiguous float32 tensors each, targets None or one tensor or None per parameter,
+    exp_avg / exp_avg_sq / step / stats as `adamw_step` takes them, exp_out float32 [1] or None (a group of one entry only) — all on
+    one device."""
+    params, grads = list(params), list(grads)
+    if not 1 <= len(params) <= _lib.POLYAK_MAX_TENSORS or len(grads) != len(params):
+        raise ValueError(f"adamw_polyak_step takes 1..{_lib.POLYAK_MAX_TENSORS} parameter tensors and as many gradients")
+    dev = params[0].device
+    for k, (p, g) in enumerate(zip(params, grads)):
+        for what, t in (("parameter", p), ("gradient", g)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel() or t.numel() < 1:
+                raise ValueError(f"adamw_polyak_step: {what} {k} must be a contiguous float32 tensor of {p.numel()} >= 1 entries on {dev}")
+    if targets is not None:
+        targets = list(targets)
+        if len(targets) != len(params):
+            raise ValueError("adamw_polyak_step: targets holds one entry per parameter (None where there is none)")
+        for k, (p, t) in enumerate(zip(params, targets)):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel()
+                                  or t.data_ptr() == p.data_ptr()):
+                raise ValueError(f"adamw_polyak_step: target {k} must be a contiguous float32 tensor of {p.numel()} entries on {dev}, not the "
+                                 f"parameter itself")
+    if not 0.0 <= float(tau) <= 1.0:
+        raise ValueError(f"adamw_polyak_step: tau must lie in [0, 1], got {tau}")
+    total = sum(p.numel() for p in params)
+    for what, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != total:
+            raise ValueError(f"adamw_polyak_step: {what} must be a contiguous float32 tensor of {total} entries on {dev}")
+    if step.dtype != torch.int64 or step.numel() != 1 or step.device != dev:
+        raise ValueError(f"adamw_polyak_step: step must be an int64 tensor of one entry on {dev}")
+    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 4 or not stats.is_contiguous() or stats.device != dev):
+        raise ValueError(f"adamw_polyak_step: stats must be a contiguous float32 [4] tensor on {dev}")
+    if exp_out is not None and (total != 1 or exp_out.dtype != torch.float32 or exp_out.numel() != 1 or exp_out.device != dev
+                                or exp_out.data_ptr() == params[0].data_ptr()):
+        raise ValueError(f"adamw_polyak_step: exp_out must be a float32 tensor of one entry on {dev}, for a group of one entry")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    g = _lib.adamw_polyak_group(_lib.QrAdamWPolyakGroup(), params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, tau=tau, lr=lr,
+                                eta_min=eta_min, t0=t0, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_adamw_polyak_step(C.byref(g), 1, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_adamw_polyak_step")
 
 
 def minibatch_slices(n_rows: int, batch_size: int):

@@ -82,8 +82,8 @@ def sac_critic_loss(critic_module, critic_target_module, actor_module, buffer: R
     `critic_module.fc{1..6}.{weight,bias}.grad` in place, as `loss.backward()` after `zero_grad()` leaves them.  noise: the [B, A]
     standard-normal draws of the sample (rsample in the reference), None: zeros.  alpha: a float, or the device tensor of automatic
     entropy tuning.  Returns stats (stats[0] = the loss).  From the second call on with an unchanged B nothing is allocated: y, the
-    workspace and stats are cached on the buffer.  The optimiser step follows on these .grad tensors (two `optim.DeviceAdamW` groups
-    of six tensors, or torch's), then `soft_update(critic_module, critic_target_module, tau)`."""
+    workspace and stats are cached on the buffer.  The optimiser step follows on these .grad tensors (one `optim.PolyakAdamW` group
+    of all twelve tensors, which can carry the soft update, or torch's and `soft_update(critic_module, critic_target_module, tau)`)."""
     if not isinstance(buffer, ReplayBuffer):
         raise ValueError("sac_critic_loss: buffer must be a ReplayBuffer")
     A = buffer.action_dims[k]

@@ -7,8 +7,8 @@ modules (`td3_critic_loss`); the actor's loss -mean Q1(s, pi(s)) with its smooth
 Replaces, per minibatch of `TD3.train` (algos/td3/td3.py:111-211): the index clones, the actor-target forward pass, randn_like's two
 clamps, two twin-critic forward passes, min, the Bellman line, two mse_loss and the autograd backward pass; and every
 policy_update_freq-th iteration three actor passes, the Q1 pass, the backward pass through the critic and three times through the
-actor, and eighteen copy_ lines.  The optimiser group of twelve tensors is not here: `optim.DeviceAdamW` takes eight tensors, so a
-twin critic is stepped as two groups of six, which clips Q1 and Q2 separately.
+actor, and eighteen copy_ lines.  The optimiser group of twelve tensors is `optim.PolyakAdamW` (one clip over all twelve, as
+the reference's; `optim.DeviceAdamW` takes eight tensors), and the whole loop is `offpolicy.Td3Updater`.
 
 The critic half also exists for ONE centralized (CTDE) twin critic over the two agents of a Decoupled buffer (td3.py:124-137, 157-158):
 `td3_target_ctde` (qr_ctde_twinq_target), `twinq_grad_ctde` (qr_ctde_twinq_grad) and `td3_critic_loss_ctde` on live modules.  The
@@ -590,7 +590,7 @@ def td3_critic_loss(critic_module, critic_target_module, actor_target_module, bu
     The defaults are the reference's (args_parse.py:44-58).  noise: the [B, A] standard-normal draws of the target policy smoothing
     (torch.randn_like in the reference), None: none.  Returns stats (stats[0] = the loss).  From the second call on with an unchanged
     B nothing is allocated: y, the workspace and stats are cached on the buffer.  The optimiser step follows on these .grad tensors:
-    two `optim.DeviceAdamW` groups of six tensors, or torch's."""
+    one `optim.PolyakAdamW` group of all twelve tensors, or torch's."""
     A = buffer.action_dims[k]
     grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups)
     m = actor_target_module

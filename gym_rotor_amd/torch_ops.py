@@ -357,6 +357,25 @@ def qr_adamw_step(params: List[torch.Tensor], grads: List[torch.Tensor], exp_avg
                max_norm=max_norm, t0=t0, eta_min=eta_min)
 
 
+@torch.library.custom_op(f"{_NS}::qr_adamw_polyak_step", mutates_args=("params", "targets", "exp_avg", "exp_avg_sq", "step", "stats", "exp_out"))
+def qr_adamw_polyak_step(params: List[torch.Tensor], grads: List[torch.Tensor], targets: List[torch.Tensor], target_slots: List[int],
+                         exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor, stats: Optional[torch.Tensor],
+                         exp_out: Optional[torch.Tensor], tau: float, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                         max_norm: float, t0: int, eta_min: float) -> None:
+    """qr_adamw_step for one group of up to 16 tensors with the soft target update and exp_out in the same launch
+    (qr_adamw_polyak_step).  targets[j] is the target of params[target_slots[j]] (both empty: no targets); exp_out float32 [1] or
+    None.  Everything else as optim.adamw_polyak_step."""
+    from .optim import adamw_polyak_step
+    _gpu(exp_avg)
+    if len(targets) != len(target_slots) or len(set(target_slots)) != len(target_slots) or any(not 0 <= k < len(params) for k in target_slots):
+        raise ValueError("target_slots names one distinct parameter per target")
+    per_param: List[Optional[torch.Tensor]] = [None] * len(params)
+    for k, t in zip(target_slots, targets):
+        per_param[k] = t
+    adamw_polyak_step(params, grads, per_param if targets else None, exp_avg, exp_avg_sq, step, stats, exp_out, tau=tau, lr=lr,
+                      betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, max_norm=max_norm, t0=t0, eta_min=eta_min)
+
+
 def _qcritic_params(critic: Sequence[torch.Tensor], action_dim: int):
     from .policy import QCriticParams
     if len(critic) != 12:

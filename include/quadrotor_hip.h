@@ -537,6 +537,35 @@ typedef struct QrAdamWGroup {
  * 8-byte aligned.  Nothing is launched on an error. */
 int qr_adamw_step(const QrAdamWGroup* groups, int32_t n_groups, void* stream);
 
+/* qr_adamw_step for groups of up to 16 tensors, with what TD3.train / SAC.train do right after the optimiser step fused into the same
+ * launch — up to 7 independent groups, one workgroup each (7 descriptors of 552 bytes fit one 4 096-byte kernarg segment, 8 do not).
+ * Sixteen slots hold the reference's twin critic (twelve tensors) as ONE group: one clip_grad_norm_ over all twelve and one step
+ * counter, as torch.optim.AdamW(critic.parameters()) has them (td3.py:166-171, sac.py:165-170).  The step itself is qr_adamw_step's,
+ * arithmetic, order and stats: a group of at most 8 tensors with no target and no exp_out gets the bits of qr_adamw_step.  Then
+ *     target[k][i] = fl(fl(tau32 * param[k][i]) + fl(omt32 * target[k][i]))   for every k with target[k] != NULL, from the NEW param[k]
+ * — qr_soft_update's expression and rounding, so the bits of qr_soft_update(param[k], target[k], tau) run after the step
+ * (td3.py:207-211, sac.py:219-221); target[k] = NULL leaves tensor k without one, all NULL is a plain step — and
+ *     *exp_out = float32(exp(float64(param[0][0])))                           where exp_out != NULL, from the NEW value
+ * for a group of exactly one entry: SAC's alpha = log_alpha.exp() (sac.py:213).  Targets and exp_out are written by the thread that
+ * wrote the parameter entry; groups, and the tensors of a group, must not share memory.  reserved0 must be 0. */
+typedef struct QrAdamWPolyakGroup {
+  float* param[16];  const float* grad[16];  float* target[16];   /* target[k]: NULL or [count[k]] */
+  int32_t count[16];  int32_t n_tensors, reserved0;               /* 1..16 tensors, count >= 1 each; 0 */
+  float* exp_avg;   float* exp_avg_sq;     /* [sum of count] each, the tensors back to back; zero before the first step */
+  int64_t* step;                            /* device: steps taken so far */
+  float* stats;                             /* device [4] or NULL */
+  float* exp_out;                           /* device [1] or NULL; only with one tensor of one entry */
+  double lr, eta_min;  int64_t t0;          /* base rate; schedule (t0 = 0: constant) */
+  float beta1, beta2, eps, weight_decay, max_norm;   /* max_norm < 0: no clipping */
+  double tau;                               /* in [0, 1]; read only where a target is set, checked always */
+} QrAdamWPolyakGroup;
+/* QR_E_NULL for a NULL struct, param, grad, state or step pointer (stats, exp_out and every target optional); QR_E_SIZE for n_groups
+ * outside 1..7, n_tensors outside 1..16, reserved0 != 0, a count < 1, a group of more than 65 536 entries, lr / eta_min / eps /
+ * weight_decay negative or not finite, a beta outside [0, 1), t0 < 0, a NaN max_norm, tau outside [0, 1] or not finite, exp_out on a
+ * group of more than one entry, or a target pointer equal to its param pointer; QR_E_ALIGN for a float pointer that is not 4-byte
+ * aligned or a step pointer that is not 8-byte aligned.  Nothing is launched on an error. */
+int qr_adamw_polyak_step(const QrAdamWPolyakGroup* groups, int32_t n_groups, void* stream);
+
 /* The critic half of one TD3 minibatch update (TD3.train, algos/td3/td3.py:123-167, the non-CTDE branch) for ONE agent, read from a
  * flat transition buffer in place, without autograd.  The reference's twin critic MLP_Critic (algos/td3/td3_mlp.py:36-99), twelve
  * float32 tensors in torch.nn.Linear layout, used in place:

@@ -40,7 +40,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
-           "qr_replay_add", "qr_replay_sample")
+           "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample")
 
 
 class QrCoeffs(C.Structure):
@@ -322,6 +322,10 @@ class QrReplayAdd(C.Structure):
                 ("col_offset", C.c_int32 * 2), ("action_row", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class QrReplayAddRule(C.Structure):
+    _fields_ = [("add", QrReplayAdd), ("x_lim", C.c_double), ("pos_tol", C.c_double), ("rot_tol", C.c_double)]
+
+
 class QrReplaySample(C.Structure):
     _fields_ = [("index", C.c_void_p), ("status", C.c_void_p), ("state", C.c_void_p), ("n", C.c_int64), ("batch", C.c_int64),
                 ("seed", C.c_uint64), ("draw", C.c_uint64)]
@@ -340,6 +344,11 @@ def replay_add_args(buffers, obs, final_obs, action, reward, done, truncated, *,
     r.count, r.capacity, r.n_envs, r.n_steps, r.n_agents = int(count), int(capacity), int(n_envs), int(n_steps), len(buffers)
     r.action_row, r.reserved0 = int(action_row), 0
     return r
+
+
+def replay_add_rule_args(add: QrReplayAdd, *, x_lim, pos_tol, rot_tol) -> QrReplayAddRule:
+    """QrReplayAddRule of one qr_replay_add_rule launch: replay_add_args' struct and the time-limit rule's three numbers."""
+    return QrReplayAddRule(add, float(x_lim), float(pos_tol), float(rot_tol))
 
 
 def replay_sample_args(index, status, state, *, n, batch, seed, draw) -> QrReplaySample:
@@ -552,6 +561,8 @@ def load():
     lib.qr_ctde_sac_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_replay_add.restype = C.c_int
     lib.qr_replay_add.argtypes = [P(QrReplayAdd), C.c_void_p]
+    lib.qr_replay_add_rule.restype = C.c_int
+    lib.qr_replay_add_rule.argtypes = [P(QrReplayAddRule), C.c_void_p]
     lib.qr_replay_sample.restype = C.c_int
     lib.qr_replay_sample.argtypes = [P(QrReplaySample), C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p

@@ -2,6 +2,7 @@
 // The data side of a TD3 / SAC iteration: the replay buffer's append and its minibatch indices.
 //   replay_add_kernel (qr_replay_add)        one horizon of a RolloutStorage into the ring of a flat transition buffer: all agents, all
 //                                            five tensors, one launch, no temporaries
+//   replay_add_rule_kernel (qr_replay_add_rule)  the same append with the reference's time-limit "solved" rule in its done segment
 //   replay_sample_kernel (qr_replay_sample)  B pairwise distinct rows below n in O(B): a keyed Feistel permutation of [0, n), integer only
 //   replay_advance_kernel                    the opt-in device counters (count, current_size, draw), advanced by ONE thread in a launch of
 //                                            its own behind the kernel that read them: no workgroup reads a word that a workgroup of the
@@ -43,54 +44,39 @@ struct ReplayAddArgs {
 // rows are contiguous in the ring except across its wrap) and read 256 consecutive bytes of obs / final_obs; the action, reward and done
 // rows are read with the stride the storage gives them.  Element offsets are 64-bit; the offset inside a tile is 32-bit and is split
 // into (row, column) by a multiply-high.
+//
+// The kernel exists twice, from ONE text (qr_replay_walk.h, included into both bodies): replay_add_kernel, and replay_add_rule_kernel
+// (kRule), whose done segment is written by the reference's time-limit rule (main.py:169-173) instead of the agent's own flag: on a
+// transition whose `truncated` is set, done = the agent's error is within tolerance in the observation the transition stores as
+// obs_next, and its reward is not the crash reward; elsewhere the own flag.  That segment then reads, per transition and still in
+// transition order (a wave writes 256 consecutive bytes of done), the truncated byte and — on a time-limit row — one reward word
+// and 3 (agent 0: ex) or 1 (agent 1: eb1) observation words.  The comparisons are made in double on the float32 words, so
+// tests/replay_rule_ref.py gives the same bits.  Every other segment is the same code.  (An inlined function template over the
+// flag compiles replay_add_kernel to other instructions than it had; the shared text leaves it as it was.)
+struct ReplayRule {
+  double x_lim, pos_tol, rot_tol;
+};
+
+constexpr double kReplayPi = 3.141592653589793;   // the double nearest pi (np.pi)
+
 __global__ __launch_bounds__(256) void replay_add_kernel(const ReplayAddArgs a) {
-  const int k = (int)blockIdx.y >= kReplaySegments;
-  const int seg = (int)blockIdx.y - kReplaySegments * k;
-  const int64_t count = a.state ? a.state[0] : a.count;
-  if (count < 0 || count >= a.capacity) return;   // (device counters that do not describe this buffer: write nothing)
-  const int na = a.n_agents;
-  const bool act = seg == 2, scalar = seg >= 3;
-  const uint32_t w = scalar ? 1u : (uint32_t)(act ? (k ? a.A1 : a.A0) : (k ? a.D1 : a.D0));
-  const uint32_t magic = act ? (k ? a.mA1 : a.mA0) : (k ? a.mD1 : a.mD0);
-  const float* obs = k ? a.obs1 : a.obs0;
-  const float* fin = k ? a.final1 : a.final0;
-  const int64_t next = k ? a.next1 : a.next0;
-  const int col = k ? a.col1 : a.col0;
-  float* dst = seg == 0 ? (k ? a.b_obs1 : a.b_obs0) : seg == 1 ? (k ? a.b_next1 : a.b_next0) : seg == 2 ? (k ? a.b_act1 : a.b_act0)
-             : seg == 3 ? (k ? a.b_rwd1 : a.b_rwd0) : (k ? a.b_done1 : a.b_done0);
-  const int64_t tiles = (a.rows + kReplayTile - 1) / kReplayTile;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t j0 = tile * kReplayTile;
-    const int64_t left = a.rows - j0;
-    const uint32_t elems = (uint32_t)(left < kReplayTile ? left : kReplayTile) * w;
-    for (uint32_t l = threadIdx.x; l < elems; l += 256) {
-      const uint32_t jl = w == 1 ? l : __umulhi(l, magic);
-      const uint32_t c = l - jl * w;
-      const int64_t j = j0 + jl;
-      int64_t row = count + j;
-      row = row >= a.capacity ? row - a.capacity : row;
-      const int64_t e = j0 * (int64_t)w + l;   // = j * w + c
-      float v;
-      if (seg == 0) {
-        v = obs[e];
-      } else if (seg == 1) {
-        bool reset = false;
-        if (fin) {
-          reset = a.done[j * na] != 0;
-          if (na > 1) reset = reset | (a.done[j * na + 1] != 0);
-          if (a.truncated) reset = reset | (a.truncated[j] != 0);
-        }
-        v = reset ? fin[e] : obs[next + e];
-      } else if (seg == 2) {
-        v = a.action[j * a.action_row + col + c];
-      } else if (seg == 3) {
-        v = a.reward[j * na + k];
-      } else {
-        v = a.done[j * na + k] != 0 ? 1.0f : 0.0f;
-      }
-      dst[row * (int64_t)w + c] = v;
-    }
-  }
+  constexpr bool kRule = false;
+  const ReplayRule rule{};
+#include "qr_replay_walk.h"
+}
+
+// The same launch with the time-limit rule in its done segment (qr_replay_add_rule).  `truncated` and `reward` are not null here,
+// and agent 0's observation has at least three words.
+struct ReplayAddRuleArgs {
+  ReplayAddArgs add;
+  ReplayRule rule;
+};
+
+__global__ __launch_bounds__(256) void replay_add_rule_kernel(const ReplayAddRuleArgs ra) {
+  constexpr bool kRule = true;
+  const ReplayAddArgs& a = ra.add;
+  const ReplayRule& rule = ra.rule;
+#include "qr_replay_walk.h"
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -55,7 +55,8 @@
 //   qr_sac.h       SAC's soft target values for one minibatch (qr_sac_target): sac_sample, SacRule, sac_target_kernel
 //   qr_sac_actor.h SAC's actor half for one minibatch (qr_sac_actor_grad): SacNet, SacRow, sac_actor_kernel, sac_actor_reduce_kernel;
 //                  agent k's actor half under the centralized (CTDE) twin critic (qr_ctde_sac_actor_grad): ctde_sac_actor_kernel
-//   qr_replay.h    the replay buffer's append and its minibatch indices (qr_replay_add, qr_replay_sample): replay_add_kernel, replay_sample_kernel,
+//   qr_replay.h    the replay buffer's append and its minibatch indices (qr_replay_add, qr_replay_add_rule, qr_replay_sample):
+//                  replay_add_kernel, replay_add_rule_kernel (the time-limit "solved" rule), replay_sample_kernel,
 //                  replay_advance_kernel (the opt-in device counters)
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
@@ -691,7 +692,8 @@ static int do_soft_update(const QrSoftUpdate* u, void* stream) {
 // ceil(2^32 / w) for w >= 2: what replay_add_kernel splits a tile offset into (row, column) with
 static uint32_t replay_magic(int32_t w) { return w >= 2 ? 0xFFFFFFFFu / (uint32_t)w + 1u : 0u; }
 
-static int do_replay_add(const QrReplayAdd* r, void* stream) {
+// qr_replay_add (rule null) and qr_replay_add_rule: one set of checks, one argument block, two kernels
+static int do_replay_add(const QrReplayAdd* r, const QrReplayAddRule* rule, void* stream) {
   if (!r) return QR_E_NULL;
   if (r->n_agents < 1 || r->n_agents > 2 || r->reserved0 != 0 || r->capacity < 1 || r->n_steps < 1 || r->n_envs < 1) return QR_E_SIZE;
   if (r->n_envs > r->capacity || (int64_t)r->n_steps * r->n_envs > r->capacity) return QR_E_SIZE;
@@ -701,7 +703,12 @@ static int do_replay_add(const QrReplayAdd* r, void* stream) {
     if (r->obs_dim[k] < 1 || r->obs_dim[k] > kReplayMaxWidth || r->action_dim[k] < 1 || r->action_dim[k] > kReplayMaxWidth) return QR_E_SIZE;
     if (r->col_offset[k] < 0 || (int64_t)r->col_offset[k] + r->action_dim[k] > r->action_row) return QR_E_SIZE;
   }
-  if (!r->action || !r->reward || !r->done) return QR_E_NULL;
+  if (rule) {
+    const auto finite_from = [](double v, bool zero) { return (zero ? v >= 0.0 : v > 0.0) && v <= 1.7e308; };   // (a NaN fails)
+    if (!finite_from(rule->pos_tol, true) || !finite_from(rule->rot_tol, true) || !finite_from(rule->x_lim, false)) return QR_E_SIZE;
+    if (r->obs_dim[0] < 3) return QR_E_SIZE;   // (agent 0's rule reads ex: three words)
+  }
+  if (!r->action || !r->reward || !r->done || (rule && !r->truncated)) return QR_E_NULL;
   for (int k = 0; k < r->n_agents; ++k)
     if (!r->obs[k] || !r->buf_obs[k] || !r->buf_obs_next[k] || !r->buf_action[k] || !r->buf_reward[k] || !r->buf_done[k]) return QR_E_NULL;
   if (r->n_agents == 2 && (r->final_obs[0] == nullptr) != (r->final_obs[1] == nullptr)) return QR_E_NULL;
@@ -727,8 +734,13 @@ static int do_replay_add(const QrReplayAdd* r, void* stream) {
   a.state = r->state; a.count = r->count; a.capacity = r->capacity; a.rows = (int64_t)r->n_steps * r->n_envs;
   a.action_row = r->action_row; a.n_agents = r->n_agents;
   const int64_t tiles = (a.rows + kReplayTile - 1) / kReplayTile;
-  hipLaunchKernelGGL(replay_add_kernel, dim3((unsigned)(tiles < kReplayCols ? tiles : kReplayCols), (unsigned)(kReplaySegments * r->n_agents)),
-                     dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  const dim3 grid((unsigned)(tiles < kReplayCols ? tiles : kReplayCols), (unsigned)(kReplaySegments * r->n_agents));
+  if (rule) {
+    const ReplayAddRuleArgs ra{a, ReplayRule{rule->x_lim, rule->pos_tol, rule->rot_tol}};
+    hipLaunchKernelGGL(replay_add_rule_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ra);
+  } else {
+    hipLaunchKernelGGL(replay_add_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+  }
   if (int rc = (int)hipGetLastError()) return rc;
   if (r->state) hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), r->state, a.rows, r->capacity, (int64_t)0);
   return (int)hipGetLastError();
@@ -749,7 +761,11 @@ static int do_replay_sample(const QrReplaySample* s, void* stream) {
 
 extern "C" {
 
-int qr_replay_add(const QrReplayAdd* add, void* stream) { return qr::do_replay_add(add, stream); }
+int qr_replay_add(const QrReplayAdd* add, void* stream) { return qr::do_replay_add(add, nullptr, stream); }
+
+int qr_replay_add_rule(const QrReplayAddRule* rule, void* stream) {
+  return rule ? qr::do_replay_add(&rule->add, rule, stream) : QR_E_NULL;
+}
 
 int qr_replay_sample(const QrReplaySample* sample, void* stream) { return qr::do_replay_sample(sample, stream); }
 

@@ -8,9 +8,13 @@ iteration actor loss (2) and actor step (1); SAC — sample, refill, critic loss
 actor and log_alpha that also leaves alpha = exp(log_alpha) (1).  The soft updates ride on the steps: a network's target is updated
 in the launch that steps the network (see `_Updater._polyak_now`).  Nothing synchronises; `capture` records policy_update_freq
 iterations in one graph.
+
+The collection half of the same loop (main.py:140-181) is `OffPolicyCollector`: the uniform-random warm-up, TD3's decaying exploration
+std or SAC's sampled actions, one horizon per call into a `RolloutStorage`, and the append with the reference's time-limit done rule.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -18,7 +22,8 @@ import torch
 from . import _lib
 from .optim import PolyakAdamW
 from .sac import sac_actor_loss, sac_actor_loss_ctde, sac_critic_loss, sac_critic_loss_ctde
-from .td3 import ReplayBuffer, td3_actor_loss, td3_actor_loss_ctde, td3_critic_loss, td3_critic_loss_ctde
+from .rollout import RolloutStorage
+from .td3 import TIME_LIMITS, ReplayBuffer, td3_actor_loss, td3_actor_loss_ctde, td3_critic_loss, td3_critic_loss_ctde
 
 MODES = ("single", "dtde", "ctde")   # Coupled with one agent; Decoupled with own critics; Decoupled with one centralized critic per agent
 T0, ETA_MIN = 1_000_000, 1e-5        # CosineAnnealingWarmRestarts(T_0, eta_min) of both algorithms (td3.py:79-80, sac.py:81-82)
@@ -315,3 +320,101 @@ class SacUpdater(_Updater):
 
     def _stats(self):
         return self.critic_stats, self.actor_stats
+
+
+class OffPolicyCollector:
+    """The collection half of the reference's TD3 / SAC loop (main.py:140-181), one horizon of T env-steps per `collect` call: a host
+    object with no kernel of its own — every launch is one the library already has.
+
+    env: a Coupled or Decoupled `QuadVecEnv` with auto_reset=True (and max_episode_steps set, or no transition is ever at the time
+    limit); buffer: the `ReplayBuffer` the horizons are appended to, with the env's agents and observation widths.  While
+    total_timesteps < start_timesteps the actions are uniform in [-1, 1) (rand * 2 - 1, main.py:155), drawn with torch into a tensor
+    made once and flown through the given-actions rollout (qr_rollout); afterwards the actors run inside the step kernel
+    (`RolloutStorage.collect`: qr_rollout_actor) — algo "td3": tanh-of-mean actors whose `log_std` tensors are set in place to
+    log(explor_noise_std), "sac": tanh-of-sample actors as they are.  Then `buffer.append(storage, time_limit=time_limit)`.
+
+    explor_noise_std follows the reference's recurrence (main.py:74-77, 237-239), one step of it per env-step collected, the warm-up's
+    included: std <- std - (init - min) / decay_timesteps while std > min, else min; decay_timesteps=None keeps it at init
+    (use_explor_noise_decay off).  Deviation: the reference applies it before every step, here a launch flies T steps, so the value
+    at the horizon's first step is held for the horizon.  Likewise the warm-up ends at a horizon's boundary.
+    time_limit "solved" sets buffer.time_limit_rule.x_lim to the env's.  Nothing synchronises, and from the second call of each kind
+    nothing is allocated.  total_timesteps: env-steps collected per env so far, a host int."""
+    ALGOS = ("td3", "sac")
+
+    def __init__(self, env, buffer: ReplayBuffer, horizon: int, start_timesteps: int = 0, algo: str = "td3", explor_noise_std_init: float = 0.3,
+                 explor_noise_std_min: float = 0.05, decay_timesteps: Optional[int] = None, time_limit: str = "solved",
+                 generator: Optional[torch.Generator] = None):
+        what = "OffPolicyCollector"
+        if algo not in self.ALGOS:
+            raise ValueError(f"{what}: algo must be one of {self.ALGOS}, got {algo!r}")
+        if time_limit not in TIME_LIMITS:
+            raise ValueError(f"{what}: time_limit must be one of {TIME_LIMITS}, got {time_limit!r}")
+        self.T, self.start_timesteps = int(horizon), int(start_timesteps)
+        if self.T < 1 or self.start_timesteps < 0:
+            raise ValueError(f"{what}: horizon must be >= 1 and start_timesteps >= 0")
+        if decay_timesteps is not None and int(decay_timesteps) < 1:
+            raise ValueError(f"{what}: decay_timesteps must be >= 1 (None: no decay)")
+        self.std_init, self.std_min = float(explor_noise_std_init), float(explor_noise_std_min)
+        if not 0.0 < self.std_min <= self.std_init < float("inf"):
+            raise ValueError(f"{what}: need 0 < explor_noise_std_min <= explor_noise_std_init < inf, got {self.std_min}, {self.std_init}")
+        if not isinstance(buffer, ReplayBuffer):
+            raise ValueError(f"{what}: buffer must be a ReplayBuffer")
+        if not getattr(env, "auto_reset", False):
+            raise ValueError(f"{what} needs an env with auto_reset=True: a horizon runs through episode ends")
+        if env.n_agents != buffer.n_agents or list(env.obs_dims) != buffer.obs_dims or sum(buffer.action_dims) != env.action_dim:
+            raise ValueError(f"{what}: the env has {env.n_agents} agent(s) with observations {list(env.obs_dims)} and {env.action_dim} action "
+                             f"columns; the buffer has {buffer.n_agents} with {buffer.obs_dims} and {buffer.action_dims}")
+        if self.T * env.num_envs > buffer.capacity:
+            raise ValueError(f"{what}: a horizon of {self.T} x {env.num_envs} transitions does not fit a buffer of {buffer.capacity}")
+        if time_limit == "solved" and buffer.obs_dims[0] < 3:
+            raise ValueError(f"{what}: time_limit='solved' reads ex, the first three words of agent 0's observation")
+        self.env, self.buffer, self.algo, self.time_limit, self.generator = env, buffer, algo, time_limit, generator
+        self.noise_std_decay = 0.0 if decay_timesteps is None else (self.std_init - self.std_min) / int(decay_timesteps)
+        self.explor_noise_std = self.std_init
+        self.total_timesteps = 0
+        if time_limit == "solved":
+            buffer.time_limit_rule = buffer.time_limit_rule._replace(x_lim=float(env.x_lim))
+        self.storage = RolloutStorage(env, self.T, action_dims=buffer.action_dims)
+        self.random_actions = torch.empty(self.T, env.num_envs, env.action_dim, dtype=torch.float32, device=env.device) if self.start_timesteps else None
+
+    @staticmethod
+    def decay(std: float, noise_std_decay: float, std_min: float, steps: int = 1) -> float:
+        """`steps` applications of main.py:237-239 to the exploration std."""
+        for _ in range(steps):
+            std = std - noise_std_decay if std > std_min else std_min
+        return std
+
+    def _check_actors(self, actors) -> list:
+        what = "OffPolicyCollector.collect"
+        actors = list(actors)
+        if len(actors) != self.env.n_agents:
+            raise ValueError(f"{what} needs one actor per agent ({self.env.n_agents}), got {len(actors)}")
+        for a in actors:
+            if self.algo == "td3" and (a.squash != _lib.ACTOR_TANH_MEAN or a.log_std is None or a.log_std_w is not None):
+                raise ValueError(f"{what}: algo 'td3' takes tanh-of-mean actors with a log_std tensor (ActorParams.from_td3_module)")
+            if self.algo == "sac" and (a.squash != _lib.ACTOR_TANH_SAMPLE or a.log_std_w is None):
+                raise ValueError(f"{what}: algo 'sac' takes tanh-of-sample actors with a log_std head (ActorParams.from_sac_module)")
+        return actors
+
+    def collect(self, actors, **kw) -> RolloutStorage:
+        """One horizon into `storage` and from there into the buffer.  actors: one `ActorParams` per agent (checked in the warm-up too);
+        kw goes to `RolloutStorage.collect` (noise, noise_seed, max_action).  Returns the storage."""
+        env, st = self.env, self.storage
+        actors = self._check_actors(actors)
+        if self.total_timesteps < self.start_timesteps:
+            cur = env._last_obs
+            if cur is None:
+                raise ValueError("no current observation: call env.get_norm_error_state() or env.step() first")
+            st.set_initial_obs(cur)
+            self.random_actions.uniform_(0.0, 1.0, generator=self.generator).mul_(2.0).sub_(1.0)
+            env.rollout(self.random_actions, out=st.horizon())
+            st.act_all.copy_(self.random_actions)   # (the given-actions rollout does not write the action rows)
+        else:
+            if self.algo == "td3":
+                for a in actors:
+                    a.log_std.fill_(math.log(self.explor_noise_std))
+            st.collect(env, actors, **kw)
+        self.buffer.append(st, time_limit=self.time_limit)
+        self.explor_noise_std = self.decay(self.explor_noise_std, self.noise_std_decay, self.std_min, self.T)
+        self.total_timesteps += self.T
+        return st

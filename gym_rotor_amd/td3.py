@@ -21,12 +21,15 @@ six gradients are produced.  A written-out CTDE iteration is `td3_critic_loss_ct
 The data side matches: `ReplayBuffer.append` writes a whole horizon into the ring in one launch (`replay_add`: qr_replay_add), and
 `ReplayBuffer.sample_index` draws a minibatch's distinct rows in O(B) (`replay_sample`: qr_replay_sample) — a keyed permutation of
 [0, current_size) in integers, not a permutation of the whole buffer.  `use_device_state()` moves the three counters into device
-memory, so an iteration that appends and samples can be captured in a graph once and replayed.
+memory, so an iteration that appends and samples can be captured in a graph once and replayed.  `append(storage, time_limit="solved")`
+stores the reference's done at the episode time limit (main.py:169-173: "solved and not crashed") in the same single launch
+(qr_replay_add_rule); the default, "own", stores each agent's own flag.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+import math
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -34,12 +37,30 @@ from . import _lib
 from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams, _grad_outputs, _vector
 
 
+TIME_LIMITS = ("own", "solved")   # what `done` holds on a transition at the episode time limit: the agent's own flag / main.py:169-173
+
+
+class TimeLimitRule(NamedTuple):
+    """The numbers of the reference's time-limit rule (main.py:169-173): done = all |ex| <= pos_tol (ex = obs_next_0[0:3] * x_lim) for
+    agent 0, |eb1| <= rot_tol (eb1 = obs_next_1[0] * pi) for Decoupled's agent 1, and the reward is not the crash reward -1."""
+    x_lim: float = 1.0      # the env's position limit (QuadVecEnv.x_lim)
+    pos_tol: float = 0.03   # [m]
+    rot_tol: float = 0.03   # [rad]
+
+    def check(self, what: str) -> "TimeLimitRule":
+        x, p, r = (float(v) for v in self)
+        if not (math.isfinite(x) and x > 0.0 and math.isfinite(p) and p >= 0.0 and math.isfinite(r) and r >= 0.0):
+            raise ValueError(f"{what}: the time-limit rule needs a finite x_lim > 0 and finite tolerances >= 0, got {tuple(self)}")
+        return TimeLimitRule(x, p, r)
+
+
 class ReplayBuffer:
     """The reference's `ReplayBuffer` (algos/replay_buffer.py) for TD3 / SAC as flat device tensors per agent k:
         obs[k], obs_next[k] [capacity, D_k]   act[k] [capacity, A_k]   rwd[k], done[k] [capacity] float32 (done: 0.0 / 1.0)
     `count` (the next row to write) and `current_size` follow the reference's ring rule, one transition at a time:
     count = (count + 1) % capacity, current_size = min(current_size + 1, capacity).
-    seed: the 64-bit key of `sample_index`'s draws (`seed(s)` changes it); `draw` counts them."""
+    seed: the 64-bit key of `sample_index`'s draws (`seed(s)` changes it); `draw` counts them.
+    time_limit_rule: the numbers `add` / `append` use with time_limit="solved" (set x_lim to the env's)."""
 
     def __init__(self, capacity: int, obs_dims: Sequence[int], action_dims: Sequence[int], device, seed: int = 0):
         self.capacity = int(capacity)
@@ -57,6 +78,7 @@ class ReplayBuffer:
         self.count, self.current_size = 0, 0
         self.draw = 0          # minibatches drawn by sample_index: with the seed, the key of the next one
         self.seed(seed)
+        self.time_limit_rule = TimeLimitRule()
         self.state = None      # use_device_state(): int64 [3] = (count, current_size, draw) on the device
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)   # qr_replay_sample raises it if a walk hits its cap (it cannot)
         self._cache = {}   # (agent, B, max_workgroups) -> y, workspace, stats of td3_critic_loss; ("actor", ...) -> td3_actor_loss's
@@ -65,25 +87,47 @@ class ReplayBuffer:
     def n_agents(self) -> int:
         return len(self.obs_dims)
 
-    def add(self, storage) -> None:
-        """Append one collected `RolloutStorage` horizon: its T * N transitions in (t, n) order — what T * N calls of the reference's
-        store_transition leave, wrapping at capacity.  obs_next is the reference's: final_obs where the env was re-sampled in the
-        step (any agent's done, or truncated: qr_critic_next_values' rule), obs[t + 1] elsewhere; done is agent k's own flag.
-        Plain torch copies, once per horizon."""
+    def _check_storage(self, storage, time_limit: str) -> Optional[TimeLimitRule]:
+        """add's and append's checks, before anything is written; the rule's numbers for time_limit "solved", None for "own"."""
         T, N = storage.T, storage.N
         n = T * N
+        if time_limit not in TIME_LIMITS:
+            raise ValueError(f"time_limit must be one of {TIME_LIMITS}, got {time_limit!r}")
         if n > self.capacity:
             raise ValueError(f"a horizon of {T} x {N} = {n} transitions does not fit a buffer of {self.capacity}")
         if storage.n_agents != self.n_agents or [o.shape[-1] for o in storage.obs] != self.obs_dims or list(storage.action_dims) != self.action_dims:
             raise ValueError("the storage's agents, observation widths or action widths differ from the buffer's")
+        if time_limit == "own":
+            return None
+        if storage.truncated is None:
+            raise ValueError("time_limit='solved' needs the storage's truncated flags: they mark the transitions at the time limit")
+        if self.obs_dims[0] < 3:
+            raise ValueError("time_limit='solved' reads ex, the first three words of agent 0's observation")
+        return TimeLimitRule(*self.time_limit_rule).check("ReplayBuffer")
+
+    def add(self, storage, time_limit: str = "own") -> None:
+        """Append one collected `RolloutStorage` horizon: its T * N transitions in (t, n) order — what T * N calls of the reference's
+        store_transition leave, wrapping at capacity.  obs_next is the reference's: final_obs where the env was re-sampled in the
+        step (any agent's done, or truncated: qr_critic_next_values' rule), obs[t + 1] elsewhere; done is agent k's own flag.
+        time_limit="solved": on transitions whose `truncated` is set, done is the reference's main.py:169-173 instead — agent 0: all
+        |obs_next_0[0:3] * x_lim| <= pos_tol, agent 1: |obs_next_1[0] * pi| <= rot_tol, compared in float64, and reward != -1
+        (`time_limit_rule` holds the three numbers).  Plain torch copies, once per horizon."""
+        rule = self._check_storage(storage, time_limit)
+        T, N = storage.T, storage.N
+        n = T * N
         reset = storage.reset_mask().reshape(n, 1) if storage.final_obs is not None else None
         first = min(n, self.capacity - self.count)   # rows [count, count + first), then rows [0, n - first)
         for k in range(self.n_agents):
             nxt = storage.obs[k][1:].reshape(n, -1)
             if reset is not None:
                 nxt = torch.where(reset, storage.final_obs[k].reshape(n, -1), nxt)
+            done = storage.done[..., k].reshape(n)
+            if rule is not None:
+                err = nxt[:, :3].double() * rule.x_lim if k == 0 else nxt[:, :1].double() * math.pi
+                solved = (err.abs() <= (rule.pos_tol if k == 0 else rule.rot_tol)).all(-1) & (storage.reward[..., k].reshape(n) != -1.0)
+                done = torch.where(storage.truncated.reshape(n), solved, done)
             cols = ((self.obs[k], storage.obs[k][:-1].reshape(n, -1)), (self.obs_next[k], nxt), (self.act[k], storage.act[k].reshape(n, -1)),
-                    (self.rwd[k], storage.reward[..., k].reshape(n)), (self.done[k], storage.done[..., k].reshape(n).to(torch.float32)))
+                    (self.rwd[k], storage.reward[..., k].reshape(n)), (self.done[k], done.to(torch.float32)))
             for dst, src in cols:
                 dst[self.count:self.count + first].copy_(src[:first])
                 if n > first:
@@ -117,17 +161,13 @@ class ReplayBuffer:
             raise ValueError("ReplayBuffer: no device state (use_device_state() was not called)")
         self.count, self.current_size, self.draw = (int(v) for v in self.state.tolist())
 
-    def append(self, storage) -> None:
-        """`add` in ONE launch (qr_replay_add): the same T * N transitions into the same ring rows with the same obs_next and done
-        rule, bit for bit, for all agents and all five tensors, without a temporary."""
-        T, N = storage.T, storage.N
-        n = T * N
-        if n > self.capacity:
-            raise ValueError(f"a horizon of {T} x {N} = {n} transitions does not fit a buffer of {self.capacity}")
-        if storage.n_agents != self.n_agents or [o.shape[-1] for o in storage.obs] != self.obs_dims or list(storage.action_dims) != self.action_dims:
-            raise ValueError("the storage's agents, observation widths or action widths differ from the buffer's")
+    def append(self, storage, time_limit: str = "own") -> None:
+        """`add` in ONE launch (qr_replay_add; time_limit="solved": qr_replay_add_rule): the same T * N transitions into the same ring rows
+        with the same obs_next and done rule, bit for bit, for all agents and all five tensors, without a temporary."""
+        rule = self._check_storage(storage, time_limit)
+        n = storage.T * storage.N
         replay_add([self.tensors(k) for k in range(self.n_agents)], storage.obs, storage.final_obs, storage.act_all, storage.reward, storage.done,
-                   storage.truncated, self.count, state=self.state)
+                   storage.truncated, self.count, state=self.state, time_limit_rule=rule)
         self.count = (self.count + n) % self.capacity
         self.current_size = min(self.current_size + n, self.capacity)
 
@@ -152,7 +192,7 @@ class ReplayBuffer:
 
 
 def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tensor, done: torch.Tensor, truncated: Optional[torch.Tensor],
-               count: int, *, state: Optional[torch.Tensor] = None) -> None:
+               count: int, *, state: Optional[torch.Tensor] = None, time_limit_rule: Optional[TimeLimitRule] = None) -> None:
     """One collected horizon into the ring of a flat transition buffer in one launch (qr_replay_add).  tensors: per agent (one or two)
     a dict with obs, obs_next [capacity, D_k], act [capacity, A_k], rwd, done [capacity], contiguous float32 (`ReplayBuffer.tensors(k)`),
     written in place.  The horizon as `RolloutStorage` holds it: obs a list of [T + 1, N, D_k]; final_obs a list of [T, N, D_k] or None;
@@ -160,8 +200,15 @@ def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tens
     [T, N] (or None) bool.  Transition j = t * N + n goes to row (count + j) % capacity; obs_next is final_obs[t, n] where it is given and
     any agent's done or truncated is set, obs[t + 1, n] elsewhere; done is agent k's own flag as 0.0 / 1.0.  The caller advances its
     counters: count = (count + T * N) % capacity, current_size = min(current_size + T * N, capacity).  state: the int64 [3] device
-    counters (count, current_size, draw), read on the device instead of `count` and advanced there behind the launch."""
+    counters (count, current_size, draw), read on the device instead of `count` and advanced there behind the launch.
+    time_limit_rule: None, or a `TimeLimitRule` (x_lim, pos_tol, rot_tol): the same launch through qr_replay_add_rule, whose done on a
+    transition with truncated set is the reference's main.py:169-173 — the agent's error in the stored obs_next is within tolerance and
+    its reward is not -1 — and the own flag elsewhere.  Needs truncated and an agent 0 observation of at least three words."""
     what = "replay_add"
+    if time_limit_rule is not None:
+        time_limit_rule = TimeLimitRule(*time_limit_rule).check(what)
+        if truncated is None:
+            raise ValueError(f"{what}: the time-limit rule needs truncated")
     tensors = [dict(t) for t in tensors]
     obs = [obs] if isinstance(obs, torch.Tensor) else list(obs)
     if final_obs is not None:
@@ -185,6 +232,8 @@ def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tens
         ad.append(a.shape[1])
     if sum(ad) != row or min(od + ad) < 1 or max(od + ad) > _lib.REPLAY_MAX_WIDTH:
         raise ValueError(f"{what}: the buffers' action widths {ad} must add up to the action row's {row}; widths lie in 1..{_lib.REPLAY_MAX_WIDTH}")
+    if time_limit_rule is not None and od[0] < 3:
+        raise ValueError(f"{what}: the time-limit rule reads the first three words of agent 0's observation, which has {od[0]}")
     if T < 1 or N < 1 or T * N > capacity:
         raise ValueError(f"{what}: a horizon of {T} x {N} = {T * N} transitions does not fit a buffer of {capacity}")
     def need(x, shape, dtype, name):
@@ -211,8 +260,12 @@ def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tens
                              capacity=capacity, n_steps=T, n_envs=N, obs_dims=od, action_dims=ad,
                              col_offsets=[sum(ad[:k]) for k in range(na)], action_row=row)
     with torch.cuda.device(dev):
-        rc = _lib.load().qr_replay_add(C.byref(r), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_replay_add")
+        if time_limit_rule is None:
+            rc = _lib.load().qr_replay_add(C.byref(r), torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rr = _lib.replay_add_rule_args(r, **time_limit_rule._asdict())
+            rc = _lib.load().qr_replay_add_rule(C.byref(rr), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_replay_add" if time_limit_rule is None else "qr_replay_add_rule")
 
 
 def _check_state(what: str, state, dev):

@@ -450,6 +450,21 @@ def qr_replay_add(buffers: List[torch.Tensor], obs: List[torch.Tensor], final_ob
     replay_add(tensors, list(obs), list(final_obs) if final_obs else None, action, reward, done, truncated, count, state=state)
 
 
+@torch.library.custom_op(f"{_NS}::qr_replay_add_rule", mutates_args=("buffers", "state"))
+def qr_replay_add_rule(buffers: List[torch.Tensor], obs: List[torch.Tensor], final_obs: List[torch.Tensor], action: torch.Tensor, reward: torch.Tensor,
+                       done: torch.Tensor, truncated: torch.Tensor, count: int, state: Optional[torch.Tensor], x_lim: float, pos_tol: float,
+                       rot_tol: float) -> None:
+    """qr_replay_add with the reference's time-limit "solved" rule in the done it stores (qr_replay_add_rule), as td3.replay_add with
+    time_limit_rule=(x_lim, pos_tol, rot_tol); the other arguments as qr_replay_add's, truncated required."""
+    from .td3 import TimeLimitRule, replay_add
+    _gpu(action)
+    if len(buffers) not in (5, 10):
+        raise ValueError("a replay buffer is 5 tensors per agent: obs, obs_next, act, rwd, done")
+    tensors = [dict(zip(_lib.REPLAY_BUFFER_NAMES, buffers[5 * k:5 * k + 5])) for k in range(len(buffers) // 5)]
+    replay_add(tensors, list(obs), list(final_obs) if final_obs else None, action, reward, done, truncated, count, state=state,
+               time_limit_rule=TimeLimitRule(x_lim, pos_tol, rot_tol))
+
+
 @torch.library.custom_op(f"{_NS}::qr_replay_sample", mutates_args=("out", "state", "status"))
 def qr_replay_sample(out: torch.Tensor, n: int, seed: int, draw: int, state: Optional[torch.Tensor], status: Optional[torch.Tensor]) -> None:
     """out.numel() pairwise distinct rows below n in one O(B) launch (qr_replay_sample), as td3.replay_sample; seed and draw are passed as

@@ -1003,6 +1003,26 @@ typedef struct QrReplayAdd {
  * written on an error.  Members of agent 1 are not read when n_agents is 1. */
 int qr_replay_add(const QrReplayAdd* add, void* stream);
 
+/* The same append with the reference's time-limit "solved" rule in the done it stores (main.py:169-173): at the episode time limit the
+ * reference overwrites done_n with "the error is within tolerance and the agent did not crash".  For transition (t, n) and agent k:
+ *     limit           = truncated[t][n] != 0
+ *     src_k           = the row buf_obs_next[k] receives for (t, n): final_obs[k][t][n] where final_obs is given (truncated is set, so
+ *                       the env was re-sampled), obs[k][t + 1][n] otherwise
+ *     solved_0        = fabs((double)src_0[c] * x_lim) <= pos_tol for c = 0, 1, 2     (ex, de-normalised: utils/utils.py:21-39)
+ *     solved_1        = fabs((double)src_1[0] * pi) <= rot_tol                        (eb1; pi = the double nearest pi; two agents only)
+ *     buf_done[k][row] = limit ? (solved_k && reward[t][n][k] != -1.0f ? 1.0 : 0.0) : (done[t][n][k] ? 1.0 : 0.0)
+ * One agent (Coupled) is agent 0 alone and its rule reads ex alone, as the reference's MONO branch does.  The comparisons are made in
+ * double on the float32 words.  -1.0f is the crash reward as the step kernels store it (a literal, not arithmetic).  Everything else —
+ * the other four tensors, the ring rows, the wrap, the device counters — is qr_replay_add's, bit for bit, in the same single launch. */
+typedef struct QrReplayAddRule {
+  QrReplayAdd add;                /* truncated and reward are required here */
+  double x_lim;                   /* the env's position limit (QrCoeffs.x_lim), > 0 */
+  double pos_tol, rot_tol;        /* [m], [rad]; the reference's are 0.03 and 0.03; finite, >= 0 */
+} QrReplayAddRule;
+/* qr_replay_add's errors in qr_replay_add's order, with: QR_E_SIZE also for a non-finite or negative pos_tol or rot_tol, an x_lim that is
+ * not finite and > 0, or obs_dim[0] < 3; QR_E_NULL also for a NULL truncated.  Nothing is launched or written on an error. */
+int qr_replay_add_rule(const QrReplayAddRule* rule, void* stream);
+
 /* `batch` pairwise distinct rows below n, in O(batch) and in integers only: index[j] is the image of j under a keyed pseudo-random
  * permutation of [0, n), so the same (n, seed, draw) gives the same indices on any device, launch geometry or CPU restatement.
  *     h    = max(1, ceil(bit_length(n - 1) / 2)),  mask = 2^h - 1

@@ -19,6 +19,7 @@ from .td3 import TimeLimitRule, replay_add, replay_sample  # noqa: F401
 from .sac import sac_actor_grad, sac_actor_loss, sac_actor_workspace_bytes, sac_critic_loss, sac_target  # noqa: F401
 from .sac import sac_critic_loss_ctde, sac_target_ctde  # noqa: F401
 from .sac import sac_actor_grad_ctde, sac_actor_loss_ctde, sac_actor_workspace_bytes_ctde  # noqa: F401
+from .noise import DeviceNoise, noise_fill  # noqa: F401
 from .offpolicy import OffPolicyCollector, SacUpdater, Td3Updater  # noqa: F401
 from .evaluate import EvalResult, PopulationResult, evaluate_policy, evaluate_population  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)

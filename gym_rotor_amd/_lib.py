@@ -40,7 +40,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
-           "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample")
+           "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill")
 
 
 class QrCoeffs(C.Structure):
@@ -356,6 +356,31 @@ def replay_sample_args(index, status, state, *, n, batch, seed, draw) -> QrRepla
     return QrReplaySample(ptr(index), ptr(status), ptr(state), int(n), int(batch), int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1))
 
 
+NOISE_MAX_SLOTS = 16                     # qr_noise_fill: tensors per launch
+NOISE_NORMAL, NOISE_UNIFORM = 0, 1
+NOISE_KIND_ID = {"normal": NOISE_NORMAL, "uniform": NOISE_UNIFORM}
+NOISE_MAX_STREAM = 2 ** 30               # stream ids lie below it
+
+
+class QrNoiseSlot(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("count", C.c_int64), ("a", C.c_float), ("b", C.c_float), ("kind", C.c_uint32), ("stream", C.c_uint32)]
+
+
+class QrNoiseFill(C.Structure):
+    _fields_ = [("slot", QrNoiseSlot * 16), ("n_slots", C.c_int32), ("seed", C.c_uint64), ("draw_dev", C.c_void_p), ("draw", C.c_int64)]
+
+
+def noise_fill_args(tensors, kinds, a, b, streams, *, seed, draw, draw_dev) -> QrNoiseFill:
+    """QrNoiseFill of one qr_noise_fill launch over 1..16 tensors; kinds, a, b, streams: one per tensor; draw_dev: a device int64
+    tensor of one element or None."""
+    f = QrNoiseFill()
+    f.n_slots, f.seed, f.draw_dev, f.draw = len(tensors), int(seed) & (2 ** 64 - 1), ptr(draw_dev), int(draw)
+    for k, t in enumerate(tensors):
+        s = f.slot[k]
+        s.out, s.count, s.a, s.b, s.kind, s.stream = t.data_ptr(), t.numel(), float(a[k]), float(b[k]), int(kinds[k]), int(streams[k])
+    return f
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -565,6 +590,8 @@ def load():
     lib.qr_replay_add_rule.argtypes = [P(QrReplayAddRule), C.c_void_p]
     lib.qr_replay_sample.restype = C.c_int
     lib.qr_replay_sample.argtypes = [P(QrReplaySample), C.c_void_p]
+    lib.qr_noise_fill.restype = C.c_int
+    lib.qr_noise_fill.argtypes = [P(QrNoiseFill), C.c_void_p]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

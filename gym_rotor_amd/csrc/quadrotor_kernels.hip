@@ -58,6 +58,8 @@
 //   qr_replay.h    the replay buffer's append and its minibatch indices (qr_replay_add, qr_replay_add_rule, qr_replay_sample):
 //                  replay_add_kernel, replay_add_rule_kernel (the time-limit "solved" rule), replay_sample_kernel,
 //                  replay_advance_kernel (the opt-in device counters)
+//   qr_noise.h     the library's noise source (qr_noise_fill): up to sixteen normal or uniform tensors of a TD3 / SAC iteration from one
+//                  counter-based stream in one launch: noise_fill_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
@@ -87,6 +89,7 @@
 #include "qr_sac.h"
 #include "qr_sac_actor.h"
 #include "qr_replay.h"
+#include "qr_noise.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -757,9 +760,44 @@ static int do_replay_sample(const QrReplaySample* s, void* stream) {
   if (s->state) hipLaunchKernelGGL(replay_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), s->state, (int64_t)0, (int64_t)1, (int64_t)1);
   return (int)hipGetLastError();
 }
+
+static int do_noise_fill(const QrNoiseFill* n, void* stream) {
+  if (!n) return QR_E_NULL;
+  if (n->n_slots < 1 || n->n_slots > kNoiseSlots) return QR_E_SIZE;
+  int64_t quads = 0;
+  for (int k = 0; k < n->n_slots; ++k) {
+    const QrNoiseSlot& s = n->slot[k];
+    if (s.count < 1 || s.count > 0x1FFFFFFFCll || s.kind > QR_NOISE_UNIFORM || s.stream >= (1u << 30)) return QR_E_SIZE;
+    if (!__builtin_isfinite(s.a) || !__builtin_isfinite(s.b)) return QR_E_SIZE;
+    quads += (s.count + 3) / 4;
+  }
+  if (quads > 0x7FFFFFFFll || (!n->draw_dev && n->draw < 0)) return QR_E_SIZE;
+  for (int k = 0; k < n->n_slots; ++k)
+    if (!n->slot[k].out) return QR_E_NULL;
+  for (int k = 0; k < n->n_slots; ++k)
+    if (reinterpret_cast<uintptr_t>(n->slot[k].out) & 3u) return QR_E_ALIGN;
+  if (reinterpret_cast<uintptr_t>(n->draw_dev) & 7u) return QR_E_ALIGN;
+  NoiseArgs a{};
+  quads = 0;
+  for (int k = 0; k < kNoiseSlots; ++k) {
+    if (k < n->n_slots) {
+      const QrNoiseSlot& s = n->slot[k];
+      a.out[k] = s.out; a.count[k] = s.count; a.a[k] = s.a; a.b[k] = s.b; a.kind[k] = s.kind; a.stream[k] = s.stream;
+      quads += (s.count + 3) / 4;
+    }
+    a.qend[k] = (uint32_t)quads;
+  }
+  a.seed = n->seed; a.draw_dev = n->draw_dev; a.draw = n->draw;
+  const int64_t blocks = (quads + kNoiseBlock - 1) / kNoiseBlock;
+  hipLaunchKernelGGL(noise_fill_kernel, dim3((unsigned)(blocks < kNoiseGrid ? blocks : kNoiseGrid)), dim3(kNoiseBlock), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_noise_fill(const QrNoiseFill* fill, void* stream) { return qr::do_noise_fill(fill, stream); }
 
 int qr_replay_add(const QrReplayAdd* add, void* stream) { return qr::do_replay_add(add, nullptr, stream); }
 

@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .noise import check_seed, noise_fill
 from .optim import PolyakAdamW
 from .sac import sac_actor_loss, sac_actor_loss_ctde, sac_critic_loss, sac_critic_loss_ctde
 from .rollout import RolloutStorage
@@ -27,6 +28,25 @@ from .td3 import TIME_LIMITS, ReplayBuffer, td3_actor_loss, td3_actor_loss_ctde,
 
 MODES = ("single", "dtde", "ctde")   # Coupled with one agent; Decoupled with own critics; Decoupled with one centralized critic per agent
 T0, ETA_MIN = 1_000_000, 1e-5        # CosineAnnealingWarmRestarts(T_0, eta_min) of both algorithms (td3.py:79-80, sac.py:81-82)
+NOISE_SOURCES = ("torch", "device")  # who draws: torch.Tensor.normal_ per tensor, or one noise_fill launch per agent (noise.py)
+# every name a `_noise_shapes` can return: a tensor's place here is part of its stream id
+NOISE_NAMES = ("smooth", "reg", "next", "eps", "eps_reg", "eps_next", "eps_pert", "noise_logp", "eps_logp", "eps_other")
+REG_STD = 0.05                       # policy_regularization's N(0, 0.05) row
+# the collector's warm-up stream: above every `noise_stream` id, so that a collector and an updater sharing a seed never share words
+COLLECTOR_STREAM = 1 << 29
+
+
+def noise_stream(k: int, name: str, j: int = 0) -> int:
+    """The stream id of agent k's noise tensor `name` (position j inside a ctde pair, else 0) under noise_source="device"."""
+    return (k << 8) | (NOISE_NAMES.index(name) << 2) | j
+
+
+def _noise_source(what: str, noise_source, noise_seed, generator) -> int:
+    if noise_source not in NOISE_SOURCES:
+        raise ValueError(f"{what}: noise_source must be one of {NOISE_SOURCES}, got {noise_source!r}")
+    if noise_source == "device" and generator is not None:
+        raise ValueError(f"{what}: noise_source='device' draws from the library's own stream (noise_seed); it takes no torch generator")
+    return check_seed(what, noise_seed)
 
 
 def _layers(module, names, what: str):
@@ -56,8 +76,10 @@ class _Updater:
     actor_layers: Sequence[str] = ()
 
     def __init__(self, actors, critics, critic_targets, *, mode, discount, tau, policy_update_freq, lam_T, lam_S, lam_M, max_action, lr_a, lr_c,
-                 grad_max_norm, batch_size, nominal, generator, refill_noise):
+                 grad_max_norm, batch_size, nominal, generator, refill_noise, noise_source="torch", noise_seed=0):
         what = self.what
+        self.noise_seed = _noise_source(what, noise_source, noise_seed, generator)
+        self.noise_source = noise_source
         self.actors, self.critics, self.critic_targets = list(actors), list(critics), list(critic_targets)
         n = self.n_agents = len(self.actors)
         if mode not in MODES:
@@ -94,7 +116,7 @@ class _Updater:
         self.critic_opts = [PolyakAdamW(critic_params[k], targets=[t.data for t in target_params[k]], lr=self.lr_c[k], **hyper) for k in range(n)]
         f32 = dict(dtype=torch.float32, device=self.device)
         self.critic_stats = [torch.zeros(4, **f32) for _ in range(n)]
-        self.index, self.noise, self._dims = None, None, None
+        self.index, self.noise, self._dims, self._fills = None, None, None, None
 
     # -- the minibatch tensors -------------------------------------------------------------------------------------------------------
     def _noise_shapes(self, k: int, B: int, od, ad) -> dict:
@@ -118,11 +140,26 @@ class _Updater:
             shapes = self._noise_shapes(k, B, buffer.obs_dims, buffer.action_dims)
             self.noise.append({name: (tuple(torch.zeros(s, dtype=torch.float32, device=dev) for s in shape) if isinstance(shape, list) else
                                       torch.zeros(shape, dtype=torch.float32, device=dev)) for name, shape in shapes.items()})
+        # per agent what one noise_fill launch takes: the tensors in `noise[k]`'s order, their stream ids and standard deviations
+        self._fills = []
+        for k in range(self.n_agents):
+            flat = [(name, j, x) for name, t in self.noise[k].items() for j, x in enumerate(t if isinstance(t, tuple) else (t,))]
+            self._fills.append(([x for _, _, x in flat], [noise_stream(k, name, j) for name, j, _ in flat],
+                                [REG_STD if name == "reg" else 1.0 for name, _, _ in flat]))
         self._dims = dims
 
-    def _refill(self, k: int) -> None:
-        """Agent k's draws of this iteration, in place: standard normal for the samples, N(0, 0.05) for policy_regularization's row."""
+    def _refill(self, k: int, buffer: ReplayBuffer) -> None:
+        """Agent k's draws of this iteration, in place: standard normal for the samples, N(0, 0.05) for policy_regularization's row.
+        noise_source "torch": one `normal_` per tensor.  "device": ONE `noise_fill` launch over all of them, keyed by noise_seed, the
+        buffer's draw number as `sample_index` has just left it — read on the device where the buffer keeps its counters there, so
+        that a captured graph draws fresh noise at every replay, the same an eager iteration draws for that minibatch number — and
+        `noise_stream(k, name, j)`."""
         if not self.refill_noise:
+            return
+        if self.noise_source == "device":
+            tensors, streams, stds = self._fills[k]
+            noise_fill(tensors, seed=self.noise_seed, draw=buffer.draw, streams=streams, b=stds,
+                       draw_dev=None if buffer.state is None else buffer.state[2:3])
             return
         for name, t in self.noise[k].items():
             for x in (t if isinstance(t, tuple) else (t,)):
@@ -156,7 +193,7 @@ class _Updater:
             polyak = self._polyak_now()
             for k in range(self.n_agents):
                 buffer.sample_index(self.batch_size, out=self.index[k])
-                self._refill(k)
+                self._refill(k, buffer)
                 self._iterate(buffer, k, polyak)
         return self._stats()
 
@@ -174,7 +211,7 @@ class _Updater:
         if self.device.type != "cuda":
             raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
         graph = torch.cuda.CUDAGraph()
-        if self.generator is not None and self.refill_noise and hasattr(graph, "register_generator_state"):
+        if self.noise_source == "torch" and self.generator is not None and self.refill_noise and hasattr(graph, "register_generator_state"):
             graph.register_generator_state(self.generator)
         start, host = self.total_it, (buffer.count, buffer.current_size, buffer.draw)
         torch.cuda.synchronize(self.device)
@@ -200,7 +237,10 @@ class Td3Updater(_Updater):
     (one agent), "dtde" (two agents, own critics) or "ctde" (two agents, each with a centralized critic).  The hyperparameters are the
     reference's names and defaults (args_parse.py:42-59, 76-78); lr_a, lr_c: a number or one per agent; the schedule is
     CosineAnnealingWarmRestarts(1_000_000, 1e-5).  nominal: per agent the [A_k] hover action of policy_regularization (needed when
-    lam_M != 0).  generator: the torch generator of the noise draws (None: the device's default).
+    lam_M != 0).  generator: the torch generator of the noise draws (None: the device's default).  noise_source: "torch" draws each
+    noise tensor with its own `normal_`; "device" fills all of an agent's tensors in ONE `noise_fill` launch from the library's
+    counter-based stream, keyed by noise_seed, the buffer's draw number and `noise_stream(k, name, j)` — the same values eager and
+    under graph replay for the same minibatch number, whatever the torch version; it takes no generator.
     Owns per agent `critic_opts[k]` (`PolyakAdamW` over the twelve critic tensors and their targets) and `actor_opts[k]` (over the
     six actor tensors and theirs), `index[k]` (int64 [B]) and `noise[k]` = {"smooth": the [B, A_k] smoothing draws (ctde: the pair),
     "reg": the [D_k] row}.  Per iteration and agent: `sample_index`, the draws, `td3_critic_loss[_ctde]`, the critic's step, and when
@@ -211,10 +251,12 @@ class Td3Updater(_Updater):
     def __init__(self, actors, critics, actor_targets, critic_targets, *, mode: str = "single", discount: float = 0.99, tau: float = 0.005,
                  target_noise: float = 0.2, noise_clip: float = 0.5, policy_update_freq: int = 3, lam_T: float = 0.4, lam_S: float = 0.3,
                  lam_M: float = 0.6, max_action: float = 1.0, lr_a=3e-4, lr_c=2e-4, grad_max_norm: float = 100.0, batch_size: int = 256,
-                 nominal=None, generator: Optional[torch.Generator] = None, refill_noise: bool = True):
+                 nominal=None, generator: Optional[torch.Generator] = None, refill_noise: bool = True, noise_source: str = "torch",
+                 noise_seed: int = 0):
         super().__init__(actors, critics, critic_targets, mode=mode, discount=discount, tau=tau, policy_update_freq=policy_update_freq, lam_T=lam_T,
                          lam_S=lam_S, lam_M=lam_M, max_action=max_action, lr_a=lr_a, lr_c=lr_c, grad_max_norm=grad_max_norm,
-                         batch_size=batch_size, nominal=nominal, generator=generator, refill_noise=refill_noise)
+                         batch_size=batch_size, nominal=nominal, generator=generator, refill_noise=refill_noise, noise_source=noise_source,
+                         noise_seed=noise_seed)
         self.actor_targets = list(actor_targets)
         if len(self.actor_targets) != self.n_agents:
             raise ValueError("Td3Updater needs one actor target per agent")
@@ -271,10 +313,12 @@ class SacUpdater(_Updater):
     def __init__(self, actors, critics, critic_targets, *, mode: str = "single", discount: float = 0.99, tau: float = 0.005,
                  policy_update_freq: int = 3, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, max_action: float = 1.0, lr_a=3e-4,
                  lr_c=2e-4, grad_max_norm: float = 100.0, automatic_entropy_tuning: bool = False, target_entropy=None, sac_alpha: float = 0.05,
-                 batch_size: int = 256, nominal=None, generator: Optional[torch.Generator] = None, refill_noise: bool = True):
+                 batch_size: int = 256, nominal=None, generator: Optional[torch.Generator] = None, refill_noise: bool = True, noise_source: str = "torch",
+                 noise_seed: int = 0):
         super().__init__(actors, critics, critic_targets, mode=mode, discount=discount, tau=tau, policy_update_freq=policy_update_freq, lam_T=lam_T,
                          lam_S=lam_S, lam_M=lam_M, max_action=max_action, lr_a=lr_a, lr_c=lr_c, grad_max_norm=grad_max_norm,
-                         batch_size=batch_size, nominal=nominal, generator=generator, refill_noise=refill_noise)
+                         batch_size=batch_size, nominal=nominal, generator=generator, refill_noise=refill_noise, noise_source=noise_source,
+                         noise_seed=noise_seed)
         n, dev = self.n_agents, self.device
         if not 0.0 <= float(sac_alpha) < float("inf"):
             raise ValueError(f"SacUpdater: sac_alpha must be finite and >= 0, got {sac_alpha}")
@@ -338,13 +382,17 @@ class OffPolicyCollector:
     (use_explor_noise_decay off).  Deviation: the reference applies it before every step, here a launch flies T steps, so the value
     at the horizon's first step is held for the horizon.  Likewise the warm-up ends at a horizon's boundary.
     time_limit "solved" sets buffer.time_limit_rule.x_lim to the env's.  Nothing synchronises, and from the second call of each kind
-    nothing is allocated.  total_timesteps: env-steps collected per env so far, a host int."""
+    nothing is allocated.  total_timesteps: env-steps collected per env so far, a host int.
+    noise_source="device": the warm-up's actions are ONE uniform `noise_fill` launch in (-1, 1) under (noise_seed, draw = total_timesteps,
+    stream COLLECTOR_STREAM, which no updater's tensor has) instead of torch's three; it takes no generator."""
     ALGOS = ("td3", "sac")
 
     def __init__(self, env, buffer: ReplayBuffer, horizon: int, start_timesteps: int = 0, algo: str = "td3", explor_noise_std_init: float = 0.3,
                  explor_noise_std_min: float = 0.05, decay_timesteps: Optional[int] = None, time_limit: str = "solved",
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, noise_source: str = "torch", noise_seed: int = 0):
         what = "OffPolicyCollector"
+        self.noise_seed = _noise_source(what, noise_source, noise_seed, generator)
+        self.noise_source = noise_source
         if algo not in self.ALGOS:
             raise ValueError(f"{what}: algo must be one of {self.ALGOS}, got {algo!r}")
         if time_limit not in TIME_LIMITS:
@@ -406,7 +454,10 @@ class OffPolicyCollector:
             if cur is None:
                 raise ValueError("no current observation: call env.get_norm_error_state() or env.step() first")
             st.set_initial_obs(cur)
-            self.random_actions.uniform_(0.0, 1.0, generator=self.generator).mul_(2.0).sub_(1.0)
+            if self.noise_source == "device":   # one launch; the draw number is the env-steps collected so far
+                noise_fill([self.random_actions], seed=self.noise_seed, draw=self.total_timesteps, streams=[COLLECTOR_STREAM], kind="uniform")
+            else:
+                self.random_actions.uniform_(0.0, 1.0, generator=self.generator).mul_(2.0).sub_(1.0)
             env.rollout(self.random_actions, out=st.horizon())
             st.act_all.copy_(self.random_actions)   # (the given-actions rollout does not write the action rows)
         else:

@@ -474,6 +474,19 @@ def qr_replay_sample(out: torch.Tensor, n: int, seed: int, draw: int, state: Opt
     replay_sample(n, out.numel(), seed, draw, out, state=state, status=status)
 
 
+@torch.library.custom_op(f"{_NS}::qr_noise_fill", mutates_args=("tensors",))
+def qr_noise_fill(tensors: List[torch.Tensor], kinds: List[int], a: List[float], b: List[float], streams: List[int], seed: int, draw: int,
+                  draw_dev: Optional[torch.Tensor]) -> None:
+    """Fill float32 tensors with normal (kind 0) or uniform (kind 1) draws of the library's counter-based stream (qr_noise_fill), as
+    noise.noise_fill: one kind, a, b and stream id per tensor; seed and draw are passed as int64 here (0 <= seed, draw < 2^63).
+    draw_dev: an int64 device tensor of one element that is read as the draw number instead of `draw`, or None."""
+    from .noise import KINDS, noise_fill
+    _gpu(tensors[0])
+    if any(k not in (0, 1) for k in kinds):
+        raise ValueError("kinds are 0 (normal) or 1 (uniform)")
+    noise_fill(list(tensors), seed=seed, draw=draw, streams=list(streams), kind=[KINDS[k] for k in kinds], a=list(a), b=list(b), draw_dev=draw_dev)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_target", mutates_args=("y", "action_out", "logp_out"))
 def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
                   done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],

@@ -1044,6 +1044,41 @@ typedef struct QrReplaySample {
  * state pointer that is not 8-byte aligned or a status pointer that is not 4-byte aligned.  Nothing is launched or written on an error. */
 int qr_replay_sample(const QrReplaySample* sample, void* stream);
 
+/* ---- The library's noise source: every random tensor of a TD3 / SAC iteration in one launch ----
+ * Up to sixteen float32 tensors ("slots") filled from one counter-based stream, keyed by a 64-bit seed, a draw number — the replay
+ * buffer's minibatch counter, so that an iteration's noise is a function of its minibatch number — and a stream id per slot.
+ * Element e of a slot is position e % 4 of quad q = e / 4.  The quad's four 32-bit words are Philox4x32-10 under the key
+ * (seed_lo, seed_hi) with the counter
+ *     { (uint32)q, (uint32)(q >> 32) ^ (uint32)(draw >> 32), (uint32)draw, 0x80000000 | 0x40000000 | stream }
+ * (the rollout noise's counter layout with bit 30 set in its last word, which no other stream of the library sets together with
+ * the top bit).  QR_NOISE_NORMAL: words (0, 1) and (2, 3) each give a Box-Muller pair, in float32: u = fma(w >> 8, 2^-24, 2^-25),
+ * r = sqrt(-2 log u1), z = (r cos(2 pi u2), r sin(2 pi u2)) — the rollout noise's arithmetic; out[e] = fma(b, z, a), so a is the
+ * mean and b the standard deviation.  QR_NOISE_UNIFORM: s = fma(w >> 8, 2^-23, 2^-24 - 1), uniform on a grid of 2^24 points in
+ * (-1, 1); out[e] = fma(b, s, a).  A value depends on (seed, draw, stream, e, kind, a, b) alone: not on the slot's position, the
+ * other slots, the launch geometry or the pointer's alignment.  A (seed, draw, stream) triple must not be used for two tensors.
+ * draw_dev: NULL, or one device int64 that the launch READS as the draw number (it is never written), for callers whose counter
+ * lives on the device (QrReplaySample.state + 2); `draw` is then ignored. */
+#define QR_NOISE_MAX_SLOTS 16
+#define QR_NOISE_NORMAL  0   /* out[e] = fmaf(b, z, a), z standard normal: a = mean, b = std        */
+#define QR_NOISE_UNIFORM 1   /* out[e] = fmaf(b, s, a), s uniform in (-1, 1)                         */
+typedef struct QrNoiseSlot {
+  float* out;                     /* [count], written; 4-byte aligned (16-byte aligned: 16-byte stores) */
+  int64_t count;                  /* >= 1; the launch's quads, the sum of ceil(count / 4) over its slots, stay below 2^31 */
+  float a, b;
+  uint32_t kind, stream;          /* QR_NOISE_*; stream < 2^30 */
+} QrNoiseSlot;
+typedef struct QrNoiseFill {
+  QrNoiseSlot slot[QR_NOISE_MAX_SLOTS];
+  int32_t n_slots;                /* 1..16 */
+  uint64_t seed;
+  const int64_t* draw_dev;        /* NULL, or one device int64 that is READ as the draw number (never written) */
+  int64_t draw;                   /* the draw number where draw_dev is NULL: >= 0 */
+} QrNoiseFill;
+/* QR_E_NULL for a NULL struct; QR_E_SIZE for n_slots outside 1..16, a count < 1 or more than 2^31 - 1 quads in the launch, a kind outside {0, 1}, a stream >= 2^30,
+ * a non-finite a or b, or a negative draw where draw_dev is NULL; QR_E_NULL for a NULL out; QR_E_ALIGN for an out that is not 4-byte
+ * aligned or a draw_dev that is not 8-byte aligned.  One launch.  Nothing is launched or written on an error. */
+int qr_noise_fill(const QrNoiseFill* fill, void* stream);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -40,7 +40,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_twinq_target", "qr_ctde_sac_target", "qr_ctde_twinq_grad", "qr_ctde_twinq_workspace_bytes",
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
-           "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill")
+           "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill",
+           "qr_episode_scan", "qr_episode_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -381,6 +382,51 @@ def noise_fill_args(tensors, kinds, a, b, streams, *, seed, draw, draw_dev) -> Q
     return f
 
 
+# qr_episode_scan: the QR_EP_* indices of `last` / `total` (agent g's field at index + g), the flag bits of ep_flags
+EP_COUNT, EP_RETURN_SUM, EP_RETURN_SQ, EP_RETURN_MIN, EP_RETURN_MAX, EP_LENGTH_SUM, EP_LENGTH_MAX = 0, 1, 3, 5, 7, 9, 10
+EP_DONE, EP_TRUNCATED, EP_SOLVED, EP_EX_SUM, EP_EB1_SUM, EP_FIELDS, EP_STEPS_SEEN, EP_TOTAL_FIELDS = 11, 13, 14, 16, 17, 18, 18, 19
+EP_FLAG_DONE0, EP_FLAG_SOLVED0, EP_FLAG_TRUNCATED = 0x01, 0x10, 0x80
+EP_INDEX = {"COUNT": EP_COUNT, "RETURN_SUM": EP_RETURN_SUM, "RETURN_SQ": EP_RETURN_SQ, "RETURN_MIN": EP_RETURN_MIN, "RETURN_MAX": EP_RETURN_MAX,
+            "LENGTH_SUM": EP_LENGTH_SUM, "LENGTH_MAX": EP_LENGTH_MAX, "DONE": EP_DONE, "TRUNCATED": EP_TRUNCATED, "SOLVED": EP_SOLVED,
+            "EX_SUM": EP_EX_SUM, "EB1_SUM": EP_EB1_SUM, "FIELDS": EP_FIELDS, "STEPS_SEEN": EP_STEPS_SEEN, "TOTAL_FIELDS": EP_TOTAL_FIELDS}
+EP_MIN_FIELDS, EP_MAX_FIELDS = (5, 6), (7, 8, 10)   # the fields that fold as a minimum / a maximum; the others add
+
+
+def episode_empty() -> list:
+    """The QR_EP_TOTAL_FIELDS values of a `total` over no episodes (its first QR_EP_FIELDS: of a `last`)."""
+    inf = float("inf")
+    return [inf if k in EP_MIN_FIELDS else -inf if k in (7, 8) else 0.0 for k in range(EP_TOTAL_FIELDS)]
+
+
+class QrEpisodeScan(C.Structure):
+    _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p), ("final_obs0", C.c_void_p), ("final_obs1", C.c_void_p),
+                ("run_return", C.c_void_p), ("run_length", C.c_void_p), ("ep_return", C.c_void_p), ("ep_length", C.c_void_p),
+                ("ep_flags", C.c_void_p), ("ep_final_error", C.c_void_p), ("last", C.c_void_p), ("total", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_envs", C.c_int64), ("n_steps", C.c_int32), ("n_agents", C.c_int32),
+                ("d0", C.c_int32), ("d1", C.c_int32), ("record", C.c_int32), ("reserved0", C.c_int32),
+                ("x_lim", C.c_double), ("pos_tol", C.c_double), ("rot_tol", C.c_double)]
+
+
+def episode_scan_args(reward, done, truncated, final_obs, run_return, run_length, dense, last, total, workspace, *, n_steps, n_envs, n_agents,
+                      x_lim, pos_tol, rot_tol, record) -> QrEpisodeScan:
+    """QrEpisodeScan of one qr_episode_scan call; final_obs: None or one tensor per agent; dense: the four optional outputs (ep_return,
+    ep_length, ep_flags, ep_final_error), tensors or None."""
+    e = QrEpisodeScan()
+    e.reward, e.done, e.truncated = ptr(reward), ptr(done), ptr(truncated)
+    if final_obs is not None:
+        e.final_obs0, e.d0 = ptr(final_obs[0]), final_obs[0].shape[-1]
+        if n_agents == 2:
+            e.final_obs1, e.d1 = ptr(final_obs[1]), final_obs[1].shape[-1]
+    else:
+        e.d0, e.d1 = 3, 1
+    e.run_return, e.run_length, e.last, e.total = ptr(run_return), ptr(run_length), ptr(last), ptr(total)
+    e.ep_return, e.ep_length, e.ep_flags, e.ep_final_error = (ptr(t) for t in dense)
+    e.workspace, e.workspace_bytes = ptr(workspace), workspace.numel() * workspace.element_size()
+    e.n_envs, e.n_steps, e.n_agents, e.record, e.reserved0 = int(n_envs), int(n_steps), int(n_agents), int(bool(record)), 0
+    e.x_lim, e.pos_tol, e.rot_tol = float(x_lim), float(pos_tol), float(rot_tol)
+    return e
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -592,6 +638,10 @@ def load():
     lib.qr_replay_sample.argtypes = [P(QrReplaySample), C.c_void_p]
     lib.qr_noise_fill.restype = C.c_int
     lib.qr_noise_fill.argtypes = [P(QrNoiseFill), C.c_void_p]
+    lib.qr_episode_scan.restype = C.c_int
+    lib.qr_episode_scan.argtypes = [P(QrEpisodeScan), C.c_void_p]
+    lib.qr_episode_workspace_bytes.restype = C.c_int64
+    lib.qr_episode_workspace_bytes.argtypes = [C.c_int64]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -60,10 +60,12 @@
 //                  replay_advance_kernel (the opt-in device counters)
 //   qr_noise.h     the library's noise source (qr_noise_fill): up to sixteen normal or uniform tensors of a TD3 / SAC iteration from one
 //                  counter-based stream in one launch: noise_fill_kernel
+//   qr_episode.h   the training curve from a collected horizon's rows (qr_episode_scan): per-episode return, length, end flags and final
+//                  error, and their statistics: episode_scan_kernel, episode_reduce_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
-//                  sac_actor_launch (qr_sac_actor_grad and qr_ctde_sac_actor_grad), do_replay_add and do_replay_sample
+//                  sac_actor_launch (qr_sac_actor_grad and qr_ctde_sac_actor_grad), do_replay_add, do_replay_sample and do_episode_scan
 // Build switches (the product build sets none): QR_SPAN, the light clock build (Makefile: span-lib); QR_ONLY_KIND /
 // QR_ONLY_LAYOUT, developer builds with one env kind / one layout.  Settled A/Bs are constants in namespace qr (qr_step.h).
 #include <hip/hip_runtime.h>
@@ -90,6 +92,7 @@
 #include "qr_sac_actor.h"
 #include "qr_replay.h"
 #include "qr_noise.h"
+#include "qr_episode.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -793,9 +796,46 @@ static int do_noise_fill(const QrNoiseFill* n, void* stream) {
                      reinterpret_cast<hipStream_t>(stream), a);
   return (int)hipGetLastError();
 }
+
+static int do_episode_scan(const QrEpisodeScan* e, void* stream) {
+  if (!e) return QR_E_NULL;
+  const bool two = e->n_agents == 2;
+  if (e->n_steps < 1 || e->n_envs < 0 || e->n_envs > (1ll << 36) || e->n_agents < 1 || e->n_agents > 2 || e->reserved0 != 0) return QR_E_SIZE;
+  if (e->d0 < 3 || (two && e->d1 < 1)) return QR_E_SIZE;
+  const auto finite_from = [](double v, bool zero) { return (zero ? v >= 0.0 : v > 0.0) && v <= 1.7e308; };   // (a NaN fails)
+  if (!finite_from(e->pos_tol, true) || !finite_from(e->rot_tol, true) || !finite_from(e->x_lim, false)) return QR_E_SIZE;
+  const int64_t tiles = e->n_envs > 0 ? (e->n_envs + 63) / 64 : 1;
+  if (e->workspace_bytes < tiles * kEpK * (int64_t)sizeof(double)) return QR_E_SIZE;
+  if (!e->reward || !e->done || !e->truncated || !e->run_return || !e->run_length || !e->last || !e->total || !e->workspace) return QR_E_NULL;
+  if (e->final_obs0 ? (two && !e->final_obs1) : e->ep_final_error != nullptr) return QR_E_NULL;
+  uintptr_t b4 = reinterpret_cast<uintptr_t>(e->reward) | reinterpret_cast<uintptr_t>(e->final_obs0) | reinterpret_cast<uintptr_t>(e->run_length) |
+                 reinterpret_cast<uintptr_t>(e->ep_length);
+  if (two && e->final_obs0) b4 |= reinterpret_cast<uintptr_t>(e->final_obs1);
+  const uintptr_t b8 = reinterpret_cast<uintptr_t>(e->run_return) | reinterpret_cast<uintptr_t>(e->ep_return) | reinterpret_cast<uintptr_t>(e->last) |
+                       reinterpret_cast<uintptr_t>(e->total) | reinterpret_cast<uintptr_t>(e->workspace) | (two ? reinterpret_cast<uintptr_t>(e->reward) : 0);
+  if ((b4 & 3u) || (b8 & 7u) || (reinterpret_cast<uintptr_t>(e->ep_final_error) & 15u)) return QR_E_ALIGN;
+  if (e->n_envs == 0) return 0;
+  const EpisodeScanArgs a{e->reward, e->done, e->truncated, e->final_obs0, e->final_obs0 && two ? e->final_obs1 : nullptr, e->run_return, e->run_length,
+                          e->ep_return, e->ep_length, e->ep_flags, e->ep_final_error, static_cast<double*>(e->workspace), e->n_envs, e->n_steps,
+                          e->d0, two ? e->d1 : 0, e->record != 0 ? 1 : 0, e->x_lim, e->pos_tol, e->rot_tol};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (two) hipLaunchKernelGGL(episode_scan_kernel<2>, dim3((unsigned)tiles), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(episode_scan_kernel<1>, dim3((unsigned)tiles), dim3(64), 0, s, a);
+  if (int rc = (int)hipGetLastError()) return rc;
+  const EpisodeReduceArgs o{a.partials, e->last, e->total, (int32_t)tiles, e->n_steps, a.record};
+  hipLaunchKernelGGL(episode_reduce_kernel, dim3(1), dim3(256), 0, s, o);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_episode_scan(const QrEpisodeScan* a, void* stream) { return qr::do_episode_scan(a, stream); }
+
+int64_t qr_episode_workspace_bytes(int64_t n_envs) {
+  if (n_envs < 0) return QR_E_SIZE;
+  return (n_envs > 0 ? (n_envs + 63) / 64 : 1) * qr::kEpK * (int64_t)sizeof(double);
+}
 
 int qr_noise_fill(const QrNoiseFill* fill, void* stream) { return qr::do_noise_fill(fill, stream); }
 

@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .episodes import EpisodeTracker
 from .noise import check_seed, noise_fill
 from .optim import PolyakAdamW
 from .sac import sac_actor_loss, sac_actor_loss_ctde, sac_critic_loss, sac_critic_loss_ctde
@@ -384,12 +385,15 @@ class OffPolicyCollector:
     time_limit "solved" sets buffer.time_limit_rule.x_lim to the env's.  Nothing synchronises, and from the second call of each kind
     nothing is allocated.  total_timesteps: env-steps collected per env so far, a host int.
     noise_source="device": the warm-up's actions are ONE uniform `noise_fill` launch in (-1, 1) under (noise_seed, draw = total_timesteps,
-    stream COLLECTOR_STREAM, which no updater's tensor has) instead of torch's three; it takes no generator."""
+    stream COLLECTOR_STREAM, which no updater's tensor has) instead of torch's three; it takes no generator.
+    track_episodes=True: the collector owns `episodes`, an `EpisodeTracker` with the buffer's time-limit rule (x_lim the env's), and
+    every `collect` ends with `episodes.update(storage, record=total_timesteps >= start_timesteps)`, total_timesteps read before the
+    horizon is counted: warm-up horizons advance the carries and are not recorded (main.py:218).  False: `episodes` is None."""
     ALGOS = ("td3", "sac")
 
     def __init__(self, env, buffer: ReplayBuffer, horizon: int, start_timesteps: int = 0, algo: str = "td3", explor_noise_std_init: float = 0.3,
                  explor_noise_std_min: float = 0.05, decay_timesteps: Optional[int] = None, time_limit: str = "solved",
-                 generator: Optional[torch.Generator] = None, noise_source: str = "torch", noise_seed: int = 0):
+                 generator: Optional[torch.Generator] = None, noise_source: str = "torch", noise_seed: int = 0, track_episodes: bool = False):
         what = "OffPolicyCollector"
         self.noise_seed = _noise_source(what, noise_source, noise_seed, generator)
         self.noise_source = noise_source
@@ -424,6 +428,8 @@ class OffPolicyCollector:
             buffer.time_limit_rule = buffer.time_limit_rule._replace(x_lim=float(env.x_lim))
         self.storage = RolloutStorage(env, self.T, action_dims=buffer.action_dims)
         self.random_actions = torch.empty(self.T, env.num_envs, env.action_dim, dtype=torch.float32, device=env.device) if self.start_timesteps else None
+        # the training curve (main.py:212-235): None unless asked for — then one more C call per horizon, behind the append
+        self.episodes = EpisodeTracker(self.storage, rule=buffer.time_limit_rule._replace(x_lim=float(env.x_lim))) if track_episodes else None
 
     @staticmethod
     def decay(std: float, noise_std_decay: float, std_min: float, steps: int = 1) -> float:
@@ -466,6 +472,8 @@ class OffPolicyCollector:
                     a.log_std.fill_(math.log(self.explor_noise_std))
             st.collect(env, actors, **kw)
         self.buffer.append(st, time_limit=self.time_limit)
+        if self.episodes is not None:   # (total_timesteps is still the count before this horizon: warm-up horizons are not recorded)
+            self.episodes.update(st, record=self.total_timesteps >= self.start_timesteps)
         self.explor_noise_std = self.decay(self.explor_noise_std, self.noise_std_decay, self.std_min, self.T)
         self.total_timesteps += self.T
         return st

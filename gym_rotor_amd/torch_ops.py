@@ -487,6 +487,23 @@ def qr_noise_fill(tensors: List[torch.Tensor], kinds: List[int], a: List[float],
     noise_fill(list(tensors), seed=seed, draw=draw, streams=list(streams), kind=[KINDS[k] for k in kinds], a=list(a), b=list(b), draw_dev=draw_dev)
 
 
+@torch.library.custom_op(f"{_NS}::qr_episode_scan", mutates_args=("run_return", "run_length", "last", "total", "ep_return", "ep_length", "ep_flags",
+                                                                  "ep_final_error", "workspace"))
+def qr_episode_scan(reward: torch.Tensor, done: torch.Tensor, truncated: torch.Tensor, final_obs: List[torch.Tensor], run_return: torch.Tensor,
+                    run_length: torch.Tensor, last: torch.Tensor, total: torch.Tensor, ep_return: Optional[torch.Tensor],
+                    ep_length: Optional[torch.Tensor], ep_flags: Optional[torch.Tensor], ep_final_error: Optional[torch.Tensor],
+                    workspace: torch.Tensor, x_lim: float, pos_tol: float, rot_tol: float, record: bool) -> None:
+    """One collected horizon's rows into per-episode records and statistics in one C call (qr_episode_scan), as episodes.episode_scan:
+    final_obs one [T, N, D_k] tensor per agent, or an empty list; the four dense outputs optional; workspace float64
+    [episodes.episode_workspace_numel(N)]."""
+    from .episodes import episode_scan
+    from .td3 import TimeLimitRule
+    _gpu(reward)
+    episode_scan(reward, done, truncated, run_return, run_length, last, total, final_obs=list(final_obs) if final_obs else None,
+                 rule=TimeLimitRule(x_lim, pos_tol, rot_tol), record=record, ep_return=ep_return, ep_length=ep_length, ep_flags=ep_flags,
+                 ep_final_error=ep_final_error, workspace=workspace)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_target", mutates_args=("y", "action_out", "logp_out"))
 def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
                   done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],

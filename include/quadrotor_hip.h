@@ -1079,6 +1079,88 @@ typedef struct QrNoiseFill {
  * aligned or a draw_dev that is not 8-byte aligned.  One launch.  Nothing is launched or written on an error. */
 int qr_noise_fill(const QrNoiseFill* fill, void* stream);
 
+/* ---- Per-episode training statistics from a collected horizon (the reference's training curve, main.py:132-137, 180, 212-235) ----
+ * A scan over the [n_steps][n_envs] rows a horizon has already written (qr_rollout / qr_rollout_actor with QR_FLAG_AUTO_RESET): one lane
+ * per env walks t = 0 .. n_steps - 1 with two carries per env that live on the device across calls,
+ *     run_return[n][g] += (double)reward[t][n][g]        run_length[n] += 1           (the terminal step counts)
+ * and the episode of env n ENDS in step t when any agent's done[t][n][.] or truncated[t][n] is set (the rule of qr_replay_add's obs_next
+ * and of qr_critic_next_values).  At an end the lane forms the episode's record and clears the env's carries:
+ *     return[g]  = run_return[n][g]: float64, the sum of the float32 rewards, NOT rounded.  Deliberate deviation, the one
+ *                  QrEvalOut.episode_return documents: the reference rounds its running sum to 4 decimals at every step (main.py:180).
+ *     length     = run_length[n]
+ *     flags      = QR_EP_FLAG_DONE0 << g where agent g's done is set | QR_EP_FLAG_TRUNCATED where truncated is set
+ *                | QR_EP_FLAG_SOLVED0 << g where truncated is set and agent g is "solved" (main.py:169-173, qr_replay_add_rule's rule):
+ *                  agent 0: fabs(ex[c]) <= pos_tol for c = 0, 1, 2 and reward[t][n][0] != -1.0f; agent 1: fabs(eb1) <= rot_tol and
+ *                  reward[t][n][1] != -1.0f
+ *     ex[c]      = (double)final_obs0[t][n][c] * x_lim,  eb1 = (double)final_obs1[t][n][0] * pi (pi the double nearest pi; 0 with one
+ *                  agent): qr_replay_add_rule's expressions, compared in double on the float32 words; stored as (float)
+ * final_obs0 NULL: ex, eb1 and the solved bits are zero (final_obs1 is then not read), and ep_final_error must be NULL.
+ * Dense per-transition outputs, each may be NULL; a row where no episode ended holds zeros, so ep_length > 0 is the mask of the ends and
+ * its non-zeros in (t, n) order are the reference's log lines in the reference's order:
+ *     ep_return [n_steps][n_envs][n_agents] float64   ep_length [n_steps][n_envs] int32   ep_flags [n_steps][n_envs] uint8
+ *     ep_final_error [n_steps][n_envs][4] float32: ex (3), eb1
+ * Statistics over the episodes that ended in this launch: QR_EP_FIELDS float64 fields, agent g's at index + g (one agent: agent 1's
+ * fields stay empty).  An empty field is +inf for a minimum, -inf for a return's maximum, 0 elsewhere. */
+#define QR_EP_COUNT        0   /* episodes */
+#define QR_EP_RETURN_SUM   1   /* +g: sum of returns */
+#define QR_EP_RETURN_SQ    3   /* +g: sum of squared returns */
+#define QR_EP_RETURN_MIN   5   /* +g */
+#define QR_EP_RETURN_MAX   7   /* +g */
+#define QR_EP_LENGTH_SUM   9
+#define QR_EP_LENGTH_MAX  10
+#define QR_EP_DONE        11   /* +g: episodes whose last step has agent g's done set */
+#define QR_EP_TRUNCATED   13   /* episodes whose last step has truncated set */
+#define QR_EP_SOLVED      14   /* +g: episodes with agent g's solved bit */
+#define QR_EP_EX_SUM      16   /* sum of max_c |ex[c]| (double) */
+#define QR_EP_EB1_SUM     17   /* sum of |eb1| (double) */
+#define QR_EP_FIELDS      18   /* K: the length of `last` and of a workgroup's partial vector */
+#define QR_EP_STEPS_SEEN  18   /* `total` only: env-steps per env scanned so far; advances by n_steps with every call */
+#define QR_EP_TOTAL_FIELDS 19  /* the length of `total` */
+#define QR_EP_FLAG_DONE0      0x01u   /* << g */
+#define QR_EP_FLAG_SOLVED0    0x10u   /* << g */
+#define QR_EP_FLAG_TRUNCATED  0x80u
+/* Each 64-env workgroup reduces its lanes' fields with a fixed shuffle tree into one vector of `workspace`; a second launch of one
+ * workgroup folds the vectors in workgroup-index order (256 strided slices, then a tree) — no floating-point atomics, and a result that
+ * does not depend on which workgroup finished first — into
+ *     last[QR_EP_FIELDS]         this call's statistics
+ *     total[QR_EP_TOTAL_FIELDS]  since the caller zeroed it (an empty vector: the fields' empty values, steps_seen 0): sums and counts
+ *                                add, minima and maxima fold.  Both are additive / foldable over env shards in the same way.
+ * record = 0 (main.py:218: episodes that end during the warm-up are not logged): the carries advance and are cleared as ever and the
+ * dense rows are written, `last` is an empty vector and `total` keeps every field but steps_seen. */
+typedef struct QrEpisodeScan {
+  const float*   reward;          /* [n_steps][n_envs][n_agents]; two agents: 8-byte aligned */
+  const uint8_t* done;            /* [n_steps][n_envs][n_agents] bool bytes */
+  const uint8_t* truncated;       /* [n_steps][n_envs] bool bytes */
+  const float*   final_obs0;      /* [n_steps][n_envs][d0] or NULL; read on the rows where an episode ended only */
+  const float*   final_obs1;      /* [n_steps][n_envs][d1]; required with two agents where final_obs0 is given */
+  double*        run_return;      /* [n_envs][n_agents], read and written */
+  int32_t*       run_length;      /* [n_envs], read and written */
+  double*        ep_return;       /* the four dense outputs, each may be NULL */
+  int32_t*       ep_length;
+  uint8_t*       ep_flags;
+  float*         ep_final_error;  /* 16-byte aligned */
+  double*        last;            /* [QR_EP_FIELDS], written */
+  double*        total;           /* [QR_EP_TOTAL_FIELDS], read and written */
+  void*          workspace;       int64_t workspace_bytes;   /* >= qr_episode_workspace_bytes(n_envs); 8-byte aligned */
+  int64_t        n_envs;
+  int32_t        n_steps, n_agents;   /* n_agents 1 or 2 */
+  int32_t        d0, d1;          /* row widths of final_obs0 / final_obs1: d0 >= 3, d1 >= 1 (two agents) */
+  int32_t        record, reserved0;   /* reserved0 must be 0 */
+  double         x_lim;           /* the env's position limit (QrCoeffs.x_lim), finite and > 0 */
+  double         pos_tol, rot_tol;/* [m], [rad]; the reference's are 0.03 and 0.03; finite, >= 0 */
+} QrEpisodeScan;
+/* Two launches on `stream` behind one call; no host synchronisation, no allocation.  In this order, all before any launch: QR_E_NULL for
+ * a NULL struct; QR_E_SIZE for n_steps < 1, n_envs < 0 or > 2^36, n_agents outside 1..2, reserved0 != 0, d0 < 3, d1 < 1 with two agents, an x_lim
+ * that is not finite and > 0, a negative or non-finite tolerance or a workspace that is too small; QR_E_NULL for a NULL reward, done,
+ * truncated, run_return, run_length, last, total or workspace, a NULL final_obs1 with two agents where final_obs0 is given, or an
+ * ep_final_error where final_obs0 is NULL; QR_E_ALIGN for a float or int32 pointer that is not 4-byte aligned, a double or workspace
+ * pointer that is not 8-byte aligned, a two-agent reward that is not 8-byte aligned or an ep_final_error that is not 16-byte aligned.
+ * n_envs = 0 launches nothing. */
+int     qr_episode_scan(const QrEpisodeScan* a, void* stream);
+/* Bytes of workspace qr_episode_scan needs: one vector of QR_EP_FIELDS doubles per 64-env workgroup (at least one); QR_E_SIZE (< 0)
+ * for n_envs < 0. */
+int64_t qr_episode_workspace_bytes(int64_t n_envs);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

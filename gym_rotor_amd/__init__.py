@@ -9,7 +9,7 @@ from .spaces import Box  # noqa: F401
 from .sharding import shard_range, make_sharded_env, all_gather_rows  # noqa: F401
 from .vec_env import CapturedStep, QuadVecEnv, as_gymnasium_vector_env  # noqa: F401
 from .compat import QuadEnv, CoupledWrapper, DecoupledWrapper  # noqa: F401
-from .rollout import RolloutStorage  # noqa: F401
+from .rollout import RolloutStorage, gae_rule, gae_rule_workspace_numel  # noqa: F401
 from .policy import ActorParams, ActorPopulation, CriticParams, QCriticParams, actor_loss, critic_loss, ppo_actor_grad, ppo_critic_grad, random_actors  # noqa: F401
 from .optim import DeviceAdamW, PolyakAdamW, PpoUpdater, adamw_polyak_step, adamw_step, minibatch_slices  # noqa: F401
 from .td3 import ReplayBuffer, dpg_actor_grad, soft_update, td3_actor_loss, td3_critic_loss, td3_target, twinq_grad  # noqa: F401
@@ -22,6 +22,7 @@ from .sac import sac_actor_grad_ctde, sac_actor_loss_ctde, sac_actor_workspace_b
 from .noise import DeviceNoise, noise_fill  # noqa: F401
 from .episodes import EpisodeTracker, episode_scan, episode_workspace_numel  # noqa: F401
 from .offpolicy import OffPolicyCollector, SacUpdater, Td3Updater  # noqa: F401
+from .ppo import PpoCollector  # noqa: F401
 from .evaluate import EvalResult, PopulationResult, evaluate_policy, evaluate_population  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)
 

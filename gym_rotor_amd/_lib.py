@@ -41,7 +41,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
            "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill",
-           "qr_episode_scan", "qr_episode_workspace_bytes")
+           "qr_episode_scan", "qr_episode_workspace_bytes", "qr_gae_rule", "qr_gae_rule_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -427,6 +427,39 @@ def episode_scan_args(reward, done, truncated, final_obs, run_return, run_length
     return e
 
 
+class QrGaeRule(C.Structure):
+    _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("truncated", C.c_void_p), ("term_obs0", C.c_void_p), ("term_obs1", C.c_void_p),
+                ("value", C.c_void_p), ("next_value", C.c_void_p), ("advantage", C.c_void_p), ("td_target", C.c_void_p), ("done_eff", C.c_void_p),
+                ("stats", C.c_void_p), ("normalized", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("n_envs", C.c_int64), ("n_steps", C.c_int32), ("n_agents", C.c_int32), ("d0", C.c_int32), ("d1", C.c_int32),
+                ("rule", C.c_int32), ("reserved0", C.c_int32), ("gamma", C.c_float), ("lam", C.c_float),
+                ("x_lim", C.c_double), ("pos_tol", C.c_double), ("rot_tol", C.c_double), ("norm_eps", C.c_double)]
+
+
+GAE_NORM_EPS = 1e-4   # ppo.py:146
+
+
+def gae_rule_args(reward, done, truncated, term_obs, value, next_value, advantage, td_target, done_eff, stats, normalized, workspace, *,
+                  n_steps, n_envs, n_agents, gamma, lam, rule, norm_eps=GAE_NORM_EPS) -> QrGaeRule:
+    """QrGaeRule of one qr_gae_rule call; term_obs: None or one tensor per agent (the transitions' obs_next rows); rule: None (each
+    agent's own done flag) or the time-limit rule's three numbers (x_lim, pos_tol, rot_tol); next_value, done_eff, stats, normalized,
+    workspace: tensors or None."""
+    e = QrGaeRule()
+    e.reward, e.done, e.truncated, e.value, e.next_value = ptr(reward), ptr(done), ptr(truncated), ptr(value), ptr(next_value)
+    if term_obs is not None:
+        e.term_obs0, e.d0 = ptr(term_obs[0]), term_obs[0].shape[-1]
+        if n_agents == 2:
+            e.term_obs1, e.d1 = ptr(term_obs[1]), term_obs[1].shape[-1]
+    e.advantage, e.td_target, e.done_eff, e.stats, e.normalized = ptr(advantage), ptr(td_target), ptr(done_eff), ptr(stats), ptr(normalized)
+    e.workspace, e.workspace_bytes = ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size()
+    e.n_envs, e.n_steps, e.n_agents, e.reserved0 = int(n_envs), int(n_steps), int(n_agents), 0
+    e.gamma, e.lam, e.norm_eps = float(gamma), float(lam), float(norm_eps)
+    e.rule = 0 if rule is None else 1
+    if rule is not None:
+        e.x_lim, e.pos_tol, e.rot_tol = (float(v) for v in rule)
+    return e
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -642,6 +675,10 @@ def load():
     lib.qr_episode_scan.argtypes = [P(QrEpisodeScan), C.c_void_p]
     lib.qr_episode_workspace_bytes.restype = C.c_int64
     lib.qr_episode_workspace_bytes.argtypes = [C.c_int64]
+    lib.qr_gae_rule.restype = C.c_int
+    lib.qr_gae_rule.argtypes = [P(QrGaeRule), C.c_void_p]
+    lib.qr_gae_rule_workspace_bytes.restype = C.c_int64
+    lib.qr_gae_rule_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

@@ -62,6 +62,8 @@
 //                  counter-based stream in one launch: noise_fill_kernel
 //   qr_episode.h   the training curve from a collected horizon's rows (qr_episode_scan): per-episode return, length, end flags and final
 //                  error, and their statistics: episode_scan_kernel, episode_reduce_kernel
+//   qr_gae.h       PPO's advantages over the done flag the reference stores at the time limit, their per-agent statistics and their
+//                  normalisation (qr_gae_rule): gae_rule_kernel, gae_fold_kernel, gae_normalize_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
@@ -93,6 +95,7 @@
 #include "qr_replay.h"
 #include "qr_noise.h"
 #include "qr_episode.h"
+#include "qr_gae.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -826,9 +829,72 @@ static int do_episode_scan(const QrEpisodeScan* e, void* stream) {
   hipLaunchKernelGGL(episode_reduce_kernel, dim3(1), dim3(256), 0, s, o);
   return (int)hipGetLastError();
 }
+
+static int64_t gae_rule_tiles(int64_t n_envs, int32_t n_agents) {
+  const int64_t m = n_envs * n_agents;
+  return m > 0 ? (m + 63) / 64 : 1;
+}
+
+static int do_gae_rule(const QrGaeRule* e, void* stream) {
+  if (!e) return QR_E_NULL;
+  const bool two = e->n_agents == 2;
+  if (e->n_steps < 1 || e->n_envs < 0 || e->n_envs > (1ll << 35) || e->n_agents < 1 || e->n_agents > 2 || e->reserved0 != 0) return QR_E_SIZE;
+  if (e->rule < 0 || e->rule > 1) return QR_E_SIZE;
+  const auto finite_from = [](double v, bool zero) { return (zero ? v >= 0.0 : v > 0.0) && v <= 1.7e308; };   // (a NaN fails)
+  if (e->rule) {
+    if (e->d0 < 3 || (two && e->d1 < 1)) return QR_E_SIZE;
+    if (!finite_from(e->pos_tol, true) || !finite_from(e->rot_tol, true) || !finite_from(e->x_lim, false)) return QR_E_SIZE;
+  }
+  if (e->normalized && (!finite_from(e->norm_eps, true) || (int64_t)e->n_steps * e->n_envs < 2)) return QR_E_SIZE;
+  const int64_t tiles = gae_rule_tiles(e->n_envs, e->n_agents);
+  const int fields = 2 * e->n_agents;
+  if (e->stats && e->workspace_bytes < tiles * fields * (int64_t)sizeof(double)) return QR_E_SIZE;
+  if (!e->reward || !e->done || !e->value || !e->advantage || !e->td_target) return QR_E_NULL;
+  if (e->rule && (!e->truncated || !e->term_obs0 || (two && !e->term_obs1))) return QR_E_NULL;
+  if ((e->normalized && !e->stats) || (e->stats && !e->workspace)) return QR_E_NULL;
+  uintptr_t b4 = reinterpret_cast<uintptr_t>(e->reward) | reinterpret_cast<uintptr_t>(e->value) | reinterpret_cast<uintptr_t>(e->next_value) |
+                 reinterpret_cast<uintptr_t>(e->advantage) | reinterpret_cast<uintptr_t>(e->td_target) | reinterpret_cast<uintptr_t>(e->normalized);
+  if (e->rule) b4 |= reinterpret_cast<uintptr_t>(e->term_obs0) | (two ? reinterpret_cast<uintptr_t>(e->term_obs1) : 0);
+  uintptr_t b8 = reinterpret_cast<uintptr_t>(e->stats);
+  if (e->stats) b8 |= reinterpret_cast<uintptr_t>(e->workspace);
+  if ((b4 & 3u) || (b8 & 7u)) return QR_E_ALIGN;
+  if (e->n_envs == 0) return 0;
+  const GaeRuleArgs g{e->reward, e->done, e->rule ? e->truncated : nullptr, e->rule ? e->term_obs0 : nullptr, e->rule && two ? e->term_obs1 : nullptr,
+                      e->value, e->next_value, e->advantage, e->td_target, e->done_eff, e->stats ? static_cast<double*>(e->workspace) : nullptr,
+                      e->n_envs, e->n_steps, e->d0, two ? e->d1 : 0, e->rule, e->gamma, e->lam, e->x_lim, e->pos_tol, e->rot_tol};
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (two) hipLaunchKernelGGL(gae_rule_kernel<2>, dim3((unsigned)tiles), dim3(64), 0, s, g);
+  else hipLaunchKernelGGL(gae_rule_kernel<1>, dim3((unsigned)tiles), dim3(64), 0, s, g);
+  if (int rc = (int)hipGetLastError()) return rc;
+  if (!e->stats) return 0;
+  const GaeFoldArgs o{g.partials, e->stats, (int32_t)tiles, fields, (double)((int64_t)e->n_steps * e->n_envs)};
+  hipLaunchKernelGGL(gae_fold_kernel, dim3(1), dim3(256), 0, s, o);
+  if (int rc = (int)hipGetLastError()) return rc;
+  if (!e->normalized) return 0;
+  const GaeNormArgs q{e->advantage, e->stats, e->normalized, (int64_t)e->n_steps * e->n_envs * e->n_agents, e->norm_eps};
+  const bool vec = ((reinterpret_cast<uintptr_t>(e->advantage) | reinterpret_cast<uintptr_t>(e->normalized)) & 15u) == 0;
+  const int64_t per = vec ? 1024 : 256;   // elements a workgroup takes per sweep
+  const int64_t blocks = (q.count + per - 1) / per;
+  const dim3 grid((unsigned)(blocks < kGaeNormGrid ? blocks : kGaeNormGrid));
+  if (two) {
+    if (vec) hipLaunchKernelGGL((gae_normalize_kernel<2, true>), grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((gae_normalize_kernel<2, false>), grid, dim3(256), 0, s, q);
+  } else {
+    if (vec) hipLaunchKernelGGL((gae_normalize_kernel<1, true>), grid, dim3(256), 0, s, q);
+    else hipLaunchKernelGGL((gae_normalize_kernel<1, false>), grid, dim3(256), 0, s, q);
+  }
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_gae_rule(const QrGaeRule* a, void* stream) { return qr::do_gae_rule(a, stream); }
+
+int64_t qr_gae_rule_workspace_bytes(int64_t n_envs, int32_t n_agents) {
+  if (n_envs < 0 || n_agents < 1 || n_agents > 2) return QR_E_SIZE;
+  return qr::gae_rule_tiles(n_envs, n_agents) * 2 * n_agents * (int64_t)sizeof(double);
+}
 
 int qr_episode_scan(const QrEpisodeScan* a, void* stream) { return qr::do_episode_scan(a, stream); }
 

@@ -13,11 +13,97 @@ all-reduced over the env shards (RCCL when launched under torchrun; gloo in the 
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import List, Optional
 
 import torch
 
 from . import _lib
+from .td3 import TIME_LIMITS, TimeLimitRule
+
+
+def gae_rule_workspace_numel(n_envs: int, n_agents: int) -> int:
+    """float64 elements of workspace `gae_rule` needs for its stats: 2 * n_agents per 64-column workgroup."""
+    return max(1, (int(n_envs) * int(n_agents) + 63) // 64) * 2 * int(n_agents)
+
+
+def gae_rule(reward, done, value, advantage, td_target, *, gamma: float = 0.99, lam: float = 0.9, next_value=None, truncated=None, term_obs=None,
+             rule=None, done_eff=None, stats=None, normalized=None, workspace=None, norm_eps: float = _lib.GAE_NORM_EPS):
+    """ppo.py:134-146 over the done flag the reference stores, in one C call (qr_gae_rule; up to three launches, no synchronisation).
+
+    reward [T, N, n_agents] float32, done [T, N, n_agents] bool, value [T + 1, N, n_agents] float32 (row T: the bootstrap; [T, ...] will
+    do with next_value), next_value None or [T, N, n_agents] float32: as `RolloutStorage` holds them and as qr_gae reads them.
+    advantage, td_target [T, N, n_agents] float32: written.  rule: None — each agent's own flag — or a `TimeLimitRule`
+    (x_lim, pos_tol, rot_tol): on transitions whose `truncated` [T, N] is set the flag is main.py:169-173's, "the error in obs_next
+    is within tolerance and the reward is not -1", read from term_obs — per agent the [T, N, D_k] rows that hold obs_next on those
+    transitions (`storage.final_obs`, or `[o[1:] for o in storage.obs]`).  done_eff [T, N, n_agents] bool or uint8: optional, the flag
+    the scan used.  stats float64 [n_agents, 3]: optional, per agent sum, sum of squares and count of its advantages
+    (`RolloutStorage.normalize`'s input).  normalized [T, N, n_agents] float32: optional, (adv - mean) / (std + norm_eps) with torch's
+    unbiased std; needs stats and T * N >= 2.  workspace: float64, `gae_rule_workspace_numel(N, n_agents)` elements (None with stats:
+    made here).  Every check raises ValueError before a launch.  Returns (advantage, td_target, stats)."""
+    what = "gae_rule"
+    if not isinstance(reward, torch.Tensor) or reward.dim() != 3 or reward.dtype != torch.float32 or not reward.is_contiguous():
+        raise ValueError(f"{what}: reward must be a contiguous float32 [T, N, n_agents] tensor")
+    T, N, na = reward.shape
+    dev = reward.device
+    if na not in (1, 2) or T < 1:
+        raise ValueError(f"{what}: one or two agents and T >= 1, got reward of shape {tuple(reward.shape)}")
+
+    def need(x, shape, dtypes, name):
+        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
+        if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.device != dev or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtypes[0]} {shape} tensor on {dev}")
+    need(done, (T, N, na), (torch.bool, torch.uint8), "done")
+    if next_value is None:
+        need(value, (T + 1, N, na), torch.float32, "value")
+    else:
+        if not isinstance(value, torch.Tensor) or value.dim() != 3 or value.shape[0] not in (T, T + 1):
+            raise ValueError(f"{what}: value must be [{T} or {T + 1}, {N}, {na}]")
+        need(value, (value.shape[0], N, na), torch.float32, "value")
+        need(next_value, (T, N, na), torch.float32, "next_value")
+    need(advantage, (T, N, na), torch.float32, "advantage")
+    need(td_target, (T, N, na), torch.float32, "td_target")
+    if rule is not None:
+        rule = TimeLimitRule(*rule).check(what)
+        if truncated is None or term_obs is None:
+            raise ValueError(f"{what}: the time-limit rule needs truncated and term_obs, the rows that hold obs_next at the time limit")
+        need(truncated, (T, N), (torch.bool, torch.uint8), "truncated")
+        term_obs = [term_obs] if isinstance(term_obs, torch.Tensor) else list(term_obs)
+        if len(term_obs) != na:
+            raise ValueError(f"{what}: term_obs is one [T, N, D_k] tensor per agent ({na}), got {len(term_obs)}")
+        for k, f in enumerate(term_obs):
+            if not isinstance(f, torch.Tensor) or f.dim() != 3 or f.shape[-1] < (3 if k == 0 else 1):
+                raise ValueError(f"{what}: term_obs[{k}] must be [T, N, D] with D >= {3 if k == 0 else 1} (ex is three words, eb1 one)")
+            need(f, (T, N, f.shape[-1]), torch.float32, f"term_obs[{k}]")
+    else:
+        truncated = term_obs = None
+    if done_eff is not None:
+        need(done_eff, (T, N, na), (torch.bool, torch.uint8), "done_eff")
+    if normalized is not None:
+        need(normalized, (T, N, na), torch.float32, "normalized")
+        if stats is None:
+            raise ValueError(f"{what}: normalized needs stats")
+        if T * N < 2:
+            raise ValueError(f"{what}: normalized needs at least two transitions per agent (the unbiased std), got {T} x {N}")
+        if not (float(norm_eps) >= 0.0 and float(norm_eps) < float("inf")):
+            raise ValueError(f"{what}: norm_eps must be finite and >= 0, got {norm_eps}")
+    if stats is not None:
+        need(stats, (na, 3), torch.float64, "stats")
+        numel = gae_rule_workspace_numel(N, na)
+        if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.device != dev or
+                                      workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < numel):
+            raise ValueError(f"{what}: workspace must be a contiguous float64 tensor of at least {numel} elements on {dev}")
+    if dev.type != "cuda":
+        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    if stats is not None and workspace is None:
+        workspace = torch.empty(gae_rule_workspace_numel(N, na), dtype=torch.float64, device=dev)
+    e = _lib.gae_rule_args(reward, done, truncated, term_obs, value, next_value, advantage, td_target, done_eff, stats, normalized,
+                           workspace if stats is not None else None, n_steps=T, n_envs=N, n_agents=na, gamma=gamma, lam=lam, rule=rule,
+                           norm_eps=norm_eps)
+    with torch.cuda.device(dev):
+        rc = _lib.load().qr_gae_rule(C.byref(e), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_gae_rule")
+    return advantage, td_target, stats
 
 
 class RolloutStorage:
@@ -69,6 +155,8 @@ class RolloutStorage:
         self.value = torch.zeros(T + 1, N, self.n_agents, **f32)
         self.advantage = torch.zeros(T, N, self.n_agents, **f32)
         self.td_target = torch.zeros(T, N, self.n_agents, **f32)
+        self.env_x_lim = getattr(env, "x_lim", None)   # the default x_lim of compute_gae(time_limit="solved")
+        self.gae_stats = self._gae_workspace = self.advantage_normalized = self.done_eff = None   # compute_gae's, made at first use
         self._lib = _lib.load()
         self._ppo_workspace = {}   # (agent, B, max_workgroups) -> workspace of actor_grad
         self._critic_workspace = {}   # (agent, B, max_workgroups) -> workspace of critic_grad
@@ -214,13 +302,30 @@ class RolloutStorage:
             self.value[t].copy_(value.reshape(self.N, self.n_agents))
 
     def compute_gae(self, gamma: float = 0.99, lam: float = 0.9, last_value: Optional[torch.Tensor] = None,
-                    next_value: Optional[torch.Tensor] = None, want_stats: bool = True):
+                    next_value: Optional[torch.Tensor] = None, want_stats: bool = True, *, time_limit: str = "own",
+                    rule: Optional[TimeLimitRule] = None, normalized: bool = False, done_eff: bool = False):
         """ppo.py:134-146 for every (env, agent) column in one launch.  `last_value` fills the
         bootstrap row value[T]; `next_value` ([T,N,n_agents]) overrides Vnext_t = value[t+1] — with an
         auto-resetting env pass `next_values(critic)`: value[t+1] is V of the NEW episode's first
         observation on reset rows, which is not what the reference bootstraps from (see the class
         docstring).  The recursion itself is the reference's: masked by `done` only.
-        Returns (advantage, td_target[, (sum, sumsq, count) per agent as float64 [n_agents, 3]])."""
+        Returns (advantage, td_target[, (sum, sumsq, count) per agent as float64 [n_agents, 3]]).
+
+        With the keyword-only arguments at their defaults that is all (qr_gae).  Any other value goes through ONE call of qr_gae_rule
+        (`gae_rule`) and returns (advantage, td_target, stats), stats being the kept tensor `gae_stats` (None with want_stats=False and
+        normalized=False):
+        time_limit="solved": `done` is, on the transitions whose `truncated` is set, the flag the reference stores there
+            (main.py:169-173, 176-177: "solved and not crashed", read from final_obs, or from obs[t + 1] in a storage without it) in
+            both places ppo.py:134-146 reads it — a solved episode is not bootstrapped and cuts the recursion, an env that crashed
+            on its last step is bootstrapped and does not.  rule: the three numbers; None: TimeLimitRule(x_lim=the env's).
+            With time_limit="own" a given rule is checked and has NO effect on the flags (the call still goes through qr_gae_rule):
+            the rule's numbers are read at the time limit only, and "own" keeps each agent's flag there.
+        normalized=True: `advantage_normalized` holds (adv - mean) / (std + 1e-4) per agent, what `normalize(advantage, stats)`
+            gives on one rank, from the same call.
+        done_eff=True: `done_eff` ([T, N, n_agents] bool) holds the flag the scan used.
+        Both tensors are made at first use and kept; every check is made before the launch."""
+        if time_limit != "own" or rule is not None or normalized or done_eff:
+            return self._compute_gae_rule(gamma, lam, last_value, next_value, want_stats, time_limit, rule, normalized, done_eff)
         if last_value is not None:
             self.value[self.T].copy_(last_value.reshape(self.N, self.n_agents))
         M = self.N * self.n_agents
@@ -245,6 +350,49 @@ class RolloutStorage:
             tot = torch.stack([a64.sum((0, 1)), (a64 * a64).sum((0, 1))], 1)
         cnt = torch.full((self.n_agents, 1), float(self.T * self.N), dtype=torch.float64, device=self.device)
         return self.advantage, self.td_target, torch.cat([tot, cnt], 1)
+
+    def _compute_gae_rule(self, gamma, lam, last_value, next_value, want_stats, time_limit, rule, normalized, done_eff):
+        """compute_gae's path through qr_gae_rule: the checks, the kept tensors, one call."""
+        what = "compute_gae"
+        if time_limit not in TIME_LIMITS:
+            raise ValueError(f"time_limit must be one of {TIME_LIMITS}, got {time_limit!r}")
+        if rule is None:
+            rule = TimeLimitRule() if self.env_x_lim is None else TimeLimitRule(x_lim=float(self.env_x_lim))
+        rule = TimeLimitRule(*rule).check(what)
+        truncated = term_obs = None
+        if time_limit == "solved":
+            if self.truncated is None:
+                raise ValueError("time_limit='solved' needs the storage's truncated flags: they mark the transitions at the time limit")
+            if self.obs[0].shape[-1] < 3:
+                raise ValueError("time_limit='solved' reads ex, the first three words of agent 0's observation")
+            truncated = self.truncated
+            term_obs = self.final_obs if self.final_obs is not None else [o[1:] for o in self.obs]
+        else:
+            rule = None
+        T, N, na, dev = self.T, self.N, self.n_agents, self.reward.device
+        if last_value is not None and last_value.numel() != N * na:
+            raise ValueError(f"last_value must hold {N} x {na} values")
+        nv = None if next_value is None else next_value.contiguous()
+        if nv is not None and (tuple(nv.shape) != (T, N, na) or nv.dtype != torch.float32 or nv.device != dev):
+            raise ValueError(f"next_value must be float32 [{T}, {N}, {na}] on {dev}")
+        if normalized and T * N < 2:
+            raise ValueError(f"{what}: normalized=True needs at least two transitions per agent, got {T} x {N}")
+        if dev.type != "cuda":
+            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        stats = want_stats or normalized
+        if stats and self.gae_stats is None:
+            self.gae_stats = torch.zeros(na, 3, dtype=torch.float64, device=dev)
+            self._gae_workspace = torch.zeros(gae_rule_workspace_numel(N, na), dtype=torch.float64, device=dev)
+        if normalized and self.advantage_normalized is None:
+            self.advantage_normalized = torch.zeros(T, N, na, dtype=torch.float32, device=dev)
+        if done_eff and self.done_eff is None:
+            self.done_eff = torch.zeros(T, N, na, dtype=torch.bool, device=dev)
+        if last_value is not None:
+            self.value[T].copy_(last_value.reshape(N, na))
+        return gae_rule(self.reward, self.done, self.value, self.advantage, self.td_target, gamma=gamma, lam=lam, next_value=nv,
+                        truncated=truncated, term_obs=term_obs, rule=rule, done_eff=self.done_eff if done_eff else None,
+                        stats=self.gae_stats if stats else None, normalized=self.advantage_normalized if normalized else None,
+                        workspace=self._gae_workspace if stats else None)
 
     @staticmethod
     def normalize(advantage: torch.Tensor, stats: torch.Tensor, group=None) -> torch.Tensor:

@@ -504,6 +504,23 @@ def qr_episode_scan(reward: torch.Tensor, done: torch.Tensor, truncated: torch.T
                  ep_final_error=ep_final_error, workspace=workspace)
 
 
+@torch.library.custom_op(f"{_NS}::qr_gae_rule", mutates_args=("advantage", "td_target", "done_eff", "stats", "normalized", "workspace"))
+def qr_gae_rule(reward: torch.Tensor, done: torch.Tensor, truncated: Optional[torch.Tensor], term_obs: List[torch.Tensor], value: torch.Tensor,
+                next_value: Optional[torch.Tensor], advantage: torch.Tensor, td_target: torch.Tensor, done_eff: Optional[torch.Tensor],
+                stats: Optional[torch.Tensor], normalized: Optional[torch.Tensor], workspace: Optional[torch.Tensor], gamma: float, lam: float,
+                rule: bool, x_lim: float, pos_tol: float, rot_tol: float, norm_eps: float) -> None:
+    """PPO's advantages over the done flag the reference stores, their per-agent statistics and their normalisation in one C call
+    (qr_gae_rule), as rollout.gae_rule: term_obs one [T, N, D_k] tensor per agent, or an empty list with rule=False (x_lim, pos_tol and
+    rot_tol are then not read); done_eff, stats, normalized optional; workspace float64 [rollout.gae_rule_workspace_numel(N, n_agents)],
+    needed with stats."""
+    from .rollout import gae_rule
+    from .td3 import TimeLimitRule
+    _gpu(reward)
+    gae_rule(reward, done, value, advantage, td_target, gamma=gamma, lam=lam, next_value=next_value, truncated=truncated,
+             term_obs=list(term_obs) if term_obs else None, rule=TimeLimitRule(x_lim, pos_tol, rot_tol) if rule else None, done_eff=done_eff,
+             stats=stats, normalized=normalized, workspace=workspace, norm_eps=norm_eps)
+
+
 @torch.library.custom_op(f"{_NS}::qr_sac_target", mutates_args=("y", "action_out", "logp_out"))
 def qr_sac_target(actor: List[torch.Tensor], critic: List[torch.Tensor], action_dim: int, obs_next: torch.Tensor, reward: torch.Tensor,
                   done: torch.Tensor, index: Optional[torch.Tensor], noise: Optional[torch.Tensor], action_next: Optional[torch.Tensor],

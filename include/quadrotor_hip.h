@@ -1161,6 +1161,63 @@ int     qr_episode_scan(const QrEpisodeScan* a, void* stream);
  * for n_envs < 0. */
 int64_t qr_episode_workspace_bytes(int64_t n_envs);
 
+/* ---- PPO's advantages with the done flag the reference stores, their statistics and their normalisation in one call ----
+ * main.py:169-173 overwrites done_n at the episode time limit with "solved and not crashed", main.py:176-177 stores that flag for PPO,
+ * and ppo.py:134-146 reads it twice: in td_error = r + gamma * V(obs_next) * (1 - done) - V and in the (1 - done) that cuts the
+ * lambda-recursion.  qr_gae_rule is qr_gae's reverse scan over the EFFECTIVE flag of transition (t, n) and agent k:
+ *     done_eff = done[t][n][k]                                             where truncated[t][n] == 0, or rule == 0
+ *              = solved_k && reward[t][n][k] != -1.0f                      where truncated[t][n] != 0 and rule == 1
+ *     solved_0 = fabs((double)term_obs0[t][n][c] * x_lim) <= pos_tol for c = 0, 1, 2
+ *     solved_1 = fabs((double)term_obs1[t][n][0] * pi) <= rot_tol          (pi = the double nearest pi; two agents only)
+ * — qr_replay_add_rule's expressions, compared in double on the float32 words; an own done = 1 on a time-limit row is overridden.
+ * term_obs0 / term_obs1 hold the transition's obs_next on time-limit rows: final_obs where the storage has it, else the rows
+ * obs[k][1:] (qr_replay_add_rule's choice); they are read on rows whose truncated is set only (three words, one word).
+ *     nd = done_eff ? 0 : 1;  delta = r + gamma * Vnext * nd - V;  adv = delta + gamma * nd * lam * adv;  td_target = adv + V
+ * in float32, qr_gae's recurrence expression for expression: advantage and td_target equal qr_gae run on done_eff bit for bit.
+ * value / next_value mean what they mean for qr_gae: without next_value, row n_steps of value is the bootstrap.
+ * Bootstrap semantics are otherwise unchanged (qr_critic_next_values supplies V(final_obs) on reset rows); the reference's
+ * cross-episode leak on unsolved time limits is kept.
+ * stats: per agent the sum and the sum of squares of its advantages in float64 and the count n_steps * n_envs as a double — the layout
+ * RolloutStorage.normalize consumes.  Each lane accumulates in float64, a fixed shuffle tree over the lanes of one agent gives one
+ * vector per 64-column workgroup in `workspace`, a second launch folds the vectors in workgroup-index order: no floating-point atomics,
+ * the same bits from call to call.
+ * normalized = (float)(((double)adv - mean) / (std + norm_eps)), mean = s1 / n, var = max(0, (s2 - n * mean * mean) / (n - 1)),
+ * std = sqrt(var): ppo.py:146 with torch's unbiased std, per agent, in a third launch that reads stats from device memory. */
+typedef struct QrGaeRule {
+  const float*   reward;          /* [n_steps][n_envs][n_agents] */
+  const uint8_t* done;            /* [n_steps][n_envs][n_agents] bool bytes */
+  const uint8_t* truncated;       /* [n_steps][n_envs] bool bytes; required where rule != 0 */
+  const float*   term_obs0;       /* [n_steps][n_envs][d0]; required where rule != 0 */
+  const float*   term_obs1;       /* [n_steps][n_envs][d1]; required where rule != 0 with two agents */
+  const float*   value;           /* [n_steps + 1][n_envs][n_agents] ([n_steps] rows are read where next_value is given) */
+  const float*   next_value;      /* [n_steps][n_envs][n_agents], or NULL */
+  float*         advantage;       /* [n_steps][n_envs][n_agents], written */
+  float*         td_target;       /* [n_steps][n_envs][n_agents], written */
+  uint8_t*       done_eff;        /* [n_steps][n_envs][n_agents], written: the done_n the reference would have stored; may be NULL */
+  double*        stats;           /* [n_agents][3] = sum, sum of squares, count; may be NULL */
+  float*         normalized;      /* [n_steps][n_envs][n_agents]; may be NULL; needs stats and n_steps * n_envs >= 2 */
+  void*          workspace;       int64_t workspace_bytes;   /* with stats: >= qr_gae_rule_workspace_bytes(n_envs, n_agents); 8-byte aligned */
+  int64_t        n_envs;
+  int32_t        n_steps, n_agents;   /* n_agents 1 or 2 */
+  int32_t        d0, d1;          /* row widths of term_obs0 / term_obs1; rule != 0: d0 >= 3, d1 >= 1 (two agents) */
+  int32_t        rule, reserved0; /* rule 0 or 1; reserved0 must be 0 */
+  float          gamma, lam;
+  double         x_lim;           /* rule != 0: the env's position limit, finite and > 0 */
+  double         pos_tol, rot_tol;/* rule != 0: [m], [rad]; the reference's are 0.03 and 0.03; finite, >= 0 */
+  double         norm_eps;        /* the reference's is 1e-4; finite, >= 0 (read with normalized only) */
+} QrGaeRule;
+/* Up to three launches on `stream` behind one call; no host synchronisation, no allocation.  In this order, all before any launch:
+ * QR_E_NULL for a NULL struct; QR_E_SIZE for n_steps < 1, n_envs < 0 or > 2^35, n_agents outside 1..2, reserved0 != 0, rule outside
+ * 0..1, with rule != 0 d0 < 3, d1 < 1 with two agents, an x_lim that is not finite and > 0 or a negative or non-finite tolerance, with
+ * normalized a negative or non-finite norm_eps or n_steps * n_envs < 2, with stats a workspace that is too small; QR_E_NULL for a NULL
+ * reward, done, value, advantage or td_target, with rule != 0 a NULL truncated, term_obs0 or (two agents) term_obs1, normalized without
+ * stats, stats without workspace; QR_E_ALIGN for a float pointer that is not 4-byte aligned or a stats or workspace pointer that is
+ * not 8-byte aligned.  n_envs = 0 launches nothing. */
+int     qr_gae_rule(const QrGaeRule* a, void* stream);
+/* Bytes of workspace qr_gae_rule needs with stats: 2 * n_agents doubles per 64-column workgroup (at least one); QR_E_SIZE (< 0) for
+ * n_envs < 0 or n_agents outside 1..2. */
+int64_t qr_gae_rule_workspace_bytes(int64_t n_envs, int32_t n_agents);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -303,6 +303,46 @@ def test_sac_actor_in_kernel_vs_reference_module(golden, kind):
 
 
 @pytest.mark.parametrize("kind", ["coupled", "decoupled"])
+def test_sac_actor_in_kernel_every_golden_row(golden, kind):
+    """The rows of test_sac_actor_in_kernel_vs_reference_module WITHOUT its two masks — 49 of Coupled's 1024 log_std values sit on a
+    clamp and 30 actions are exactly +-1 — in the two forms that hold there (tests/action_ref.py, tests/test_gpu_action_rules.py):
+    (i) the action against tanh(u) of the float64 network, under sac_action_bar with the running bound of a float32 evaluation of
+    these weights on these rows (heads_with_error: pre-activations reach 65, so that bound, not the rule's, is most of the bar);
+    (ii) the log-prob against sac_logp_from_action at the RETURNED action.  The module's own float32 log-prob is no yardstick
+    where |a| -> 1: it forms 1 - a^2 with a rounded square and sits up to 2.2 from the float64 value at its own action."""
+    import action_ref as AR
+    from gym_rotor_amd import ActorParams, _lib
+    d = golden("actor_sac")
+    tags = [f"{kind}0"] if kind == "coupled" else [f"{kind}0", f"{kind}1"]
+    n = d[f"{tags[0]}_obs"].shape[0]
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    names = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mean_w", "mean_b", "log_std_w", "log_std_b")
+    actors = [ActorParams(*[cu(d[f"{t}_{k}"]) for k in names[:6]], None, cu(d[f"{t}_log_std_w"]), cu(d[f"{t}_log_std_b"]), _lib.ACTOR_TANH_SAMPLE)
+              for t in tags]
+    env = _env(kind, n)
+    env.reset("train")
+    obs = [cu(d[f"{t}_obs"]) for t in tags]
+    eps = np.concatenate([d[f"{t}_eps"] for t in tags], 1)
+    out = env.rollout_actor(actors, 1, obs=obs, noise=cu(eps[None]))
+    det = env.rollout_actor(actors, 1, obs=obs, deterministic=True)
+    heads = [AR.heads_with_error({k: d[f"{t}_{k}"] for k in names}, d[f"{t}_obs"]) for t in tags]
+    pre, ls, pre_err, ls_err = (np.concatenate([h[k] for h in heads], 1) for k in range(4))
+    lsc, e64 = np.clip(ls, AR.LOG_STD_MIN, AR.LOG_STD_MAX), eps.astype(np.float64)
+    assert (np.abs(ls) >= 2.0).sum() > 20 and (np.abs(np.concatenate([d[f"{t}_action"] for t in tags], 1)) == 1.0).sum() > 20
+    for label, o, z in (("sampled", out, e64), ("deterministic", det, None)):
+        a, logp = _np(o["action"][0]), _np(o["logprob"][0])
+        want_a = AR.tanh_sample_rule(pre, ls, z)[0]
+        err_a, bar_a = np.abs(a - want_a), AR.sac_action_bar(pre, lsc, z, pre_err, ls_err)
+        err_l, bar_l = np.abs(logp - AR.sac_logp_from_action(lsc, z, a)), AR.sac_logp_bar(lsc, z, a, ls_err)
+        print(f"[sac golden rows, unmasked] {kind} {label}: action error / bar {(err_a / bar_a).max():.3f} (max error {err_a.max():.3e}, bars "
+              f"{bar_a.min():.1e} .. {bar_a.max():.1e}); logp error / bar {(err_l / bar_l).max():.3f} (max error {err_l.max():.3e}, bars "
+              f"{bar_l.min():.1e} .. {bar_l.max():.1e}); {int((np.abs(a) == 1).sum())} actions of +-1")
+        assert (np.abs(a) <= 1.0).all() and np.isfinite(logp).all()
+        assert (err_a <= bar_a).all(), (label, np.argwhere(err_a > bar_a)[:4].tolist())
+        assert (err_l <= bar_l).all(), (label, np.argwhere(err_l > bar_l)[:4].tolist())
+
+
+@pytest.mark.parametrize("kind", ["coupled", "decoupled"])
 @pytest.mark.parametrize("algo", ["ppo", "sac"])
 def test_actor_rollout_helper_launch_equals_the_plain_one(kind, algo):
     """qr_rollout_actor picks a helper-wave instantiation (noise, reset pool and observation rows on a second wavefront per tile) for

@@ -24,6 +24,7 @@ from .episodes import EpisodeTracker, episode_scan, episode_workspace_numel  # n
 from .offpolicy import OffPolicyCollector, SacUpdater, Td3Updater  # noqa: F401
 from .ppo import PpoCollector  # noqa: F401
 from .evaluate import EvalResult, PopulationResult, evaluate_policy, evaluate_population  # noqa: F401
+from .es import EvolutionStrategy, es_gradient, es_perturb, es_stream  # noqa: F401  (the module's other helpers stay in gym_rotor_amd.es)
 from . import torch_ops  # noqa: F401  (registers torch.ops.gym_rotor_amd.*)
 
 __all__ = ["QuadVecEnv", "QuadEnv", "CoupledWrapper", "DecoupledWrapper", "QuadConstants", "Box",

@@ -41,7 +41,8 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_dpg_actor_grad", "qr_ctde_dpg_actor_workspace_bytes",
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
            "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill",
-           "qr_episode_scan", "qr_episode_workspace_bytes", "qr_gae_rule", "qr_gae_rule_workspace_bytes")
+           "qr_episode_scan", "qr_episode_workspace_bytes", "qr_gae_rule", "qr_gae_rule_workspace_bytes",
+           "qr_es_perturb", "qr_es_gradient", "qr_es_workspace_bytes")
 
 
 class QrCoeffs(C.Structure):
@@ -460,6 +461,66 @@ def gae_rule_args(reward, done, truncated, term_obs, value, next_value, advantag
     return e
 
 
+ES_MAX_TENSORS, ES_MAX_COPIES, ES_MAX_POLICIES, ES_STATS = 16, 8, 8192, 4   # qr_es_perturb / qr_es_gradient
+ES_CENTERED_RANK, ES_STANDARDIZE = 0, 1
+ES_SHAPING_ID = {"centered_rank": ES_CENTERED_RANK, "standardize": ES_STANDARDIZE}
+
+
+class QrEsTensor(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("out", C.c_void_p), ("count", C.c_int64), ("stream", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class QrEsCopy(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("count", C.c_int64)]
+
+
+class QrEsPerturb(C.Structure):
+    _fields_ = [("tensor", QrEsTensor * ES_MAX_TENSORS), ("copy", QrEsCopy * ES_MAX_COPIES), ("n_tensors", C.c_int32), ("n_copies", C.c_int32),
+                ("n_policies", C.c_int32), ("max_workgroups", C.c_int32), ("sigma", C.c_float), ("reserved0", C.c_float), ("seed", C.c_uint64),
+                ("generation_dev", C.c_void_p), ("generation", C.c_int64)]
+
+
+class QrEsGradient(C.Structure):
+    _fields_ = [("tensor", QrEsTensor * ES_MAX_TENSORS), ("fitness", C.c_void_p), ("stats", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("n_tensors", C.c_int32), ("n_policies", C.c_int32), ("shaping", C.c_int32),
+                ("max_workgroups", C.c_int32), ("sigma", C.c_float), ("reserved0", C.c_float), ("seed", C.c_uint64),
+                ("generation_dev", C.c_void_p), ("generation", C.c_int64)]
+
+
+def _es_key(s, *, n_policies, sigma, seed, generation, generation_dev, max_workgroups):
+    s.n_policies, s.max_workgroups, s.sigma, s.reserved0 = int(n_policies), int(max_workgroups), float(sigma), 0.0
+    s.seed, s.generation_dev, s.generation = int(seed) & (2 ** 64 - 1), ptr(generation_dev), int(generation)
+
+
+def es_perturb_args(base, out, copies, streams, **key) -> QrEsPerturb:
+    """QrEsPerturb of one qr_es_perturb launch: base / out 1..16 tensors each (out the stacked [P, ...] ones), copies up to 8 (src, dst)
+    pairs, streams one id per tensor; key: n_policies, sigma, seed, generation, generation_dev (a device int64 tensor or None),
+    max_workgroups."""
+    p = QrEsPerturb()
+    p.n_tensors, p.n_copies = len(base), len(copies)
+    for k, (b, o) in enumerate(zip(base, out)):
+        t = p.tensor[k]
+        t.base, t.out, t.count, t.stream, t.reserved0 = b.data_ptr(), o.data_ptr(), b.numel(), int(streams[k]), 0
+    for k, (src, dst) in enumerate(copies):
+        c = p.copy[k]
+        c.src, c.dst, c.count = src.data_ptr(), dst.data_ptr(), src.numel()
+    _es_key(p, **key)
+    return p
+
+
+def es_gradient_args(fitness, grads, stats, workspace, streams, *, shaping, **key) -> QrEsGradient:
+    """QrEsGradient of one qr_es_gradient call: grads 1..16 tensors, streams one id per tensor, shaping an ES_* id; key as above."""
+    g = QrEsGradient()
+    g.n_tensors, g.shaping = len(grads), int(shaping)
+    for k, t_ in enumerate(grads):
+        t = g.tensor[k]
+        t.base, t.out, t.count, t.stream, t.reserved0 = None, t_.data_ptr(), t_.numel(), int(streams[k]), 0
+    g.fitness, g.stats, g.workspace = ptr(fitness), ptr(stats), ptr(workspace)
+    g.workspace_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _es_key(g, **key)
+    return g
+
+
 def soft_update_args(params, targets, tau) -> QrSoftUpdate:
     """QrSoftUpdate of one qr_soft_update launch: 1..24 (param, target) tensor pairs."""
     u = QrSoftUpdate()
@@ -679,6 +740,12 @@ def load():
     lib.qr_gae_rule.argtypes = [P(QrGaeRule), C.c_void_p]
     lib.qr_gae_rule_workspace_bytes.restype = C.c_int64
     lib.qr_gae_rule_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.qr_es_perturb.restype = C.c_int
+    lib.qr_es_perturb.argtypes = [P(QrEsPerturb), C.c_void_p]
+    lib.qr_es_gradient.restype = C.c_int
+    lib.qr_es_gradient.argtypes = [P(QrEsGradient), C.c_void_p]
+    lib.qr_es_workspace_bytes.restype = C.c_int64
+    lib.qr_es_workspace_bytes.argtypes = [C.c_int32]
     lib.qr_step_kernel_info.restype = C.c_char_p
     lib.qr_step_kernel_info.argtypes = [P(QrEnv), C.c_int32, P(C.c_int32), P(C.c_int32)]
     lib.qr_launch_plan.restype = C.c_int

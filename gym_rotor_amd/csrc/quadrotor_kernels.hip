@@ -64,6 +64,8 @@
 //                  error, and their statistics: episode_scan_kernel, episode_reduce_kernel
 //   qr_gae.h       PPO's advantages over the done flag the reference stores at the time limit, their per-agent statistics and their
 //                  normalisation (qr_gae_rule): gae_rule_kernel, gae_fold_kernel, gae_normalize_kernel
+//   qr_es.h        what surrounds the population evaluation in an evolution-strategy generation (qr_es_perturb, qr_es_gradient): the keyed
+//                  antithetic perturbation, the fitness shaping and the gradient estimator: es_perturb_kernel, es_utility_kernel, es_grad_kernel
 //   qr_launch.h    host side: argument blocks, the launch rule, the instantiation table, launchers
 //   this file      the C-ABI; the launchers of the update entries, among them actor_grad_launch (qr_ppo_actor_grad, qr_dpg_actor_grad and qr_ctde_dpg_actor_grad),
 //                  mlp_grad_launch (qr_ppo_critic_grad, qr_twinq_grad and qr_ctde_twinq_grad), target_launch (the four target entries) and
@@ -96,6 +98,7 @@
 #include "qr_noise.h"
 #include "qr_episode.h"
 #include "qr_gae.h"
+#include "qr_es.h"
 #include "qr_launch.h"
 
 namespace qr {
@@ -885,9 +888,109 @@ static int do_gae_rule(const QrGaeRule* e, void* stream) {
   }
   return (int)hipGetLastError();
 }
+
+// What qr_es_perturb and qr_es_gradient check alike in their sizes: P, the tensors' counts and stream ids, sigma, the grid cap and the
+// generation.  quads: the sum of ceil(count / 4) over the tensors.
+static int es_sizes(const QrEsTensor* t, int32_t n_tensors, int32_t P, float sigma, float reserved0, int32_t max_workgroups,
+                    const int64_t* generation_dev, int64_t generation, int64_t* quads) {
+  if (P < 2 || (P & 1) || P > QR_ES_MAX_POLICIES || n_tensors < 1 || n_tensors > kEsSlots) return QR_E_SIZE;
+  *quads = 0;
+  for (int k = 0; k < n_tensors; ++k) {
+    if (t[k].count < 1 || t[k].count > 0x7FFFFFFFll || t[k].stream >= (1u << 30) || t[k].reserved0 != 0) return QR_E_SIZE;
+    for (int m = 0; m < k; ++m)
+      if (t[m].stream == t[k].stream) return QR_E_SIZE;
+    *quads += (t[k].count + 3) / 4;
+  }
+  if (*quads * (P / 2) > 0x7FFFFFFFll) return QR_E_SIZE;
+  if (!(sigma > 0.0f) || !__builtin_isfinite(sigma) || reserved0 != 0.0f || max_workgroups < 0) return QR_E_SIZE;
+  if (!generation_dev && generation < 0) return QR_E_SIZE;
+  return 0;
+}
+
+static int do_es_perturb(const QrEsPerturb* p, void* stream) {
+  if (!p) return QR_E_NULL;
+  int64_t quads = 0;
+  if (int rc = es_sizes(p->tensor, p->n_tensors, p->n_policies, p->sigma, p->reserved0, p->max_workgroups, p->generation_dev, p->generation, &quads))
+    return rc;
+  if (p->n_copies < 0 || p->n_copies > kEsCopies) return QR_E_SIZE;
+  for (int c = 0; c < p->n_copies; ++c)
+    if (p->copy[c].count < 1 || p->copy[c].count > 0x7FFFFFFFll) return QR_E_SIZE;
+  uintptr_t b4 = 0;
+  for (int k = 0; k < p->n_tensors; ++k) {
+    if (!p->tensor[k].base || !p->tensor[k].out) return QR_E_NULL;
+    b4 |= reinterpret_cast<uintptr_t>(p->tensor[k].base) | reinterpret_cast<uintptr_t>(p->tensor[k].out);
+  }
+  for (int c = 0; c < p->n_copies; ++c) {
+    if (!p->copy[c].src || !p->copy[c].dst) return QR_E_NULL;
+    b4 |= reinterpret_cast<uintptr_t>(p->copy[c].src) | reinterpret_cast<uintptr_t>(p->copy[c].dst);
+  }
+  if ((b4 & 3u) || (reinterpret_cast<uintptr_t>(p->generation_dev) & 7u)) return QR_E_ALIGN;
+  EsPerturbArgs a{};
+  const int64_t half = p->n_policies / 2;
+  int64_t end = 0;
+  for (int k = 0; k < kEsSlots; ++k) {
+    if (k < p->n_tensors) {
+      const QrEsTensor& t = p->tensor[k];
+      a.base[k] = t.base; a.out[k] = t.out; a.count[k] = (uint32_t)t.count; a.quads[k] = (uint32_t)((t.count + 3) / 4); a.stream[k] = t.stream;
+      end += half * a.quads[k];
+    }
+    a.qend[k] = (uint32_t)end;
+  }
+  for (int c = 0; c < p->n_copies; ++c) { a.csrc[c] = p->copy[c].src; a.cdst[c] = p->copy[c].dst; a.ccount[c] = (uint32_t)p->copy[c].count; }
+  a.n_copies = p->n_copies; a.P = (uint32_t)p->n_policies; a.sigma = p->sigma;
+  a.seed = p->seed; a.gen_dev = p->generation_dev; a.gen = p->generation;
+  const int64_t blocks = (end + kEsBlock - 1) / kEsBlock, cap = p->max_workgroups > 0 && p->max_workgroups < kEsGrid ? p->max_workgroups : kEsGrid;
+  hipLaunchKernelGGL(es_perturb_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(kEsBlock), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
+static int do_es_gradient(const QrEsGradient* g, void* stream) {
+  if (!g) return QR_E_NULL;
+  int64_t quads = 0;
+  if (int rc = es_sizes(g->tensor, g->n_tensors, g->n_policies, g->sigma, g->reserved0, g->max_workgroups, g->generation_dev, g->generation, &quads))
+    return rc;
+  if (g->shaping < QR_ES_CENTERED_RANK || g->shaping > QR_ES_STANDARDIZE) return QR_E_SIZE;
+  if (g->workspace_bytes < (int64_t)(g->n_policies / 2) * (int64_t)sizeof(double)) return QR_E_SIZE;
+  uintptr_t b4 = reinterpret_cast<uintptr_t>(g->fitness);
+  for (int k = 0; k < g->n_tensors; ++k) {
+    if (!g->tensor[k].out) return QR_E_NULL;
+    b4 |= reinterpret_cast<uintptr_t>(g->tensor[k].out);
+  }
+  if (!g->fitness || !g->stats || !g->workspace) return QR_E_NULL;
+  const uintptr_t b8 = reinterpret_cast<uintptr_t>(g->stats) | reinterpret_cast<uintptr_t>(g->workspace) | reinterpret_cast<uintptr_t>(g->generation_dev);
+  if ((b4 & 3u) || (b8 & 7u)) return QR_E_ALIGN;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const EsUtilityArgs u{g->fitness, static_cast<double*>(g->workspace), g->stats, g->n_policies, g->shaping};
+  hipLaunchKernelGGL(es_utility_kernel, dim3((unsigned)((g->n_policies + kEsBlock - 1) / kEsBlock)), dim3(kEsBlock), 0, s, u);
+  if (int rc = (int)hipGetLastError()) return rc;
+  EsGradArgs a{};
+  int64_t end = 0;
+  for (int k = 0; k < kEsSlots; ++k) {
+    if (k < g->n_tensors) {
+      const QrEsTensor& t = g->tensor[k];
+      a.grad[k] = t.out; a.count[k] = (uint32_t)t.count; a.quads[k] = (uint32_t)((t.count + 3) / 4); a.stream[k] = t.stream;
+      end += a.quads[k];
+    }
+    a.qend[k] = (uint32_t)end;
+  }
+  a.w = u.w; a.half = (uint32_t)(g->n_policies / 2); a.den = (double)g->n_policies * (double)g->sigma;
+  a.seed = g->seed; a.gen_dev = g->generation_dev; a.gen = g->generation;
+  const int64_t cap = g->max_workgroups > 0 && g->max_workgroups < kEsGradGrid ? g->max_workgroups : kEsGradGrid;
+  hipLaunchKernelGGL(es_grad_kernel, dim3((unsigned)(end < cap ? end : cap)), dim3(64), 0, s, a);
+  return (int)hipGetLastError();
+}
 }  // namespace qr
 
 extern "C" {
+
+int qr_es_perturb(const QrEsPerturb* p, void* stream) { return qr::do_es_perturb(p, stream); }
+
+int qr_es_gradient(const QrEsGradient* g, void* stream) { return qr::do_es_gradient(g, stream); }
+
+int64_t qr_es_workspace_bytes(int32_t n_policies) {
+  if (n_policies < 2 || (n_policies & 1) || n_policies > QR_ES_MAX_POLICIES) return QR_E_SIZE;
+  return (int64_t)(n_policies / 2) * (int64_t)sizeof(double);
+}
 
 int qr_gae_rule(const QrGaeRule* a, void* stream) { return qr::do_gae_rule(a, stream); }
 

@@ -74,9 +74,10 @@ def _prepare_episodes(kind, num_envs, traj_mode, seed, **env_kw):
     return env, env.get_norm_error_state()
 
 
-def _tile_episodes(src: QuadVecEnv, src_obs, env: QuadVecEnv, P: int) -> list:
+def _tile_episodes(src: QuadVecEnv, src_obs, env: QuadVecEnv, P: int, obs: Optional[list] = None) -> list:
     """Copy the prepared episodes of `src` (E envs: state, parameters, integrators, goal, generator state, episode index) into every
-    one of the P policies' blocks of `env` (P * Epad envs); returns `src_obs` tiled the same way, zeros in the padding rows."""
+    one of the P policies' blocks of `env` (P * Epad envs); returns `src_obs` tiled the same way, zeros in the padding rows.
+    `obs`: the rows an earlier call returned for the same `src_obs` — they are returned as they are and nothing is allocated."""
     from .policy import population_tile
     E = src.num_envs
     if src._goal is not None:   # (the goal buffer of a stateless generator mode exists from get_desired(store_goal=True) on)
@@ -85,6 +86,8 @@ def _tile_episodes(src: QuadVecEnv, src_obs, env: QuadVecEnv, P: int) -> list:
         if getattr(src, name) is not None:
             population_tile(getattr(src, name), P, E, getattr(env, name), env_dim=1)
     population_tile(src._episode, P, E, env._episode)
+    if obs is not None:
+        return obs
     return [population_tile(o, P, E, torch.zeros(env.num_envs, o.shape[1], dtype=o.dtype, device=o.device)) for o in src_obs]
 
 

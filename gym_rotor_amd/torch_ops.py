@@ -487,6 +487,35 @@ def qr_noise_fill(tensors: List[torch.Tensor], kinds: List[int], a: List[float],
     noise_fill(list(tensors), seed=seed, draw=draw, streams=list(streams), kind=[KINDS[k] for k in kinds], a=list(a), b=list(b), draw_dev=draw_dev)
 
 
+@torch.library.custom_op(f"{_NS}::qr_es_perturb", mutates_args=("out", "copy_dst"))
+def qr_es_perturb(base: List[torch.Tensor], out: List[torch.Tensor], copy_src: List[torch.Tensor], copy_dst: List[torch.Tensor], streams: List[int],
+                  sigma: float, seed: int, generation: int, generation_dev: Optional[torch.Tensor], max_workgroups: int) -> None:
+    """The antithetic evolution-strategy population around `base` in one launch (qr_es_perturb), as es.es_perturb_tensors: out[i]
+    [P, ...] gets base[i] +- sigma eps in its even / odd rows, copy_dst[c] [P, ...] gets copy_src[c] in every row; one stream id per
+    base tensor; seed and generation are passed as int64 here.  generation_dev: an int64 device tensor of one element that is read as
+    the generation instead of `generation`, or None."""
+    from .es import es_perturb_tensors
+    _gpu(out[0])
+    if len(copy_src) != len(copy_dst):
+        raise ValueError("copy_src and copy_dst must pair up")
+    es_perturb_tensors(list(base), list(out), sigma=sigma, seed=seed, generation=generation if generation_dev is None else generation_dev,
+                       streams=list(streams), copies=list(zip(copy_src, copy_dst)), max_workgroups=max_workgroups)
+
+
+@torch.library.custom_op(f"{_NS}::qr_es_gradient", mutates_args=("grads", "stats", "workspace"))
+def qr_es_gradient(fitness: torch.Tensor, grads: List[torch.Tensor], stats: torch.Tensor, workspace: torch.Tensor, streams: List[int], sigma: float,
+                   seed: int, generation: int, generation_dev: Optional[torch.Tensor], shaping: int, max_workgroups: int) -> None:
+    """The shaped fitness and the evolution-strategy gradient estimate in one C call (qr_es_gradient), as es.es_gradient on a flat
+    list of gradient tensors: shaping 0 = centered ranks, 1 = standardised fitness; stats float64 [4]; workspace float64
+    [es.es_workspace_numel(P)]."""
+    from .es import SHAPINGS, es_gradient
+    _gpu(fitness)
+    if shaping not in (0, 1):
+        raise ValueError("shaping is 0 (centered_rank) or 1 (standardize)")
+    es_gradient(fitness, list(grads), sigma=sigma, seed=seed, generation=generation if generation_dev is None else generation_dev,
+                streams=list(streams), shaping=SHAPINGS[shaping], stats=stats, workspace=workspace, max_workgroups=max_workgroups)
+
+
 @torch.library.custom_op(f"{_NS}::qr_episode_scan", mutates_args=("run_return", "run_length", "last", "total", "ep_return", "ep_length", "ep_flags",
                                                                   "ep_final_error", "workspace"))
 def qr_episode_scan(reward: torch.Tensor, done: torch.Tensor, truncated: torch.Tensor, final_obs: List[torch.Tensor], run_return: torch.Tensor,

@@ -1218,6 +1218,92 @@ int     qr_gae_rule(const QrGaeRule* a, void* stream);
  * n_envs < 0 or n_agents outside 1..2. */
 int64_t qr_gae_rule_workspace_bytes(int64_t n_envs, int32_t n_agents);
 
+/* ---- An evolution-strategy generation around qr_evaluate_population: the perturbed population and the gradient estimator ----
+ * The base theta is a list of up to sixteen float32 tensors (an actor's weights and biases).  Tensor i has count_i elements,
+ * Q_i = ceil(count_i / 4) quads and a stream id s_i < 2^30.  The population has P policies, P even, in antithetic adjacent pairs.
+ * THE PERTURBATION STREAM: eps_j[e], the draw of pair j (0 <= j < P / 2) for element e of tensor i, is element j * 4 Q_i + e of the
+ * qr_noise_fill stream (seed, draw = generation, stream = s_i, QR_NOISE_NORMAL, a = 0, b = 1): quad j * Q_i + e / 4, position e % 4.
+ * So the eps of a generation is, bit for bit, what qr_noise_fill writes into a [P / 2][4 Q_i] tensor under that key; it is never
+ * stored: both entries regenerate it, and a generation is a function of (seed, generation) alone.  A (seed, generation, stream)
+ * triple must not be used for two tensors.  generation_dev: NULL, or one device int64 that the launches READ as the generation (it is
+ * never written); `generation` is then ignored.
+ *
+ * qr_es_perturb, one launch:  d = fl32(sigma * eps_j[e]);  out[2j][e] = fl32(base[e] + d);  out[2j + 1][e] = fl32(base[e] - d)
+ * — two roundings each, the product never fused into the sum.  copy[c]: a tensor that is not perturbed (the log_std source) is
+ * written to all P rows of its stacked tensor in the same launch.  A value does not depend on the tensor's place in the launch, the
+ * other tensors, max_workgroups or a pointer's alignment (16-byte aligned rows get 16-byte stores). */
+#define QR_ES_MAX_TENSORS  16
+#define QR_ES_MAX_COPIES   8
+#define QR_ES_MAX_POLICIES 8192
+typedef struct QrEsTensor {
+  const float* base;              /* [count]; qr_es_perturb only */
+  float*       out;               /* qr_es_perturb: the stacked tensor [P][count], written; qr_es_gradient: grad [count], written */
+  int64_t      count;             /* 1 .. 2^31 - 1; (P / 2) * the sum of ceil(count / 4) over the tensors stays below 2^31 */
+  uint32_t     stream, reserved0; /* stream < 2^30, pairwise distinct; reserved0 must be 0 */
+} QrEsTensor;
+typedef struct QrEsCopy {
+  const float* src;               /* [count] */
+  float*       dst;               /* [P][count], written */
+  int64_t      count;             /* 1 .. 2^31 - 1 */
+} QrEsCopy;
+typedef struct QrEsPerturb {
+  QrEsTensor tensor[QR_ES_MAX_TENSORS];
+  QrEsCopy   copy[QR_ES_MAX_COPIES];
+  int32_t    n_tensors, n_copies; /* 1..16, 0..8 */
+  int32_t    n_policies;          /* P: even, 2 .. QR_ES_MAX_POLICIES */
+  int32_t    max_workgroups;      /* 0: the library's choice; > 0: a cap on the grid (it cannot change a value) */
+  float      sigma, reserved0;    /* sigma finite and > 0; reserved0 must be 0 */
+  uint64_t   seed;
+  const int64_t* generation_dev;  /* NULL, or one device int64 that is READ as the generation (never written) */
+  int64_t    generation;          /* the generation where generation_dev is NULL: >= 0 */
+} QrEsPerturb;
+/* In this order, all before the launch: QR_E_NULL for a NULL struct; QR_E_SIZE for an odd P, P < 2 or > 8192, n_tensors outside 1..16,
+ * n_copies outside 0..8, a count < 1 or too many quads, a stream >= 2^30 or one that appears twice, a reserved0 != 0, a sigma that is
+ * not finite and > 0, max_workgroups < 0 or a negative generation where generation_dev is NULL; QR_E_NULL for a NULL base, out, src or
+ * dst; QR_E_ALIGN for a float pointer that is not 4-byte aligned or a generation_dev that is not 8-byte aligned.  Nothing is launched
+ * or written on an error. */
+int qr_es_perturb(const QrEsPerturb* p, void* stream);
+
+/* qr_es_gradient, two launches behind one call.
+ * Utilities: fitness [P] float32 -> w [P / 2] float64 in the workspace, w_j = u_2j - u_2j+1.
+ *   QR_ES_CENTERED_RANK  rank_i = #{k : f_k < f_i} + 0.5 * (#{k : f_k == f_i} - 1),  u_i = rank_i / (P - 1) - 0.5.  A NaN is ranked as
+ *                        -inf is (NaNs tie with each other and with -inf).  The counts are integers: u_i is exact up to its one
+ *                        division and one subtraction in float64, and equal fitness everywhere gives every w_j = 0 exactly.
+ *   QR_ES_STANDARDIZE    u_i = (f_i - mean) / (std + 1e-8), mean and the unbiased std in float64 in index order; w_j is formed as
+ *                        ((double)f_2j - (double)f_2j+1) / (std + 1e-8), in which the mean has cancelled.  With a non-finite fitness
+ *                        every w_j = 0.
+ * stats [QR_ES_STATS] float64: the fitness mean (float64, index order), the largest fitness and the index of its first occurrence
+ * (NaNs are passed over; -inf and 0 where no value compares larger), and 1.0 where a fitness is NaN or infinite, else 0.0.
+ * Estimator: for every element of every tensor
+ *     grad[e] = fl32( -( sum_j w_j * (double)eps_j[e] ) / (P * sigma) )
+ * with eps regenerated from the key.  The sum is float64 in one fixed order — the 64 lanes of a wave stride over j, then a fixed
+ * shuffle tree — and rounded to float32 once: no floating-point atomics, the same bits from call to call and for any max_workgroups.
+ * The sign makes it a DESCENT gradient of -fitness: an optimiser step on it ascends the fitness. */
+#define QR_ES_CENTERED_RANK 0
+#define QR_ES_STANDARDIZE   1
+#define QR_ES_STATS         4   /* mean, max, argmax, non-finite flag */
+typedef struct QrEsGradient {
+  QrEsTensor tensor[QR_ES_MAX_TENSORS];   /* out = grad [count]; base is not read */
+  const float* fitness;           /* [P] */
+  double*    stats;               /* [QR_ES_STATS], written; 8-byte aligned */
+  void*      workspace;           int64_t workspace_bytes;   /* >= qr_es_workspace_bytes(P); 8-byte aligned */
+  int32_t    n_tensors;           /* 1..16 */
+  int32_t    n_policies;          /* P: even, 2 .. QR_ES_MAX_POLICIES */
+  int32_t    shaping;             /* QR_ES_CENTERED_RANK or QR_ES_STANDARDIZE */
+  int32_t    max_workgroups;      /* 0: the library's choice; > 0: a cap on the estimator's grid (it cannot change a value) */
+  float      sigma, reserved0;    /* sigma finite and > 0; reserved0 must be 0 */
+  uint64_t   seed;
+  const int64_t* generation_dev;
+  int64_t    generation;
+} QrEsGradient;
+/* In this order, all before any launch: QR_E_NULL for a NULL struct; QR_E_SIZE for what qr_es_perturb refuses in its sizes, a shaping
+ * outside 0..1 or a workspace that is too small; QR_E_NULL for a NULL grad, fitness, stats or workspace; QR_E_ALIGN for a float
+ * pointer that is not 4-byte aligned or a stats, workspace or generation_dev pointer that is not 8-byte aligned.  No host
+ * synchronisation, no allocation.  Nothing is launched or written on an error. */
+int     qr_es_gradient(const QrEsGradient* g, void* stream);
+/* Bytes of workspace qr_es_gradient needs: P / 2 doubles; QR_E_SIZE (< 0) for an odd P, P < 2 or P > 8192. */
+int64_t qr_es_workspace_bytes(int32_t n_policies);
+
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);
 int  qr_abi_version(void);

@@ -20,6 +20,7 @@ from .sac import sac_actor_grad, sac_actor_loss, sac_actor_workspace_bytes, sac_
 from .sac import sac_critic_loss_ctde, sac_target_ctde  # noqa: F401
 from .sac import sac_actor_grad_ctde, sac_actor_loss_ctde, sac_actor_workspace_bytes_ctde  # noqa: F401
 from .noise import DeviceNoise, noise_fill  # noqa: F401
+from .shuffle import ppo_stream, shuffle  # noqa: F401
 from .episodes import EpisodeTracker, episode_scan, episode_workspace_numel  # noqa: F401
 from .offpolicy import OffPolicyCollector, SacUpdater, Td3Updater  # noqa: F401
 from .ppo import PpoCollector  # noqa: F401

@@ -42,7 +42,7 @@ SYMBOLS = ("qr_step", "qr_rollout", "qr_rollout_actor", "qr_error_obs", "qr_erro
            "qr_ctde_sac_actor_grad", "qr_ctde_sac_actor_workspace_bytes",
            "qr_replay_add", "qr_replay_add_rule", "qr_replay_sample", "qr_noise_fill",
            "qr_episode_scan", "qr_episode_workspace_bytes", "qr_gae_rule", "qr_gae_rule_workspace_bytes",
-           "qr_es_perturb", "qr_es_gradient", "qr_es_workspace_bytes")
+           "qr_es_perturb", "qr_es_gradient", "qr_es_workspace_bytes", "qr_shuffle", "qr_ppo_actor_grad_dev")
 
 
 class QrCoeffs(C.Structure):
@@ -383,6 +383,22 @@ def noise_fill_args(tensors, kinds, a, b, streams, *, seed, draw, draw_dev) -> Q
     return f
 
 
+SHUFFLE_ROUNDS, SHUFFLE_MIX_M1, SHUFFLE_MIX_M2 = 8, 0x7FEB352D, 0x846CA68B   # qr_shuffle: Feistel rounds, the finaliser's multipliers
+SHUFFLE_MAX_N = 2 ** 32                  # n lies below it
+
+
+class QrShuffle(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("draw_dev", C.c_void_p), ("n", C.c_int64), ("first", C.c_int64), ("count", C.c_int64),
+                ("seed", C.c_uint64), ("draw", C.c_int64), ("stream", C.c_uint32), ("max_workgroups", C.c_int32)]
+
+
+def shuffle_args(out, *, n, first, seed, draw, draw_dev, stream, max_workgroups=0) -> QrShuffle:
+    """QrShuffle of one qr_shuffle launch: out an int64 tensor (its numel is the count); draw_dev: a device int64 tensor of one
+    element or None."""
+    return QrShuffle(ptr(out) if out.numel() else None, ptr(draw_dev), int(n), int(first), out.numel(), int(seed) & (2 ** 64 - 1), int(draw),
+                     int(stream), int(max_workgroups))
+
+
 # qr_episode_scan: the QR_EP_* indices of `last` / `total` (agent g's field at index + g), the flag bits of ep_flags
 EP_COUNT, EP_RETURN_SUM, EP_RETURN_SQ, EP_RETURN_MIN, EP_RETURN_MAX, EP_LENGTH_SUM, EP_LENGTH_MAX = 0, 1, 3, 5, 7, 9, 10
 EP_DONE, EP_TRUNCATED, EP_SOLVED, EP_EX_SUM, EP_EB1_SUM, EP_FIELDS, EP_STEPS_SEEN, EP_TOTAL_FIELDS = 11, 13, 14, 16, 17, 18, 18, 19
@@ -680,6 +696,8 @@ def load():
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.qr_ppo_actor_grad.restype = C.c_int
     lib.qr_ppo_actor_grad.argtypes = [P(QrActor), P(QrPpoBatch), P(QrPpoGrad), C.c_void_p]
+    lib.qr_ppo_actor_grad_dev.restype = C.c_int
+    lib.qr_ppo_actor_grad_dev.argtypes = [P(QrActor), P(QrPpoBatch), P(QrPpoGrad), C.c_void_p, C.c_void_p]
     lib.qr_ppo_actor_workspace_bytes.restype = C.c_int64
     lib.qr_ppo_actor_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]
     lib.qr_ppo_critic_grad.restype = C.c_int
@@ -732,6 +750,8 @@ def load():
     lib.qr_replay_sample.argtypes = [P(QrReplaySample), C.c_void_p]
     lib.qr_noise_fill.restype = C.c_int
     lib.qr_noise_fill.argtypes = [P(QrNoiseFill), C.c_void_p]
+    lib.qr_shuffle.restype = C.c_int
+    lib.qr_shuffle.argtypes = [P(QrShuffle), C.c_void_p]
     lib.qr_episode_scan.restype = C.c_int
     lib.qr_episode_scan.argtypes = [P(QrEpisodeScan), C.c_void_p]
     lib.qr_episode_workspace_bytes.restype = C.c_int64

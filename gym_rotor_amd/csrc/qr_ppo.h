@@ -365,6 +365,7 @@ struct PpoReduceArgs {
   int32_t n_parts, np, action_dim;
   double B;
   float entropy_coef, lam_T, lam_S, lam_M;
+  const float* entropy_coef_dev;   // null: `entropy_coef` above; else the coefficient is *entropy_coef_dev (read only: qr_ppo_actor_grad_dev)
 };
 
 // Entry e of the result = the sum over the partial vectors of entry e, in float64 and in an order the grid alone fixes: Q entries
@@ -398,7 +399,8 @@ __global__ __launch_bounds__(256) void ppo_reduce_kernel(const PpoReduceArgs o) 
 #pragma unroll
       for (int k = 1; k < 7; ++k)
         if (e >= o.off[k]) { dst = o.grad[k]; base = o.off[k]; }
-      dst[e - base] = (float)(e >= o.off[6] ? v - (double)o.entropy_coef : v);  // dH / dlog_std = 1 per component
+      const float entropy_coef = o.entropy_coef_dev ? *o.entropy_coef_dev : o.entropy_coef;
+      dst[e - base] = (float)(e >= o.off[6] ? v - (double)entropy_coef : v);  // dH / dlog_std = 1 per component
     }
     return;
   }
@@ -406,10 +408,11 @@ __global__ __launch_bounds__(256) void ppo_reduce_kernel(const PpoReduceArgs o) 
   ppo_block_sum<8>(o, red, o.off[7] + (t & 7), valid);
   if (t == 0) {
     const double na = o.B * o.action_dim;
+    const float entropy_coef = o.entropy_coef_dev ? *o.entropy_coef_dev : o.entropy_coef;
     double H = 0.0;
     for (int j = 0; j < o.action_dim; ++j) H += 0.5 + 0.91893853320467274 + (double)o.log_std[j];
     const double reg = ((double)o.lam_T * red[3] + (double)o.lam_S * red[4] + (double)o.lam_M * red[5]) / na;
-    o.stats[0] = (float)(-red[0] / o.B - (double)o.entropy_coef * H + reg);
+    o.stats[0] = (float)(-red[0] / o.B - (double)entropy_coef * H + reg);
     o.stats[1] = (float)(red[0] / o.B);
     o.stats[2] = (float)(red[1] / o.B);
     o.stats[3] = (float)(red[2] / o.B);

@@ -60,6 +60,8 @@
 //                  replay_advance_kernel (the opt-in device counters)
 //   qr_noise.h     the library's noise source (qr_noise_fill): up to sixteen normal or uniform tensors of a TD3 / SAC iteration from one
 //                  counter-based stream in one launch: noise_fill_kernel
+//   qr_shuffle.h   a keyed permutation of [0, n), PPO's epoch shuffle (qr_shuffle): a cycle-walking Feistel network under keys from the
+//                  noise stream, no sort and no state: shuffle_kernel
 //   qr_episode.h   the training curve from a collected horizon's rows (qr_episode_scan): per-episode return, length, end flags and final
 //                  error, and their statistics: episode_scan_kernel, episode_reduce_kernel
 //   qr_gae.h       PPO's advantages over the done flag the reference stores at the time limit, their per-agent statistics and their
@@ -96,6 +98,7 @@
 #include "qr_sac_actor.h"
 #include "qr_replay.h"
 #include "qr_noise.h"
+#include "qr_shuffle.h"
 #include "qr_episode.h"
 #include "qr_gae.h"
 #include "qr_es.h"
@@ -187,7 +190,8 @@ static int actor_grad_launch(const QrActor* p, Args& a, RArgs& r, bool log_std, 
   return (int)hipGetLastError();
 }
 
-static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* g, void* stream) {
+// entropy_coef_dev: NULL (qr_ppo_actor_grad), or the device float the reduce launch reads instead of b->entropy_coef
+static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* g, const float* entropy_coef_dev, void* stream) {
   if (!c || !b || !g) return QR_E_NULL;
   const bool sizes_ok = b->n_steps >= 1 && b->n_envs >= 1 && b->row_stride >= 1 && b->adv_stride >= 1 && b->col_offset >= 0 &&
                         b->col_offset + c->action_dim <= b->row_stride && !(b->final_obs && b->n_agents < 1);
@@ -204,11 +208,11 @@ static int do_ppo_actor(const QrActor* c, const QrPpoBatch* b, const QrPpoGrad* 
   a.clip = b->clip; a.max_action = b->max_action; a.lam_T = b->lam_T; a.lam_S = b->lam_S; a.lam_M = b->lam_M;
   PpoReduceArgs r{};
   r.stats = g->stats; r.log_std = c->log_std; r.action_dim = c->action_dim; r.B = (double)b->batch;
-  r.entropy_coef = b->entropy_coef; r.lam_T = b->lam_T; r.lam_S = b->lam_S; r.lam_M = b->lam_M;
+  r.entropy_coef = b->entropy_coef; r.entropy_coef_dev = entropy_coef_dev; r.lam_T = b->lam_T; r.lam_S = b->lam_S; r.lam_M = b->lam_M;
   float* const grads[7] = {g->fc1_w, g->fc1_b, g->fc2_w, g->fc2_b, g->mean_w, g->mean_b, g->log_std};
   static void (*const kernel[3])(PpoArgs) = {ppo_actor_kernel<23, 16, 4>, ppo_actor_kernel<15, 16, 4>, ppo_actor_kernel<3, 4, 1>};
   return actor_grad_launch(c, a, r, true, sizes_ok, supplied_ok,
-                           {g->stats, b->obs, b->final_obs, b->action, b->logp_old, b->advantage, b->noise, b->nominal}, grads, 7,
+                           {g->stats, b->obs, b->final_obs, b->action, b->logp_old, b->advantage, b->noise, b->nominal, entropy_coef_dev}, grads, 7,
                            b->workspace_bytes, b->max_workgroups, kPpoNP, kernel, ppo_reduce_kernel, 4, stream);
 }
 
@@ -803,6 +807,21 @@ static int do_noise_fill(const QrNoiseFill* n, void* stream) {
   return (int)hipGetLastError();
 }
 
+static int do_shuffle(const QrShuffle* p, void* stream) {
+  if (!p) return QR_E_NULL;
+  if (p->n < 1 || p->n > 0xFFFFFFFFll || p->first < 0 || p->count < 0 || p->first > p->n || p->count > p->n - p->first) return QR_E_SIZE;
+  if (p->stream >= (1u << 30) || p->max_workgroups < 0 || (!p->draw_dev && p->draw < 0)) return QR_E_SIZE;
+  if (p->count == 0) return 0;
+  if (!p->out) return QR_E_NULL;
+  if ((reinterpret_cast<uintptr_t>(p->out) | reinterpret_cast<uintptr_t>(p->draw_dev)) & 7u) return QR_E_ALIGN;
+  uint32_t w = 1;
+  while (w < 16 && (1ull << (2 * w)) < (uint64_t)p->n) ++w;
+  const ShuffleArgs a{p->out, p->draw_dev, p->draw, p->seed, (uint32_t)p->n, (uint32_t)p->first, (uint32_t)p->count, p->stream, w};
+  const int64_t blocks = (p->count + kShuffleBlock - 1) / kShuffleBlock, cap = p->max_workgroups > 0 ? p->max_workgroups : kShuffleGrid;
+  hipLaunchKernelGGL(shuffle_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(kShuffleBlock), 0, reinterpret_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
 static int do_episode_scan(const QrEpisodeScan* e, void* stream) {
   if (!e) return QR_E_NULL;
   const bool two = e->n_agents == 2;
@@ -1007,6 +1026,7 @@ int64_t qr_episode_workspace_bytes(int64_t n_envs) {
 }
 
 int qr_noise_fill(const QrNoiseFill* fill, void* stream) { return qr::do_noise_fill(fill, stream); }
+int qr_shuffle(const QrShuffle* shuffle, void* stream) { return qr::do_shuffle(shuffle, stream); }
 
 int qr_replay_add(const QrReplayAdd* add, void* stream) { return qr::do_replay_add(add, nullptr, stream); }
 
@@ -1113,7 +1133,10 @@ int64_t qr_ppo_critic_workspace_bytes(int32_t in_dim, int32_t hidden_dim, int64_
 }
 
 int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream) {
-  return qr::do_ppo_actor(actor, batch, grad, stream);
+  return qr::do_ppo_actor(actor, batch, grad, nullptr, stream);
+}
+int qr_ppo_actor_grad_dev(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, const float* entropy_coef_dev, void* stream) {
+  return qr::do_ppo_actor(actor, batch, grad, entropy_coef_dev, stream);
 }
 
 int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups) {

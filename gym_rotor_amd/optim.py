@@ -13,7 +13,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .noise import check_seed, noise_fill
 from .policy import actor_loss, critic_loss
+from .shuffle import ppo_stream, shuffle
 
 
 def _f32(v) -> float:
@@ -329,6 +331,10 @@ def minibatch_slices(n_rows: int, batch_size: int):
     return [slice(i, min(i + batch_size, n_rows)) for i in range(0, n_rows, batch_size)]
 
 
+SOURCES = ("torch", "device")        # who shuffles and who draws: torch's generator, or the library's keyed streams (shuffle.py, noise.py)
+NOISE_STD = 0.05                     # policy_regularization's N(0, 0.05) row (policy_regularization.py:21)
+
+
 class PpoUpdater:
     """`PPO.train`'s update loop (ppo.py:148-214) for all agents of an env kind, after `compute_gae` / `normalize`: per agent and
     epoch one shuffle, then the actor's minibatches (`actor_loss`, then a `DeviceAdamW` step), then the critic's (`critic_loss`, then
@@ -340,16 +346,35 @@ class PpoUpdater:
     place; actor_opts / critic_opts: their `DeviceAdamW`s; critic_inputs: per agent the observation rows its critic reads ((k,) by
     default, (0, 1) for CTDE).  noise / nominal: per agent the [D_k] draw of the spatial term and the [A_k] nominal action
     (`RolloutStorage.nominal_action`), required when lam_S / lam_M != 0; the noise tensor is read at every minibatch, so the caller
-    may refill it in place between updates.  The hyperparameters are the reference's names and defaults (args_parse.py:65-78)."""
+    may refill it in place between updates.  The hyperparameters are the reference's names and defaults (args_parse.py:65-78).
+
+    shuffle_source / noise_source ("torch" by default: the behaviour and the bits described above).  "device" takes the epoch's
+    permutation from `shuffle` into one kept [rows] buffer, and draws agent k's [D_k] noise row afresh before EVERY actor minibatch,
+    as the reference does, with `noise_fill(kind="normal", a=0, b=noise_std)` into a tensor the updater owns (`noise=` is then
+    refused) — both keyed by `seed`, the streams `ppo_stream(k, "shuffle")` / `ppo_stream(k, "noise")` and two draw numbers that
+    live on the device: `state` int64 [2] = the shuffles and the noise rows drawn so far, each advanced by an in-place add behind its
+    reader (host copies: `epoch_draw`, `minibatch_draw`).  With either device source the entropy coefficient is also kept in the
+    float32 device word `entropy_dev`, set from the host's value after each decay and read by the launch (`entropy_coef_dev=`): the
+    float32 the by-value path would pass.  So nothing in an epoch depends on a host value, and `capture` can record it."""
 
     def __init__(self, actors, critics, actor_opts, critic_opts, *, critic_inputs=None, K_epochs: int = 20, actor_batch_size: int = 128,
                  critic_batch_size: int = 128, clip: float = 0.2, entropy_coef: float = 1e-2, entropy_coef_decay: float = 0.99,
                  l2_reg: float = 1e-4, lam_T: float = 0.4, lam_S: float = 0.3, lam_M: float = 0.6, noise=None, nominal=None,
-                 max_action: float = 1.0):
+                 max_action: float = 1.0, shuffle_source: str = "torch", noise_source: str = "torch", seed: int = 0,
+                 noise_std: float = NOISE_STD):
         self.actors, self.critics, self.actor_opts, self.critic_opts = list(actors), list(critics), list(actor_opts), list(critic_opts)
         n = len(self.actors)
         if n < 1 or not (len(self.critics) == len(self.actor_opts) == len(self.critic_opts) == n):
             raise ValueError("PpoUpdater needs one actor, critic, actor optimiser and critic optimiser per agent")
+        for name, v in (("shuffle_source", shuffle_source), ("noise_source", noise_source)):
+            if v not in SOURCES:
+                raise ValueError(f"PpoUpdater: {name} must be one of {SOURCES}, got {v!r}")
+        self.shuffle_source, self.noise_source, self.seed = shuffle_source, noise_source, check_seed("PpoUpdater", seed)
+        self.noise_std = float(noise_std)
+        if not 0.0 <= self.noise_std <= 3.4028234663852886e38:
+            raise ValueError(f"PpoUpdater: noise_std must be a finite float32 number >= 0, got {noise_std}")
+        if noise_source == "device" and noise is not None:
+            raise ValueError("PpoUpdater: noise_source='device' draws the noise rows itself; it takes no noise=")
         self.critic_inputs = [tuple(i) for i in critic_inputs] if critic_inputs is not None else [(k,) for k in range(n)]
         self.noise = list(noise) if noise is not None else [None] * n
         self.nominal = list(nominal) if nominal is not None else [None] * n
@@ -360,37 +385,143 @@ class PpoUpdater:
         self.K_epochs, self.actor_batch_size, self.critic_batch_size = int(K_epochs), int(actor_batch_size), int(critic_batch_size)
         self.clip, self.entropy_coef, self.entropy_coef_decay, self.l2_reg = float(clip), float(entropy_coef), float(entropy_coef_decay), float(l2_reg)
         self.lam_T, self.lam_S, self.lam_M, self.max_action = float(lam_T), float(lam_S), float(lam_M), float(max_action)
-        dev = self.actor_opts[0].device
+        dev = self.device = self.actor_opts[0].device
         self.actor_stats = [torch.zeros(4, dtype=torch.float32, device=dev) for _ in range(n)]
         self.critic_stats = [torch.zeros(4, dtype=torch.float32, device=dev) for _ in range(n)]
+        self.device_sources = "device" in (shuffle_source, noise_source)
+        self.epoch_draw, self.minibatch_draw = 0, 0
+        self.state, self.entropy_dev, self._perm, self._rows = None, None, None, None
+        if self.device_sources:
+            self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.entropy_dev = torch.full((1,), self.entropy_coef, dtype=torch.float32, device=dev)
+        if noise_source == "device":
+            self.noise = [torch.zeros(m.fc1.weight.shape[1], dtype=torch.float32, device=dev) for m in self.actors]
+
+    def _epoch(self, storage, advantage: torch.Tensor, k: int, generator) -> None:
+        """One epoch of agent k: the shuffle, then its minibatches.  With the device sources every launch reads what it needs on the
+        device, so this is also what `capture` records."""
+        rows = storage.T * storage.N
+        a_kw = dict(clip=self.clip, entropy_coef=self.entropy_coef, lam_T=self.lam_T, lam_S=self.lam_S, lam_M=self.lam_M,
+                    noise=self.noise[k], nominal=self.nominal[k], max_action=self.max_action, stats=self.actor_stats[k])
+        if self.device_sources:
+            a_kw["entropy_coef_dev"] = self.entropy_dev
+        c_kw = dict(inputs=self.critic_inputs[k], l2_reg=self.l2_reg, stats=self.critic_stats[k])
+        actor, critic, opt_a, opt_c = self.actors[k], self.critics[k], self.actor_opts[k], self.critic_opts[k]
+        if self.shuffle_source == "device":
+            perm = shuffle(self._perm, n=rows, seed=self.seed, draw=self.epoch_draw, stream=ppo_stream(k, "shuffle"), draw_dev=self.state[0:1])
+            self.state[0:1].add_(1)                       # behind its reader, on the same stream
+            self.epoch_draw += 1
+        else:
+            perm = torch.randperm(rows, device=storage.device, generator=generator)
+
+        def actor_minibatch(sl):
+            if self.noise_source == "device":
+                noise_fill([self.noise[k]], seed=self.seed, draw=self.minibatch_draw, streams=[ppo_stream(k, "noise")], kind="normal", a=0.0,
+                           b=self.noise_std, draw_dev=self.state[1:2])
+                self.state[1:2].add_(1)
+                self.minibatch_draw += 1
+            actor_loss(actor, storage, k, advantage, perm[sl], **a_kw)
+
+        if self.actor_batch_size == self.critic_batch_size:
+            both = [opt_a, opt_c]
+            for sl in minibatch_slices(rows, self.actor_batch_size):
+                actor_minibatch(sl)
+                critic_loss(critic, storage, k, perm[sl], **c_kw)
+                DeviceAdamW.step_all(both)
+        else:
+            for sl in minibatch_slices(rows, self.actor_batch_size):
+                actor_minibatch(sl)
+                opt_a.step()
+            for sl in minibatch_slices(rows, self.critic_batch_size):
+                critic_loss(critic, storage, k, perm[sl], **c_kw)
+                opt_c.step()
+
+    def _decay(self) -> None:
+        """The host's decay (ppo.py:149) and, with a device source, the word the launches read: the float32 of the host's value."""
+        self.entropy_coef *= self.entropy_coef_decay
+        if self.entropy_dev is not None:
+            self.entropy_dev.fill_(self.entropy_coef)
 
     def update(self, storage, advantage: torch.Tensor, generator: Optional[torch.Generator] = None):
         """One PPO update from `storage` (after compute_gae: td_target is read from it) and the normalised `advantage`
         [T, N, n_agents].  Returns (actor_stats, critic_stats): per agent the stats tensors of the last minibatch, on the device,
-        no synchronisation.  From the second call on nothing is allocated but the permutations."""
+        no synchronisation.  From the second call on nothing is allocated but the permutations — and with shuffle_source="device",
+        which takes no generator, nothing at all."""
         if storage.n_agents != len(self.actors):
             raise ValueError(f"the storage has {storage.n_agents} agents, the updater {len(self.actors)}")
+        if generator is not None and self.shuffle_source == "device":
+            raise ValueError("PpoUpdater.update: shuffle_source='device' shuffles from the library's own stream (seed); it takes no torch generator")
         rows = storage.T * storage.N
-        self.entropy_coef *= self.entropy_coef_decay
-        a_slices, c_slices = minibatch_slices(rows, self.actor_batch_size), minibatch_slices(rows, self.critic_batch_size)
+        if self.shuffle_source == "device" and (self._perm is None or self._perm.numel() != rows):
+            self._perm = torch.zeros(rows, dtype=torch.int64, device=storage.device)
+        self._rows = rows
+        self._decay()
         for k in range(len(self.actors)):
-            a_kw = dict(clip=self.clip, entropy_coef=self.entropy_coef, lam_T=self.lam_T, lam_S=self.lam_S, lam_M=self.lam_M,
-                        noise=self.noise[k], nominal=self.nominal[k], max_action=self.max_action, stats=self.actor_stats[k])
-            c_kw = dict(inputs=self.critic_inputs[k], l2_reg=self.l2_reg, stats=self.critic_stats[k])
-            actor, critic, opt_a, opt_c = self.actors[k], self.critics[k], self.actor_opts[k], self.critic_opts[k]
             for _ in range(self.K_epochs):
-                perm = torch.randperm(rows, device=storage.device, generator=generator)
-                if self.actor_batch_size == self.critic_batch_size:
-                    both = [opt_a, opt_c]
-                    for sl in a_slices:
-                        actor_loss(actor, storage, k, advantage, perm[sl], **a_kw)
-                        critic_loss(critic, storage, k, perm[sl], **c_kw)
-                        DeviceAdamW.step_all(both)
-                else:
-                    for sl in a_slices:
-                        actor_loss(actor, storage, k, advantage, perm[sl], **a_kw)
-                        opt_a.step()
-                    for sl in c_slices:
-                        critic_loss(critic, storage, k, perm[sl], **c_kw)
-                        opt_c.step()
+                self._epoch(storage, advantage, k, generator)
         return self.actor_stats, self.critic_stats
+
+    def _grad_addresses(self):
+        """The address of every parameter's .grad, None where there is none: what a recorded epoch writes and steps from."""
+        return [None if p.grad is None else p.grad.data_ptr() for o in self.actor_opts + self.critic_opts for p in o.params]
+
+    def capture(self, storage, advantage: torch.Tensor):
+        """Record ONE epoch per agent — the shuffle, then per minibatch the noise row, `actor_loss`, `critic_loss`, the optimiser
+        step(s) and the counter adds, a linear chain of launches — in one `torch.cuda.graph` each, and return a callable that
+        performs one whole update: the host's entropy decay and the fill of its device word, then per agent K_epochs replays of that
+        agent's graph, then the host counters.  It returns `update`'s stats tensors.  `storage` and `advantage` are read in place: a
+        later `collect` / `compute_gae` into the same tensors is what the next call trains on.  Needs both device sources and one
+        eager `update` on this storage before it, which makes the workspaces, the .grad tensors and the permutation buffer.
+        Capturing runs nothing and leaves the host counters where they were.  The callable raises ValueError where a parameter's
+        .grad has been rebound since (the graphs write and read the recorded tensors)."""
+        if self.shuffle_source != "device" or self.noise_source != "device":
+            raise ValueError("PpoUpdater.capture needs shuffle_source='device' and noise_source='device': a replay cannot follow torch's generator")
+        if storage.n_agents != len(self.actors):
+            raise ValueError(f"the storage has {storage.n_agents} agents, the updater {len(self.actors)}")
+        if self._rows is None or self._perm is None or None in self._grad_addresses():
+            raise ValueError("PpoUpdater.capture: run update() on this storage once first (it makes the workspaces the graphs record)")
+        rows = storage.T * storage.N
+        if rows != self._rows:
+            raise ValueError(f"PpoUpdater.capture: the storage holds T * N = {rows} rows, the last update ran on {self._rows}")
+        if self.device.type != "cuda":
+            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        host = (self.epoch_draw, self.minibatch_draw)
+        graphs = []
+        torch.cuda.synchronize(self.device)
+        for k in range(len(self.actors)):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._epoch(storage, advantage, k, None)
+            graphs.append(graph)
+        per_update = tuple(c - h for c, h in zip((self.epoch_draw, self.minibatch_draw), host))   # one epoch of every agent
+        self.epoch_draw, self.minibatch_draw = host                                               # nothing ran
+        grads = self._grad_addresses()
+
+        def replay():
+            if self._grad_addresses() != grads:
+                raise ValueError("PpoUpdater.capture: a parameter's .grad was rebound after the capture; capture again")
+            self._decay()
+            for graph in graphs:
+                for _ in range(self.K_epochs):
+                    graph.replay()
+            self.epoch_draw += per_update[0] * self.K_epochs
+            self.minibatch_draw += per_update[1] * self.K_epochs
+            return self.actor_stats, self.critic_stats
+
+        replay.graphs = graphs
+        return replay
+
+    def state_dict(self) -> dict:
+        return {"seed": self.seed, "epoch_draw": self.epoch_draw, "minibatch_draw": self.minibatch_draw, "entropy_coef": self.entropy_coef}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copies into the existing device tensors (their addresses stay: a captured graph keeps working — under the seed it was
+        recorded with: the seed is a launch argument)."""
+        seed, e, m = check_seed("PpoUpdater.load_state_dict", state["seed"]), int(state["epoch_draw"]), int(state["minibatch_draw"])
+        if not (0 <= e < 2 ** 63 and 0 <= m < 2 ** 63):
+            raise ValueError("PpoUpdater.load_state_dict: the draw numbers must lie in [0, 2^63)")
+        self.seed, self.epoch_draw, self.minibatch_draw, self.entropy_coef = seed, e, m, float(state["entropy_coef"])
+        if self.state is not None:
+            self.state.copy_(torch.tensor([e, m], dtype=torch.int64))
+            self.entropy_dev.fill_(self.entropy_coef)
+

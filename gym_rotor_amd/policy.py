@@ -386,7 +386,7 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
                    truncated: Optional[torch.Tensor] = None, clip: float = 0.2, entropy_coef: float = 0.0, lam_T: float = 0.0,
                    lam_S: float = 0.0, lam_M: float = 0.0, noise: Optional[torch.Tensor] = None, nominal: Optional[torch.Tensor] = None,
                    max_action: float = 1.0, col_offset: int = 0, grads: Optional[dict] = None, stats: Optional[torch.Tensor] = None,
-                   workspace: Optional[torch.Tensor] = None, max_workgroups: int = 0):
+                   workspace: Optional[torch.Tensor] = None, max_workgroups: int = 0, entropy_coef_dev: Optional[torch.Tensor] = None):
     """PPO's actor loss (ppo.py:169-182 + policy_regularization.py) and its gradients for ONE agent and one minibatch, in one launch
     plus a small reduction (qr_ppo_actor_grad) — no autograd, no copies of the minibatch's rows.
     obs [T+1, N, D] contiguous float32 (the storage's rows of this agent); action / logp_old [T, N, ..]: this agent's columns start at
@@ -394,7 +394,9 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
     advantage: float32, T * N elements with one element stride (`advantage[..., k]`); index: int64 [B] rows of the flat [T * N]
     transitions, None = all of them in order.  final_obs [T, N, D] with done [T, N, n_agents] (and truncated [T, N]) give the
     reference's obs_next for lam_T (without them: obs[t + 1]).  noise [D]: the ONE draw of N(0, 0.05) the spatial term adds to every
-    row (required when lam_S != 0); nominal [A]: `RolloutStorage.nominal_action` (required when lam_M != 0).
+    row (required when lam_S != 0); nominal [A]: `RolloutStorage.nominal_action` (required when lam_M != 0).  entropy_coef_dev: a
+    float32 tensor of one element on obs' device that the launch reads the entropy coefficient from, instead of `entropy_coef`
+    (qr_ppo_actor_grad_dev: the bits of passing that float by value; a captured launch follows the word).
     Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std — `grads` given:
     overwritten in place — and stats float32 [4] = loss, mean surrogate, clip fraction, mean of (rho - 1) - log rho."""
     dev = obs.device
@@ -448,6 +450,9 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
             raise ValueError(f"ppo_actor_grad: {name} is required when lam_{'S' if name == 'noise' else 'M'} != 0")
         _vector(t, n, dev, "ppo_actor_grad", name)
         vecs[name] = t
+    if entropy_coef_dev is not None and (not isinstance(entropy_coef_dev, torch.Tensor) or entropy_coef_dev.dtype != torch.float32 or
+                                         entropy_coef_dev.device != dev or entropy_coef_dev.numel() != 1):
+        raise ValueError(f"ppo_actor_grad: entropy_coef_dev must be a float32 tensor of one element on {dev}")
     shapes = _GRAD_SHAPES(D, H, A)
     grads, stats, workspace = _grad_outputs("ppo_actor_grad", shapes, dev, B, grads, stats, workspace,
                                             lambda: ppo_workspace_bytes((D, H, A), B, max_workgroups))
@@ -464,8 +469,12 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
     g = _lib.QrPpoGrad(*[grads[n].data_ptr() for n in _lib.PPO_GRAD_NAMES], stats.data_ptr())
     q = actor.as_c()
     with torch.cuda.device(dev):
-        rc = _lib.load().qr_ppo_actor_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ppo_actor_grad")
+        if entropy_coef_dev is None:
+            rc = _lib.load().qr_ppo_actor_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = _lib.load().qr_ppo_actor_grad_dev(C.byref(q), C.byref(b), C.byref(g), entropy_coef_dev.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "qr_ppo_actor_grad" if entropy_coef_dev is None else "qr_ppo_actor_grad_dev")
     return grads, stats
 
 
@@ -473,6 +482,7 @@ def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional
     """The actor update of a training loop, as the reference writes it, without autograd: runs `storage.actor_grad` for agent k on the
     live `module` (attributes fc1, fc2, mean_linear, log_std — its tensors are read in place) and writes the gradients into
     `module.<param>.grad` in place (log_std in the module's [1, A] shape), as `loss.backward()` after `zero_grad()` leaves them.
+    coeffs: `RolloutStorage.actor_grad`'s, among them entropy_coef_dev= (the coefficient read from a device word).
     Returns stats (stats[0] = the loss).  Gradient clipping, the optimiser step and the schedule follow on these .grad tensors: `optim.DeviceAdamW` (one launch), or torch's."""
     params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.mean_linear.weight, module.mean_linear.bias,
               module.log_std)

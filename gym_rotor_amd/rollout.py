@@ -231,7 +231,7 @@ class RolloutStorage:
         all of them) in one launch that reads this storage in place (`policy.ppo_actor_grad`): obs[k], the agent's columns of
         the shared action / logprob rows, final_obs / done / truncated for the reference's obs_next.  advantage: [T, N, n_agents]
         (agent k's column is taken) or [T, N].  coeffs: clip, entropy_coef, lam_T, lam_S, lam_M, noise, nominal, max_action, grads,
-        stats, max_workgroups.  The workspace is kept per (agent, B, max_workgroups).  Returns (grads, stats)."""
+        stats, max_workgroups, entropy_coef_dev (a float32 device word read instead of entropy_coef).  The workspace is kept per (agent, B, max_workgroups).  Returns (grads, stats)."""
         from .policy import ppo_actor_grad, ppo_workspace_bytes
         k = int(k)
         if not 0 <= k < self.n_agents:

@@ -329,6 +329,24 @@ def qr_ppo_actor_grad(actor: List[torch.Tensor], obs: torch.Tensor, final_obs: O
                    max_workgroups=max_workgroups)
 
 
+@torch.library.custom_op(f"{_NS}::qr_ppo_actor_grad_dev", mutates_args=("grads", "stats"))
+def qr_ppo_actor_grad_dev(actor: List[torch.Tensor], obs: torch.Tensor, final_obs: Optional[torch.Tensor], done: Optional[torch.Tensor],
+                          truncated: Optional[torch.Tensor], action: torch.Tensor, logp_old: torch.Tensor, advantage: torch.Tensor,
+                          index: Optional[torch.Tensor], noise: Optional[torch.Tensor], nominal: Optional[torch.Tensor],
+                          grads: List[torch.Tensor], stats: torch.Tensor, entropy_coef_dev: torch.Tensor, col_offset: int, clip: float,
+                          lam_T: float, lam_S: float, lam_M: float, max_action: float, max_workgroups: int = 0) -> None:
+    """qr_ppo_actor_grad with the entropy coefficient read from the float32 device tensor of one element `entropy_coef_dev`
+    (qr_ppo_actor_grad_dev); everything else as that op."""
+    from .policy import ActorParams, ppo_actor_grad
+    _gpu(obs)
+    if len(actor) != 7 or len(grads) != 7:
+        raise ValueError("the actor and its gradients are 7 tensors each: fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std")
+    ppo_actor_grad(ActorParams(*actor[:6], actor[6].reshape(-1)), obs, action, logp_old, advantage, index, final_obs=final_obs, done=done,
+                   truncated=truncated, clip=clip, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, noise=noise, nominal=nominal, max_action=max_action,
+                   col_offset=col_offset, grads=dict(zip(_lib.PPO_GRAD_NAMES, grads)), stats=stats, max_workgroups=max_workgroups,
+                   entropy_coef_dev=entropy_coef_dev)
+
+
 @torch.library.custom_op(f"{_NS}::qr_ppo_critic_grad", mutates_args=("grads", "stats"))
 def qr_ppo_critic_grad(critic: List[torch.Tensor], inputs: List[int], obs0: Optional[torch.Tensor], obs1: Optional[torch.Tensor],
                        target: torch.Tensor, index: Optional[torch.Tensor], grads: List[torch.Tensor], stats: torch.Tensor,
@@ -485,6 +503,16 @@ def qr_noise_fill(tensors: List[torch.Tensor], kinds: List[int], a: List[float],
     if any(k not in (0, 1) for k in kinds):
         raise ValueError("kinds are 0 (normal) or 1 (uniform)")
     noise_fill(list(tensors), seed=seed, draw=draw, streams=list(streams), kind=[KINDS[k] for k in kinds], a=list(a), b=list(b), draw_dev=draw_dev)
+
+
+@torch.library.custom_op(f"{_NS}::qr_shuffle", mutates_args=("out",))
+def qr_shuffle(out: torch.Tensor, n: int, first: int, seed: int, draw: int, stream: int, draw_dev: Optional[torch.Tensor],
+               max_workgroups: int = 0) -> None:
+    """out[i] = perm(first + i), the keyed permutation of [0, n) (qr_shuffle), as shuffle.shuffle; seed and draw are passed as int64
+    here (0 <= seed, draw < 2^63).  draw_dev: an int64 device tensor of one element that is read as the draw number, or None."""
+    from .shuffle import shuffle
+    _gpu(out)
+    shuffle(out, n=n, seed=seed, draw=draw, stream=stream, first=first, draw_dev=draw_dev, max_workgroups=max_workgroups)
 
 
 @torch.library.custom_op(f"{_NS}::qr_es_perturb", mutates_args=("out", "copy_dst"))

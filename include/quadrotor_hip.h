@@ -468,6 +468,11 @@ typedef struct QrPpoGrad {
  * < 1, a column offset outside the row, max_workgroups < 0 or a workspace that is too small; QR_E_ALIGN for a float pointer that is
  * not 4-byte aligned or an index / workspace pointer that is not 8-byte aligned.  Nothing is launched on an error. */
 int qr_ppo_actor_grad(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, void* stream);
+/* The same with the entropy coefficient in device memory: entropy_coef_dev not NULL — the reduce launch READS the coefficient from that
+ * float (it is never written) and batch->entropy_coef is ignored, so that a recorded launch follows a coefficient that decays between
+ * replays; with the word holding c the result is, bit for bit, qr_ppo_actor_grad's with entropy_coef = c.  NULL: qr_ppo_actor_grad
+ * itself.  The errors are that entry's, and QR_E_ALIGN for an entropy_coef_dev that is not 4-byte aligned. */
+int qr_ppo_actor_grad_dev(const QrActor* actor, const QrPpoBatch* batch, const QrPpoGrad* grad, const float* entropy_coef_dev, void* stream);
 /* Bytes of workspace qr_ppo_actor_grad needs for this actor size, batch and max_workgroups; QR_E_SIZE (< 0) where it would refuse them. */
 int64_t qr_ppo_actor_workspace_bytes(int32_t obs_dim, int32_t hidden_dim, int32_t action_dim, int64_t batch, int32_t max_workgroups);
 
@@ -1303,6 +1308,41 @@ typedef struct QrEsGradient {
 int     qr_es_gradient(const QrEsGradient* g, void* stream);
 /* Bytes of workspace qr_es_gradient needs: P / 2 doubles; QR_E_SIZE (< 0) for an odd P, P < 2 or P > 8192. */
 int64_t qr_es_workspace_bytes(int32_t n_policies);
+
+/* ---- A keyed permutation of [0, n): PPO's epoch shuffle (ppo.py:158) with no sort, no state and no stored table ----
+ *     out[i] = perm(first + i)   for i < count, as int64
+ * perm is a bijection of [0, n) and a function of (seed, draw, stream, n) ALONE: not of the grid, of first / count (a slice holds the
+ * same values as those positions of the whole, so a rank can form just its own rows), of other calls or of torch's generator.
+ *   n = 1: perm = {0}.  Otherwise w = the smallest integer in 1..16 with 2^(2w) >= n (so 2^(2w) < 4 n), and perm(i) walks a balanced
+ *   Feistel network P on 2w bits from x = i: x = P(x) until x < n (cycle walking: the walk follows a cycle of P that holds i < n, so it
+ *   ends; a pass succeeds with probability n / 4^w > 1/4, the expected number of extra passes is below 3).
+ *   P: (L, R) = (x >> w, x & (2^w - 1)); QR_SHUFFLE_ROUNDS = 8 rounds r = 0 .. 7 of (L, R) <- (R, L ^ F_r(R)); P(x) = L << w | R.
+ *   F_r(v) = mix32(v + key[r]) >> (32 - w), the sum modulo 2^32, with the 32-bit multiply-xorshift finaliser
+ *       mix32(x): x ^= x >> 16; x *= QR_SHUFFLE_MIX_M1; x ^= x >> 15; x *= QR_SHUFFLE_MIX_M2; x ^= x >> 16.
+ *   key[4k .. 4k + 3] = the four raw Philox4x32-10 words of quad k of the qr_noise_fill stream for the triple
+ *   seed, draw, stream (QrNoiseFill's counter layout; the words before they become floats).  A (seed, draw, stream) triple used here
+ *   must not be used for a noise tensor as well.
+ * Deviation from numpy / torch.randperm: another family of permutations (a keyed cipher, not Fisher-Yates or a sort of random keys),
+ * and nothing is stored: element i costs a handful of passes wherever and whenever it is formed.
+ * draw_dev: NULL, or one device int64 that the launch READS as the draw number (never written); `draw` is then ignored.
+ * One launch: one thread per element, the grid min(ceil(count / 256), max_workgroups) with max_workgroups = 0: 1024, then strided —
+ * the grid cannot change a value.  count = 0: nothing is launched (out may be NULL). */
+#define QR_SHUFFLE_ROUNDS 8
+#define QR_SHUFFLE_MIX_M1 0x7FEB352Du
+#define QR_SHUFFLE_MIX_M2 0x846CA68Bu
+typedef struct QrShuffle {
+  int64_t* out;                   /* [count], written; 8-byte aligned */
+  const int64_t* draw_dev;        /* NULL, or one device int64 that is READ as the draw number (never written) */
+  int64_t n, first, count;        /* 1 <= n < 2^32; 0 <= first, 0 <= count, first + count <= n */
+  uint64_t seed;
+  int64_t draw;                   /* the draw number where draw_dev is NULL: >= 0 */
+  uint32_t stream;                /* < 2^30 */
+  int32_t max_workgroups;         /* 0: the library's choice (1024); > 0: a cap on the grid */
+} QrShuffle;
+/* In this order, all before the launch: QR_E_NULL for a NULL struct; QR_E_SIZE for n outside [1, 2^32), first < 0, count < 0,
+ * first + count > n, a stream >= 2^30, max_workgroups < 0 or a negative draw where draw_dev is NULL; then count = 0 returns 0;
+ * QR_E_NULL for a NULL out; QR_E_ALIGN for an out or draw_dev that is not 8-byte aligned.  Nothing is launched or written on an error. */
+int qr_shuffle(const QrShuffle* shuffle, void* stream);
 
 /* Host-side helpers (no device work). */
 void qr_default_coeffs(QrCoeffs* c);

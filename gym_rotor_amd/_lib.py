@@ -8,6 +8,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Optional
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QR_LIB overrides the path for measurement builds (the span build, tools/build_ab.sh A/B builds) only.
@@ -131,6 +134,40 @@ PPO_CRITIC_GRAD_NAMES = ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")  
 
 class QrCriticGrad(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_CRITIC_GRAD_NAMES + ("stats",)]
+
+
+def ppo_batch_args(obs, action, logp_old, advantage, workspace, *, final_obs=None, done=None, truncated=None, index=None, noise=None, nominal=None,
+                   batch, n_envs, n_steps, n_agents, row_stride, col_offset, adv_stride, max_workgroups, clip, entropy_coef, lam_T, lam_S, lam_M,
+                   max_action) -> QrPpoBatch:
+    """QrPpoBatch of one qr_ppo_actor_grad launch; final_obs, done, truncated, index, noise, nominal: tensors or None."""
+    b = QrPpoBatch()
+    b.obs, b.final_obs, b.done, b.truncated = ptr(obs), ptr(final_obs), ptr(done), ptr(truncated)
+    b.action, b.logp_old, b.advantage, b.index = ptr(action), ptr(logp_old), ptr(advantage), ptr(index)
+    b.noise, b.nominal = ptr(noise), ptr(nominal)
+    b.workspace, b.workspace_bytes = ptr(workspace), workspace.numel() * workspace.element_size()
+    b.batch, b.n_envs, b.n_steps, b.n_agents = int(batch), int(n_envs), int(n_steps), int(n_agents)
+    b.row_stride, b.col_offset, b.adv_stride, b.max_workgroups = int(row_stride), int(col_offset), int(adv_stride), int(max_workgroups)
+    b.clip, b.entropy_coef, b.lam_T, b.lam_S, b.lam_M, b.max_action = (float(v) for v in (clip, entropy_coef, lam_T, lam_S, lam_M, max_action))
+    return b
+
+
+def ppo_grad_args(grads, stats) -> QrPpoGrad:
+    """QrPpoGrad of one qr_ppo_actor_grad launch: grads = {name: tensor} over PPO_GRAD_NAMES."""
+    return QrPpoGrad(*[grads[n].data_ptr() for n in PPO_GRAD_NAMES], stats.data_ptr())
+
+
+def critic_batch_args(obs0, obs1, target, workspace, *, index=None, batch, rows, target_stride, max_workgroups, l2_reg) -> QrCriticBatch:
+    """QrCriticBatch of one qr_ppo_critic_grad launch; obs0 / obs1: the row tensors the critic reads, None for one it does not."""
+    b = QrCriticBatch()
+    b.obs0, b.obs1, b.target, b.index = ptr(obs0), ptr(obs1), ptr(target), ptr(index)
+    b.workspace, b.workspace_bytes = ptr(workspace), workspace.numel() * workspace.element_size()
+    b.batch, b.rows, b.target_stride, b.max_workgroups, b.l2_reg = int(batch), int(rows), int(target_stride), int(max_workgroups), float(l2_reg)
+    return b
+
+
+def critic_grad_args(grads, stats) -> QrCriticGrad:
+    """QrCriticGrad of one qr_ppo_critic_grad launch: grads = {name: tensor} over PPO_CRITIC_GRAD_NAMES."""
+    return QrCriticGrad(*[grads[n].data_ptr() for n in PPO_CRITIC_GRAD_NAMES], stats.data_ptr())
 
 
 QCRITIC_MAX_IN, QCRITIC_MAX_HIDDEN = 28, 64   # qr_twinq_target / qr_twinq_grad: widest obs_dim + action_dim, widest hidden layer
@@ -560,9 +597,10 @@ def ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def adamw_group(g: QrAdamWGroup, params, grads, exp_avg, exp_avg_sq, step, stats, *, lr, eta_min, t0, betas, eps, weight_decay, max_norm):
+def adamw_group(g: Optional[QrAdamWGroup], params, grads, exp_avg, exp_avg_sq, step, stats, *, lr, eta_min, t0, betas, eps, weight_decay, max_norm):
     """Fill the QrAdamWGroup `g` of one optimiser step: the parameter tensors and their gradients (1..8 of each, in the order of the
-    flat moment buffers), the state tensors, the hyperparameters.  Returns g."""
+    flat moment buffers), the state tensors, the hyperparameters.  g None: a fresh struct.  Returns g."""
+    g = QrAdamWGroup() if g is None else g
     g.n_tensors = len(params)
     for k, (p, d) in enumerate(zip(params, grads)):
         g.param[k], g.grad[k], g.count[k] = p.data_ptr(), d.data_ptr(), p.numel()
@@ -586,10 +624,11 @@ class QrAdamWPolyakGroup(C.Structure):
                 ("tau", C.c_double)]
 
 
-def adamw_polyak_group(g: QrAdamWPolyakGroup, params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, *, tau, lr, eta_min, t0, betas,
+def adamw_polyak_group(g: Optional[QrAdamWPolyakGroup], params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, *, tau, lr, eta_min, t0, betas,
                        eps, weight_decay, max_norm):
     """Fill the QrAdamWPolyakGroup `g` of one step: as adamw_group with 1..16 tensors, plus per parameter its target tensor or None
-    (targets = None: none at all), the exp output (or None) and tau.  Returns g."""
+    (targets = None: none at all), the exp output (or None) and tau.  g None: a fresh struct.  Returns g."""
+    g = QrAdamWPolyakGroup() if g is None else g
     g.n_tensors, g.reserved0 = len(params), 0
     for k, (p, d) in enumerate(zip(params, grads)):
         g.param[k], g.grad[k], g.count[k] = p.data_ptr(), d.data_ptr(), p.numel()
@@ -796,6 +835,27 @@ def check(rc: int, what: str):
     if rc < 0:
         raise ValueError(f"{what}: {ERRORS.get(rc, rc)}")
     raise QuadrotorLibError(f"{what}: hipError_t {rc}")
+
+
+_byref, _Structure = C.byref, C.Structure
+
+
+def launch(dev, name: str, *args) -> None:
+    """One library launch outside the env's hot path: entry `name` on `dev`'s current stream, under torch.cuda.device(dev).  A
+    ctypes.Structure goes by reference; None, ints, floats, pointers and ctypes arrays go as they are; the stream is appended.
+    The return code goes through `check`."""
+    args = [_byref(a) if isinstance(a, _Structure) else a for a in args]
+    with torch.cuda.device(dev):
+        rc = getattr(load(), name)(*args, torch.cuda.current_stream(dev).cuda_stream)
+    if rc:
+        check(rc, name)
+
+
+def workspace_bytes(name: str, *ints) -> int:
+    """The size query `name` (a qr_*_workspace_bytes entry) of the given integers; a refusal (negative) goes through `check`."""
+    n = getattr(load(), name)(*(int(i) for i in ints))
+    check(n if n < 0 else 0, name)
+    return int(n)
 
 
 def launch_thresholds() -> dict:

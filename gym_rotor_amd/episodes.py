@@ -14,12 +14,12 @@ step; here the float32 rewards are summed in float64 and never rounded (at most 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .td3 import TimeLimitRule
 
@@ -40,16 +40,12 @@ def _check(what, reward, done, truncated, run_return, run_length, last, total, f
     dev = reward.device
     if na not in (1, 2) or T < 1:
         raise ValueError(f"{what}: one or two agents and T >= 1, got reward of shape {tuple(reward.shape)}")
-
-    def need(x, shape, dtype, name):
-        if not isinstance(x, torch.Tensor) or x.dtype != dtype or x.device != dev or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous {dtype} {shape} tensor on {dev}")
-    need(done, (T, N, na), torch.bool, "done")
-    need(truncated, (T, N), torch.bool, "truncated")
-    need(run_return, (N, na), torch.float64, "run_return")
-    need(run_length, (N,), torch.int32, "run_length")
-    need(last, (K,), torch.float64, "last")
-    need(total, (KT,), torch.float64, "total")
+    ck.tensor(what, "done", done, torch.bool, (T, N, na), dev)
+    ck.tensor(what, "truncated", truncated, torch.bool, (T, N), dev)
+    ck.tensor(what, "run_return", run_return, torch.float64, (N, na), dev)
+    ck.tensor(what, "run_length", run_length, torch.int32, (N,), dev)
+    ck.tensor(what, "last", last, torch.float64, (K,), dev)
+    ck.tensor(what, "total", total, torch.float64, (KT,), dev)
     if final_obs is not None:
         final_obs = [final_obs] if isinstance(final_obs, torch.Tensor) else list(final_obs)
         if len(final_obs) != na:
@@ -57,18 +53,13 @@ def _check(what, reward, done, truncated, run_return, run_length, last, total, f
         for k, f in enumerate(final_obs):
             if not isinstance(f, torch.Tensor) or f.dim() != 3 or f.shape[-1] < (3 if k == 0 else 1):
                 raise ValueError(f"{what}: final_obs[{k}] must be [T, N, D] with D >= {3 if k == 0 else 1} (ex is three words, eb1 one)")
-            need(f, (T, N, f.shape[-1]), torch.float32, f"final_obs[{k}]")
-    shapes = {"ep_return": ((T, N, na), torch.float64), "ep_length": ((T, N), torch.int32), "ep_flags": ((T, N), torch.uint8),
-              "ep_final_error": ((T, N, 4), torch.float32)}
-    for name, x in zip(DENSE_NAMES, dense):
-        if x is not None:
-            need(x, *shapes[name], name)
+            ck.tensor(what, f"final_obs[{k}]", f, torch.float32, (T, N, f.shape[-1]), dev)
+    shapes = ((torch.float64, (T, N, na)), (torch.int32, (T, N)), (torch.uint8, (T, N)), (torch.float32, (T, N, 4)))
+    for name, x, (dtype, shape) in zip(DENSE_NAMES, dense, shapes):
+        ck.tensor(what, name, x, dtype, shape, dev, True)
     if dense[3] is not None and final_obs is None:
         raise ValueError(f"{what}: ep_final_error needs final_obs")
-    if workspace is not None:
-        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.device != dev or workspace.dim() != 1 or \
-                not workspace.is_contiguous() or workspace.numel() < episode_workspace_numel(N):
-            raise ValueError(f"{what}: workspace must be a contiguous float64 tensor of at least {episode_workspace_numel(N)} elements on {dev}")
+    ck.workspace(what, workspace, episode_workspace_numel(N), dev)
     return T, N, na, final_obs
 
 
@@ -92,15 +83,12 @@ def episode_scan(reward, done, truncated, run_return, run_length, last, total, *
     dense = (ep_return, ep_length, ep_flags, ep_final_error)
     T, N, na, final_obs = _check(what, reward, done, truncated, run_return, run_length, last, total, final_obs, dense, workspace)
     dev = reward.device
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    ck.require_gpu(dev)
     if workspace is None:
         workspace = torch.empty(episode_workspace_numel(N), dtype=torch.float64, device=dev)
     e = _lib.episode_scan_args(reward, done, truncated, final_obs, run_return, run_length, dense, last, total, workspace, n_steps=T, n_envs=N,
                                n_agents=na, x_lim=rule.x_lim, pos_tol=rule.pos_tol, rot_tol=rule.rot_tol, record=record)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_episode_scan(C.byref(e), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_episode_scan")
+    _lib.launch(dev, "qr_episode_scan", e)
     return last
 
 

@@ -17,10 +17,11 @@ from typing import List, Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .noise import check_seed
 from .optim import DeviceAdamW
-from .policy import ACTOR_DIMS, ActorParams, ActorPopulation, _WEIGHTS, population_layout, population_view
+from .policy import ACTOR_DIMS, ActorParams, ActorPopulation, _WEIGHTS, module_grads, population_layout, population_view
 
 NAMES = _WEIGHTS                      # the perturbed tensors of an actor, in stream order
 SHAPINGS = tuple(_lib.ES_SHAPING_ID)
@@ -39,9 +40,7 @@ def es_stream(k: int, name: str) -> int:
 
 def es_workspace_numel(n_policies: int) -> int:
     """float64 elements of workspace one `es_gradient` call needs (qr_es_workspace_bytes / 8)."""
-    n = _lib.load().qr_es_workspace_bytes(int(n_policies))
-    _lib.check(n if n < 0 else 0, "qr_es_workspace_bytes")
-    return int(n) // 8
+    return _lib.workspace_bytes("qr_es_workspace_bytes", n_policies) // 8
 
 
 def population_like(base_actors: Sequence[ActorParams], n: int) -> ActorPopulation:
@@ -69,8 +68,7 @@ def _check_key(what: str, n_policies, sigma, seed, generation, streams, n_tensor
     gen_dev = None
     if isinstance(generation, torch.Tensor):
         gen_dev, generation = generation, 0
-        if gen_dev.dtype != torch.int64 or gen_dev.numel() != 1 or gen_dev.device != dev:
-            raise ValueError(f"{what}: a generation on the device must be an int64 tensor of one element on {dev}")
+        ck.scalar(what, "a generation on the device", gen_dev, torch.int64, dev)
     else:
         generation = int(generation)
         if not 0 <= generation < 2 ** 63:
@@ -113,13 +111,9 @@ def es_perturb_tensors(base: Sequence[torch.Tensor], out: Sequence[torch.Tensor]
                 or d.shape[0] != P or d.numel() != P * s.numel()):
             raise ValueError(f"{what}: {dn} must be a contiguous float32 [{P}, {s.numel()} elements] tensor on {dev}")
     _check_quads(what, base, P)
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    p = _lib.es_perturb_args(base, out, copies, streams, n_policies=P, sigma=sigma, seed=seed, generation=generation, generation_dev=gen_dev,
-                             max_workgroups=max_workgroups)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_es_perturb(C.byref(p), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_es_perturb")
+    ck.require_gpu(dev)
+    _lib.launch(dev, "qr_es_perturb", _lib.es_perturb_args(base, out, copies, streams, n_policies=P, sigma=sigma, seed=seed, generation=generation,
+                                                           generation_dev=gen_dev, max_workgroups=max_workgroups))
 
 
 def _default_streams(n_agents: int) -> List[int]:
@@ -207,17 +201,14 @@ def es_gradient(fitness: torch.Tensor, grads, *, sigma: float, seed: int, genera
     if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.device != dev
                                   or workspace.numel() < P // 2 or not workspace.is_contiguous()):
         raise ValueError(f"{what}: workspace must be a contiguous float64 tensor of at least {P // 2} elements on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    ck.require_gpu(dev)
     if stats is None:
         stats = torch.empty(_lib.ES_STATS, dtype=torch.float64, device=dev)
     if workspace is None:
         workspace = torch.empty(es_workspace_numel(P), dtype=torch.float64, device=dev)
     g = _lib.es_gradient_args(fitness, flat, stats, workspace, streams, shaping=shaping, n_policies=P, sigma=sigma, seed=seed,
                               generation=generation, generation_dev=gen_dev, max_workgroups=max_workgroups)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_es_gradient(C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_es_gradient")
+    _lib.launch(dev, "qr_es_gradient", g)
     return stats
 
 
@@ -331,12 +322,7 @@ class EvolutionStrategy:
         self.fitness_values = torch.zeros(P, dtype=torch.float32, device=dev)   # the last generation's fitness [P]
         self.stats = torch.zeros(_lib.ES_STATS, dtype=torch.float64, device=dev)
         self._workspace = torch.zeros(es_workspace_numel(P), dtype=torch.float64, device=dev)
-        self._grads = []
-        for params in self.params:
-            for p in params:
-                if p.grad is None or not p.grad.is_contiguous():
-                    p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            self._grads.append({n: p.grad for n, p in zip(NAMES, params)})
+        self._grads = [module_grads(NAMES, params) for params in self.params]
 
     def prepare_episodes(self) -> list:
         """Step (1): the prepared episodes (state, parameters, integrators, goal, generator state, episode index) into every policy's

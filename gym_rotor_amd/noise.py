@@ -11,12 +11,12 @@ device: with `draw_dev` the launch reads it there, which is what lets a captured
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 
 KINDS = tuple(_lib.NOISE_KIND_ID)
@@ -74,21 +74,14 @@ def noise_fill(tensors: Sequence[torch.Tensor], *, seed: int, draw: int, streams
     for i, t in enumerate(tensors):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() < 1:
             raise ValueError(f"{what}: tensors[{i}] must be a non-empty contiguous float32 tensor on {dev}")
-    if draw_dev is not None and (not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype != torch.int64 or draw_dev.device != dev or
-                                 draw_dev.numel() != 1):
-        raise ValueError(f"{what}: draw_dev must be an int64 tensor of one element on {dev}")
+    ck.scalar(what, "draw_dev", draw_dev, torch.int64, dev)
     m = _lib.NOISE_MAX_SLOTS
     if any(sum((t.numel() + 3) // 4 for t in tensors[i:i + m]) >= 2 ** 31 for i in range(0, n, m)):
         raise ValueError(f"{what}: a launch's sixteen tensors hold at most 2^31 - 1 quads of four elements")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        for i in range(0, n, m):
-            f = _lib.noise_fill_args(tensors[i:i + m], kinds[i:i + m], a[i:i + m], b[i:i + m], streams[i:i + m], seed=seed,
-                                     draw=0 if draw_dev is not None else draw, draw_dev=draw_dev)
-            _lib.check(lib.qr_noise_fill(C.byref(f), stream), "qr_noise_fill")
+    ck.require_gpu(dev)
+    for i in range(0, n, m):
+        _lib.launch(dev, "qr_noise_fill", _lib.noise_fill_args(tensors[i:i + m], kinds[i:i + m], a[i:i + m], b[i:i + m], streams[i:i + m], seed=seed,
+                                                               draw=0 if draw_dev is not None else draw, draw_dev=draw_dev))
 
 
 class DeviceNoise:
@@ -106,10 +99,7 @@ class DeviceNoise:
         self.draw_dev: Optional[torch.Tensor] = None
 
     def bind(self, counter: Optional[torch.Tensor]) -> "DeviceNoise":
-        if counter is not None and (not isinstance(counter, torch.Tensor) or counter.dtype != torch.int64 or counter.numel() != 1 or
-                                    counter.device != self.device):
-            raise ValueError(f"DeviceNoise.bind: the counter must be an int64 tensor of one element on {self.device}")
-        self.draw_dev = counter
+        self.draw_dev = ck.scalar("DeviceNoise.bind", "the counter", counter, torch.int64, self.device)
         return self
 
     def fill(self, tensors, *, streams: Optional[Sequence[int]] = None, kind="normal", a=0.0, b=1.0) -> None:

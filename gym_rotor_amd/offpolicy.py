@@ -19,6 +19,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .episodes import EpisodeTracker
 from .noise import check_seed, noise_fill
@@ -209,8 +210,7 @@ class _Updater:
             raise ValueError(f"{what}.capture: the buffer must keep its counters on the device (ReplayBuffer.use_device_state())")
         if self._dims != (tuple(buffer.obs_dims), tuple(buffer.action_dims), self.batch_size) or self.total_it == 0:
             raise ValueError(f"{what}.capture: run update() on this buffer once first (it makes the workspaces the graph records)")
-        if self.device.type != "cuda":
-            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        ck.require_gpu(self.device)
         graph = torch.cuda.CUDAGraph()
         if self.noise_source == "torch" and self.generator is not None and self.refill_noise and hasattr(graph, "register_generator_state"):
             graph.register_generator_state(self.generator)

@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .noise import check_seed, noise_fill
 from .policy import actor_loss, critic_loss
@@ -75,18 +76,22 @@ class DeviceAdamW:
         return dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm, t0=self.t0,
                     eta_min=self.eta_min)
 
-    def _fill(self) -> _lib.QrAdamWGroup:
-        """The launch struct of the next step, from the parameters' current .grad tensors."""
+    def _grads(self) -> list:
+        """The parameters' current .grad tensors, checked.  This runs once per minibatch for every parameter, so the test stands here
+        and `_checks.flat` only words the refusal."""
         grads = []
         for k, p in enumerate(self.params):
             g = p.grad
             if g is None:
-                raise ValueError(f"DeviceAdamW.step: parameter {k} has no .grad")
+                raise ValueError(f"{type(self).__name__}.step: parameter {k} has no .grad")
             if g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device or g.numel() != p.numel():
-                raise ValueError(f"DeviceAdamW.step: the .grad of parameter {k} must be a contiguous float32 tensor of {p.numel()} entries on "
-                                 f"{self.device}")
+                ck.flat(f"{type(self).__name__}.step", f"the .grad of parameter {k}", g, torch.float32, p.numel(), self.device)
             grads.append(g)
-        return _lib.adamw_group(self._group, self.params, grads, self.exp_avg, self.exp_avg_sq, self.step_count, self.stats, **self.hyper())
+        return grads
+
+    def _fill(self) -> _lib.QrAdamWGroup:
+        """The launch struct of the next step, from the parameters' current .grad tensors."""
+        return _lib.adamw_group(self._group, self.params, self._grads(), self.exp_avg, self.exp_avg_sq, self.step_count, self.stats, **self.hyper())
 
     def step(self) -> None:
         """One optimiser step (clip, AdamW, schedule) in one launch on the current stream."""
@@ -105,14 +110,10 @@ class DeviceAdamW:
         if len({id(o) for o in opts}) != len(opts):
             raise ValueError("DeviceAdamW.step_all: an optimiser appears twice")
         groups = [o._fill() for o in opts]
-        if dev.type != "cuda":
-            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for i in range(0, len(groups), _lib.ADAMW_MAX_GROUPS):
-                chunk = groups[i:i + _lib.ADAMW_MAX_GROUPS]
-                _lib.check(lib.qr_adamw_step((_lib.QrAdamWGroup * len(chunk))(*chunk), len(chunk), stream), "qr_adamw_step")
+        ck.require_gpu(dev)
+        for i in range(0, len(groups), _lib.ADAMW_MAX_GROUPS):
+            chunk = groups[i:i + _lib.ADAMW_MAX_GROUPS]
+            _lib.launch(dev, "qr_adamw_step", (_lib.QrAdamWGroup * len(chunk))(*chunk), len(chunk))
 
     @property
     def steps(self) -> int:
@@ -139,6 +140,24 @@ class DeviceAdamW:
             dst.copy_(state[name].reshape(dst.shape))
 
 
+def _check_pairs(what: str, params, grads, dev) -> None:
+    """`adamw_step`'s and `adamw_polyak_step`'s check of the parameters and their gradients."""
+    for k, (p, g) in enumerate(zip(params, grads)):
+        for kind, t in (("parameter", p), ("gradient", g)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel() or t.numel() < 1:
+                raise ValueError(f"{what}: {kind} {k} must be a contiguous float32 tensor of {p.numel()} >= 1 entries on {dev}")
+
+
+def _check_state(what: str, params, exp_avg, exp_avg_sq, step, stats, dev) -> int:
+    """... and of the state tensors; returns the parameters' entries together."""
+    total = sum(p.numel() for p in params)
+    ck.flat(what, "exp_avg", exp_avg, torch.float32, total, dev)
+    ck.flat(what, "exp_avg_sq", exp_avg_sq, torch.float32, total, dev)
+    ck.scalar(what, "step", step, torch.int64, dev, optional=False)
+    ck.flat(what, "stats", stats, torch.float32, 4, dev, True)
+    return total
+
+
 def adamw_step(params, grads, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor, stats: Optional[torch.Tensor], *, lr: float,
                betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, max_norm: float = -1.0, t0: int = 0, eta_min: float = 0.0) -> None:
     """One `qr_adamw_step` launch for ONE group on explicit tensors (what `DeviceAdamW.step` does with its own state and the
@@ -148,25 +167,12 @@ def adamw_step(params, grads, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, s
     if not 1 <= len(params) <= _lib.ADAMW_MAX_TENSORS or len(grads) != len(params):
         raise ValueError(f"adamw_step takes 1..{_lib.ADAMW_MAX_TENSORS} parameter tensors and as many gradients")
     dev = params[0].device
-    for k, (p, g) in enumerate(zip(params, grads)):
-        for what, t in (("parameter", p), ("gradient", g)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel() or t.numel() < 1:
-                raise ValueError(f"adamw_step: {what} {k} must be a contiguous float32 tensor of {p.numel()} >= 1 entries on {dev}")
-    total = sum(p.numel() for p in params)
-    for what, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != total:
-            raise ValueError(f"adamw_step: {what} must be a contiguous float32 tensor of {total} entries on {dev}")
-    if step.dtype != torch.int64 or step.numel() != 1 or step.device != dev:
-        raise ValueError(f"adamw_step: step must be an int64 tensor of one entry on {dev}")
-    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 4 or not stats.is_contiguous() or stats.device != dev):
-        raise ValueError(f"adamw_step: stats must be a contiguous float32 [4] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    g = _lib.adamw_group(_lib.QrAdamWGroup(), params, grads, exp_avg, exp_avg_sq, step, stats, lr=lr, eta_min=eta_min, t0=t0, betas=betas,
-                         eps=eps, weight_decay=weight_decay, max_norm=max_norm)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_adamw_step(C.byref(g), 1, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_adamw_step")
+    _check_pairs("adamw_step", params, grads, dev)
+    _check_state("adamw_step", params, exp_avg, exp_avg_sq, step, stats, dev)
+    ck.require_gpu(dev)
+    g = _lib.adamw_group(None, params, grads, exp_avg, exp_avg_sq, step, stats, lr=lr, eta_min=eta_min, t0=t0, betas=betas, eps=eps,
+                         weight_decay=weight_decay, max_norm=max_norm)
+    _lib.launch(dev, "qr_adamw_step", g, 1)
 
 
 class PolyakAdamW(DeviceAdamW):
@@ -234,16 +240,7 @@ class PolyakAdamW(DeviceAdamW):
 
     def _fill(self, polyak: bool = True) -> _lib.QrAdamWPolyakGroup:
         """The launch struct of the next step, from the parameters' current .grad tensors."""
-        grads = []
-        for k, p in enumerate(self.params):
-            g = p.grad
-            if g is None:
-                raise ValueError(f"PolyakAdamW.step: parameter {k} has no .grad")
-            if g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device or g.numel() != p.numel():
-                raise ValueError(f"PolyakAdamW.step: the .grad of parameter {k} must be a contiguous float32 tensor of {p.numel()} entries on "
-                                 f"{self.device}")
-            grads.append(g)
-        return _lib.adamw_polyak_group(self._group, self.params, grads, self.targets if polyak else None, self.exp_avg, self.exp_avg_sq,
+        return _lib.adamw_polyak_group(self._group, self.params, self._grads(), self.targets if polyak else None, self.exp_avg, self.exp_avg_sq,
                                        self.step_count, self.stats, self.exp_out, tau=self.tau, **self.hyper())
 
     def step(self, polyak: bool = True) -> None:
@@ -266,14 +263,10 @@ class PolyakAdamW(DeviceAdamW):
         if len({id(o) for o, _ in pairs}) != len(pairs):
             raise ValueError("PolyakAdamW.step_all: an optimiser appears twice")
         groups = [o._fill(bool(polyak)) for o, polyak in pairs]
-        if dev.type != "cuda":
-            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for i in range(0, len(groups), _lib.POLYAK_MAX_GROUPS):
-                chunk = groups[i:i + _lib.POLYAK_MAX_GROUPS]
-                _lib.check(lib.qr_adamw_polyak_step((_lib.QrAdamWPolyakGroup * len(chunk))(*chunk), len(chunk), stream), "qr_adamw_polyak_step")
+        ck.require_gpu(dev)
+        for i in range(0, len(groups), _lib.POLYAK_MAX_GROUPS):
+            chunk = groups[i:i + _lib.POLYAK_MAX_GROUPS]
+            _lib.launch(dev, "qr_adamw_polyak_step", (_lib.QrAdamWPolyakGroup * len(chunk))(*chunk), len(chunk))
 
 
 def adamw_polyak_step(params, grads, targets, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, step: torch.Tensor, stats: Optional[torch.Tensor],
@@ -287,10 +280,8 @@ def adamw_polyak_step(params, grads, targets, exp_avg: torch.Tensor, exp_avg_sq:
     if not 1 <= len(params) <= _lib.POLYAK_MAX_TENSORS or len(grads) != len(params):
         raise ValueError(f"adamw_polyak_step takes 1..{_lib.POLYAK_MAX_TENSORS} parameter tensors and as many gradients")
     dev = params[0].device
-    for k, (p, g) in enumerate(zip(params, grads)):
-        for what, t in (("parameter", p), ("gradient", g)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != p.numel() or t.numel() < 1:
-                raise ValueError(f"adamw_polyak_step: {what} {k} must be a contiguous float32 tensor of {p.numel()} >= 1 entries on {dev}")
+    what = "adamw_polyak_step"
+    _check_pairs(what, params, grads, dev)
     if targets is not None:
         targets = list(targets)
         if len(targets) != len(params):
@@ -302,24 +293,14 @@ def adamw_polyak_step(params, grads, targets, exp_avg: torch.Tensor, exp_avg_sq:
                                  f"parameter itself")
     if not 0.0 <= float(tau) <= 1.0:
         raise ValueError(f"adamw_polyak_step: tau must lie in [0, 1], got {tau}")
-    total = sum(p.numel() for p in params)
-    for what, t in (("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != total:
-            raise ValueError(f"adamw_polyak_step: {what} must be a contiguous float32 tensor of {total} entries on {dev}")
-    if step.dtype != torch.int64 or step.numel() != 1 or step.device != dev:
-        raise ValueError(f"adamw_polyak_step: step must be an int64 tensor of one entry on {dev}")
-    if stats is not None and (stats.dtype != torch.float32 or stats.numel() != 4 or not stats.is_contiguous() or stats.device != dev):
-        raise ValueError(f"adamw_polyak_step: stats must be a contiguous float32 [4] tensor on {dev}")
+    total = _check_state(what, params, exp_avg, exp_avg_sq, step, stats, dev)
     if exp_out is not None and (total != 1 or exp_out.dtype != torch.float32 or exp_out.numel() != 1 or exp_out.device != dev
                                 or exp_out.data_ptr() == params[0].data_ptr()):
         raise ValueError(f"adamw_polyak_step: exp_out must be a float32 tensor of one entry on {dev}, for a group of one entry")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    g = _lib.adamw_polyak_group(_lib.QrAdamWPolyakGroup(), params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, tau=tau, lr=lr,
-                                eta_min=eta_min, t0=t0, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_adamw_polyak_step(C.byref(g), 1, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_adamw_polyak_step")
+    ck.require_gpu(dev)
+    g = _lib.adamw_polyak_group(None, params, grads, targets, exp_avg, exp_avg_sq, step, stats, exp_out, tau=tau, lr=lr, eta_min=eta_min, t0=t0,
+                                betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_norm)
+    _lib.launch(dev, "qr_adamw_polyak_step", g, 1)
 
 
 def minibatch_slices(n_rows: int, batch_size: int):
@@ -483,8 +464,7 @@ class PpoUpdater:
         rows = storage.T * storage.N
         if rows != self._rows:
             raise ValueError(f"PpoUpdater.capture: the storage holds T * N = {rows} rows, the last update ran on {self._rows}")
-        if self.device.type != "cuda":
-            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        ck.require_gpu(self.device)
         host = (self.epoch_draw, self.minibatch_draw)
         graphs = []
         torch.cuda.synchronize(self.device)

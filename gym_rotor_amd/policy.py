@@ -13,12 +13,12 @@ takes a live module, so an optimiser step is seen by the next rollout without an
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 
 # (obs_dim, hidden_dim, action_dim) per agent: main.py:68-73 + args_parse.py:40
@@ -241,35 +241,12 @@ class QCriticParams:
         return q
 
 
-def _element_stride(t: torch.Tensor, what: str) -> int:
-    """The one stride between consecutive elements of `t` in row-major order (a column of a contiguous [.., n_agents] tensor)."""
-    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]
-    for (_, s), (n1, s1) in zip(dims, dims[1:]):
-        if s != s1 * n1:
-            raise ValueError(f"{what} must have one element stride (a column of a contiguous tensor), got shape {tuple(t.shape)} strides {t.stride()}")
-    stride = dims[-1][1] if dims else 1
-    if stride < 1:
-        raise ValueError(f"{what} must have a positive element stride")
-    return stride
-
-
 def _critic_launch_args(critic: CriticParams, rows, n_rows: int, value: torch.Tensor, what: str):
     dev = value.device
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    ck.require_gpu(dev)
     if critic.device != dev:
         raise ValueError(f"{what}: the critic's tensors are on {critic.device}, the values on {dev}")
-    rows = list(rows) + [None] * (2 - len(rows))
-    widths = []
-    for k, r in enumerate(rows[:2]):
-        if r is None:
-            widths.append(0)
-            continue
-        if r.dtype != torch.float32 or r.device != dev or not r.is_contiguous() or r.dim() < 2 or r[..., 0].numel() != n_rows:
-            raise ValueError(f"{what}: observation rows {k} must be contiguous float32 [{n_rows} rows, D] on {dev}")
-        widths.append(r.shape[-1])
-    while widths and widths[-1] == 0:
-        widths.pop()
+    rows, widths = ck.obs_rows(what, rows, n_rows, dev)
     q = critic.as_c(widths)
     return q, (_lib.ptr(rows[0]) if q.in0 else None), (_lib.ptr(rows[1]) if q.in1 else None)
 
@@ -280,14 +257,11 @@ def critic_values(critic: CriticParams, obs, value: torch.Tensor) -> None:
     stride — e.g. `storage.value[..., k]`."""
     if value.dtype != torch.float32:
         raise ValueError("critic_values: value must be float32")
-    n_rows, stride = value.numel(), _element_stride(value, "value")
+    n_rows, stride = value.numel(), ck.element_stride("critic_values", "value", value)
     q, p0, p1 = _critic_launch_args(critic, obs, n_rows, value, "critic_values")
     if n_rows == 0:   # nothing to launch (and an empty tensor has no address to pass)
         return
-    with torch.cuda.device(value.device):
-        rc = _lib.load().qr_critic_values(C.byref(q), p0, p1, n_rows, value.data_ptr(), stride,
-                                          torch.cuda.current_stream(value.device).cuda_stream)
-    _lib.check(rc, "qr_critic_values")
+    _lib.launch(value.device, "qr_critic_values", q, p0, p1, n_rows, value.data_ptr(), stride)
 
 
 def critic_next_values(critic: CriticParams, final_obs, done: torch.Tensor, truncated: Optional[torch.Tensor], value: torch.Tensor,
@@ -301,23 +275,15 @@ def critic_next_values(critic: CriticParams, final_obs, done: torch.Tensor, trun
     dev = next_value.device
     if value.dtype != torch.float32 or next_value.dtype != torch.float32 or value.device != dev or tuple(value.shape) != (T + 1, N):
         raise ValueError(f"critic_next_values: value must be float32 [{T + 1}, {N}] and next_value float32 [{T}, {N}] on one device")
-    stride = _element_stride(next_value, "next_value")
-    if T * N > 1 and _element_stride(value, "value") != stride:
+    stride = ck.element_stride("critic_next_values", "next_value", next_value)
+    if T * N > 1 and ck.element_stride("critic_next_values", "value", value) != stride:
         raise ValueError("critic_next_values: value and next_value must have the same element stride")
-    flags = [("done", done, 3)] + ([("truncated", truncated, 2)] if truncated is not None else [])
-    for name, t, nd in flags:
-        if t.dtype not in (torch.bool, torch.uint8) or t.device != dev or not t.is_contiguous() or t.dim() != nd or tuple(t.shape[:2]) != (T, N):
-            raise ValueError(f"critic_next_values: {name} must be contiguous bool / uint8 [{T}, {N}{', n_agents' if nd == 3 else ''}] on {dev}")
-    if done.shape[2] < 1:
-        raise ValueError("critic_next_values: done needs at least one agent column")
+    n_agents = ck.reset_flags("critic_next_values", done, truncated, T, N, dev)
     q, p0, p1 = _critic_launch_args(critic, final_obs, T * N, next_value, "critic_next_values")
     if T >= 1 and N == 0:
         return
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_critic_next_values(C.byref(q), p0, p1, done.data_ptr(), done.shape[2], _lib.ptr(truncated), T, N,
-                                               value.data_ptr(), next_value.data_ptr(), stride,
-                                               torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_critic_next_values")
+    _lib.launch(dev, "qr_critic_next_values", q, p0, p1, done.data_ptr(), n_agents, _lib.ptr(truncated), T, N, value.data_ptr(),
+                next_value.data_ptr(), stride)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -329,14 +295,18 @@ _GRAD_SHAPES = lambda D, H, A: {"fc1_w": (H, D), "fc1_b": (H,), "fc2_w": (H, H),
 
 def ppo_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `ppo_actor_grad` launch needs (qr_ppo_actor_workspace_bytes)."""
-    n = _lib.load().qr_ppo_actor_workspace_bytes(int(dims[0]), int(dims[1]), int(dims[2]), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_ppo_actor_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_ppo_actor_workspace_bytes", dims[0], dims[1], dims[2], batch, max_workgroups)
 
 
-def _vector(t, width: int, dev, what: str, name: str):
-    if t is not None and (t.dtype != torch.float32 or t.device != dev or t.numel() != width or not t.is_contiguous()):
-        raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {width} elements on {dev}")
+def module_grads(names, params) -> dict:
+    """How the "on live modules" wrappers start: each parameter's .grad, made (zeros) where there is none or it is not contiguous —
+    what `loss.backward()` after `zero_grad()` leaves to write into.  Returns {name: p.grad} over `names` (parameters past the
+    names get their .grad too)."""
+    params = list(params)
+    for p in params:
+        if p.grad is None or not p.grad.is_contiguous():
+            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+    return {n: p.grad for n, p in zip(names, params)}
 
 
 def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace, workspace_bytes, size_given: bool = True, n_stats: int = 4):
@@ -347,16 +317,12 @@ def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace,
     to launch (and an empty tensor has no address to pass) — grads and stats are zero-filled and the caller returns them."""
     if grads is None:
         grads = {n: torch.empty(s, dtype=torch.float32, device=dev) for n, s in shapes.items()}
-    for n, s in shapes.items():
-        g = grads.get(n)
-        if g is None or g.dtype != torch.float32 or g.device != dev or g.numel() != torch.Size(s).numel() or not g.is_contiguous():
-            raise ValueError(f"{what}: grads[{n!r}] must be a contiguous float32 tensor of {torch.Size(s).numel()} elements (shape {s}) on {dev}")
+    ck.named(what, "grads[{!r}]", grads, shapes, dev, by_numel=True)
     if stats is None:
         stats = torch.empty(n_stats, dtype=torch.float32, device=dev)
-    elif stats.dtype != torch.float32 or stats.device != dev or stats.numel() != n_stats or not stats.is_contiguous():
-        raise ValueError(f"{what}: stats must be a contiguous float32 [{n_stats}] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    else:
+        ck.flat(what, "stats", stats, torch.float32, n_stats, dev)
+    ck.require_gpu(dev)
     if B == 0:
         for n in shapes:
             grads[n].zero_()
@@ -368,17 +334,6 @@ def _grad_outputs(what: str, shapes: dict, dev, B: int, grads, stats, workspace,
     elif workspace.device != dev or not workspace.is_contiguous():
         raise ValueError(f"{what}: workspace must be a contiguous tensor on {dev}")
     return grads, stats, workspace
-
-
-def _rows_view(t: torch.Tensor, T: int, N: int, A: int, col_offset: int, what: str, dev):
-    """Row stride of a float32 [T, N, >= col_offset + A] tensor whose rows lie one row stride apart (the storage's own [T, N, 5]
-    rows, or a per-agent view of them)."""
-    if t.dtype != torch.float32 or t.device != dev or t.dim() != 3 or tuple(t.shape[:2]) != (T, N) or t.shape[2] < col_offset + A:
-        raise ValueError(f"ppo_actor_grad: {what} must be float32 [{T}, {N}, >= {col_offset + A}] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    rs = t.stride(1)
-    if (t.shape[2] > 1 and t.stride(2) != 1) or rs < t.shape[2] or (T > 1 and t.stride(0) != N * rs):
-        raise ValueError(f"ppo_actor_grad: {what} must be rows of a contiguous [T, N, W] tensor, got strides {t.stride()}")
-    return rs
 
 
 def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, logp_old: torch.Tensor, advantage: torch.Tensor,
@@ -399,82 +354,61 @@ def ppo_actor_grad(actor: ActorParams, obs: torch.Tensor, action: torch.Tensor, 
     (qr_ppo_actor_grad_dev: the bits of passing that float by value; a captured launch follows the word).
     Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, mean_w, mean_b, log_std — `grads` given:
     overwritten in place — and stats float32 [4] = loss, mean surrogate, clip fraction, mean of (rho - 1) - log rho."""
+    what = "ppo_actor_grad"
     dev = obs.device
     if actor.dims not in PPO_ACTOR_DIMS:
-        raise ValueError(f"ppo_actor_grad: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
+        raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
     if actor.squash != _lib.ACTOR_TANH_MEAN or actor.log_std_w is not None or actor.log_std is None:
-        raise ValueError("ppo_actor_grad: the actor must be of MLP_Actor_PPO's form: the tanh-of-mean rule and a log_std parameter, no log_std head")
+        raise ValueError(f"{what}: the actor must be of MLP_Actor_PPO's form: the tanh-of-mean rule and a log_std parameter, no log_std head")
     actor.check(actor.dims, dev)
     D, H, A = actor.dims
     if obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[0] < 2 or obs.shape[2] != D or not obs.is_contiguous():
-        raise ValueError(f"ppo_actor_grad: obs must be contiguous float32 [T+1, N, {D}], got {obs.dtype} {tuple(obs.shape)}")
+        raise ValueError(f"{what}: obs must be contiguous float32 [T+1, N, {D}], got {obs.dtype} {tuple(obs.shape)}")
     T, N = obs.shape[0] - 1, obs.shape[1]
     if N < 1:
-        raise ValueError("ppo_actor_grad: obs holds no env")
+        raise ValueError(f"{what}: obs holds no env")
     col_offset = int(col_offset)
     if col_offset < 0:
-        raise ValueError("ppo_actor_grad: col_offset must be >= 0")
-    rs = _rows_view(action, T, N, A, col_offset, "action", dev)
-    if _rows_view(logp_old, T, N, A, col_offset, "logp_old", dev) != rs:
-        raise ValueError("ppo_actor_grad: action and logp_old must have the same row stride")
+        raise ValueError(f"{what}: col_offset must be >= 0")
+    rs = ck.rows_view(what, "action", action, T, N, A, col_offset, dev)
+    if ck.rows_view(what, "logp_old", logp_old, T, N, A, col_offset, dev) != rs:
+        raise ValueError(f"{what}: action and logp_old must have the same row stride")
     if advantage.dtype != torch.float32 or advantage.device != dev or advantage.numel() != T * N:
-        raise ValueError(f"ppo_actor_grad: advantage must be float32 with {T * N} elements on {dev}")
-    adv_stride = _element_stride(advantage, "advantage")
+        raise ValueError(f"{what}: advantage must be float32 with {T * N} elements on {dev}")
+    adv_stride = ck.element_stride(what, "advantage", advantage)
     n_agents = 0
     if final_obs is not None:
-        if final_obs.dtype != torch.float32 or final_obs.device != dev or tuple(final_obs.shape) != (T, N, D) or not final_obs.is_contiguous():
-            raise ValueError(f"ppo_actor_grad: final_obs must be contiguous float32 [{T}, {N}, {D}] on {dev}")
+        ck.tensor(what, "final_obs", final_obs, torch.float32, (T, N, D), dev)
         if done is None:
-            raise ValueError("ppo_actor_grad: final_obs needs done")
-        flags = [("done", done, 3)] + ([("truncated", truncated, 2)] if truncated is not None else [])
-        for name, t, nd in flags:
-            if t.dtype not in (torch.bool, torch.uint8) or t.device != dev or not t.is_contiguous() or t.dim() != nd or tuple(t.shape[:2]) != (T, N):
-                raise ValueError(f"ppo_actor_grad: {name} must be contiguous bool / uint8 [{T}, {N}{', n_agents' if nd == 3 else ''}] on {dev}")
-        n_agents = done.shape[2]
-        if n_agents < 1:
-            raise ValueError("ppo_actor_grad: done needs at least one agent column")
+            raise ValueError(f"{what}: final_obs needs done")
+        n_agents = ck.reset_flags(what, done, truncated, T, N, dev)
     else:
         done = truncated = None
-    if index is not None:
-        if index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous():
-            raise ValueError(f"ppo_actor_grad: index must be a contiguous int64 [B] tensor on {dev}")
-        B = index.numel()
-    else:
-        B = T * N
-    vecs = {}
-    for name, t, n, lam in (("noise", noise, D, lam_S), ("nominal", nominal, A, lam_M)):
-        if lam == 0:
-            vecs[name] = None
-            continue
-        if t is None:
-            raise ValueError(f"ppo_actor_grad: {name} is required when lam_{'S' if name == 'noise' else 'M'} != 0")
-        _vector(t, n, dev, "ppo_actor_grad", name)
-        vecs[name] = t
-    if entropy_coef_dev is not None and (not isinstance(entropy_coef_dev, torch.Tensor) or entropy_coef_dev.dtype != torch.float32 or
-                                         entropy_coef_dev.device != dev or entropy_coef_dev.numel() != 1):
-        raise ValueError(f"ppo_actor_grad: entropy_coef_dev must be a float32 tensor of one element on {dev}")
-    shapes = _GRAD_SHAPES(D, H, A)
-    grads, stats, workspace = _grad_outputs("ppo_actor_grad", shapes, dev, B, grads, stats, workspace,
+    B = ck.index(what, index, dev, T * N)
+    if lam_S == 0:
+        noise = None
+    elif noise is None:
+        raise ValueError(f"{what}: noise is required when lam_S != 0")
+    ck.flat(what, "noise", noise, torch.float32, D, dev, True)
+    if lam_M == 0:
+        nominal = None
+    elif nominal is None:
+        raise ValueError(f"{what}: nominal is required when lam_M != 0")
+    ck.flat(what, "nominal", nominal, torch.float32, A, dev, True)
+    ck.scalar(what, "entropy_coef_dev", entropy_coef_dev, torch.float32, dev)
+    grads, stats, workspace = _grad_outputs(what, _GRAD_SHAPES(D, H, A), dev, B, grads, stats, workspace,
                                             lambda: ppo_workspace_bytes((D, H, A), B, max_workgroups))
     if workspace is None:
         return grads, stats
-    b = _lib.QrPpoBatch()
-    b.obs, b.final_obs, b.done, b.truncated = obs.data_ptr(), _lib.ptr(final_obs), _lib.ptr(done), _lib.ptr(truncated)
-    b.action, b.logp_old, b.advantage, b.index = action.data_ptr(), logp_old.data_ptr(), advantage.data_ptr(), _lib.ptr(index)
-    b.noise, b.nominal = _lib.ptr(vecs["noise"]), _lib.ptr(vecs["nominal"])
-    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    b.batch, b.n_envs, b.n_steps, b.n_agents = B, N, T, n_agents
-    b.row_stride, b.col_offset, b.adv_stride, b.max_workgroups = rs, col_offset, adv_stride, int(max_workgroups)
-    b.clip, b.entropy_coef, b.lam_T, b.lam_S, b.lam_M, b.max_action = (float(v) for v in (clip, entropy_coef, lam_T, lam_S, lam_M, max_action))
-    g = _lib.QrPpoGrad(*[grads[n].data_ptr() for n in _lib.PPO_GRAD_NAMES], stats.data_ptr())
-    q = actor.as_c()
-    with torch.cuda.device(dev):
-        if entropy_coef_dev is None:
-            rc = _lib.load().qr_ppo_actor_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rc = _lib.load().qr_ppo_actor_grad_dev(C.byref(q), C.byref(b), C.byref(g), entropy_coef_dev.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ppo_actor_grad" if entropy_coef_dev is None else "qr_ppo_actor_grad_dev")
+    b = _lib.ppo_batch_args(obs, action, logp_old, advantage, workspace, final_obs=final_obs, done=done, truncated=truncated, index=index,
+                            noise=noise, nominal=nominal, batch=B, n_envs=N, n_steps=T, n_agents=n_agents, row_stride=rs, col_offset=col_offset,
+                            adv_stride=adv_stride, max_workgroups=max_workgroups, clip=clip, entropy_coef=entropy_coef, lam_T=lam_T, lam_S=lam_S,
+                            lam_M=lam_M, max_action=max_action)
+    g = _lib.ppo_grad_args(grads, stats)
+    if entropy_coef_dev is None:
+        _lib.launch(dev, "qr_ppo_actor_grad", actor.as_c(), b, g)
+    else:
+        _lib.launch(dev, "qr_ppo_actor_grad_dev", actor.as_c(), b, g, entropy_coef_dev.data_ptr())
     return grads, stats
 
 
@@ -484,13 +418,8 @@ def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional
     `module.<param>.grad` in place (log_std in the module's [1, A] shape), as `loss.backward()` after `zero_grad()` leaves them.
     coeffs: `RolloutStorage.actor_grad`'s, among them entropy_coef_dev= (the coefficient read from a device word).
     Returns stats (stats[0] = the loss).  Gradient clipping, the optimiser step and the schedule follow on these .grad tensors: `optim.DeviceAdamW` (one launch), or torch's."""
-    params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.mean_linear.weight, module.mean_linear.bias,
-              module.log_std)
-    grads = {}
-    for n, p in zip(_lib.PPO_GRAD_NAMES, params):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
+    grads = module_grads(_lib.PPO_GRAD_NAMES, (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.mean_linear.weight,
+                                               module.mean_linear.bias, module.log_std))
     _, stats = storage.actor_grad(k, ActorParams.from_module(module), advantage, index, grads=grads, **coeffs)
     return stats
 
@@ -500,9 +429,7 @@ def actor_loss(module, storage, k: int, advantage: torch.Tensor, index: Optional
 # ----------------------------------------------------------------------------------------------------------------
 def ppo_critic_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `ppo_critic_grad` launch needs (qr_ppo_critic_workspace_bytes); dims = (input width, hidden width)."""
-    n = _lib.load().qr_ppo_critic_workspace_bytes(int(dims[0]), int(dims[1]), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_ppo_critic_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_ppo_critic_workspace_bytes", dims[0], dims[1], batch, max_workgroups)
 
 
 def ppo_critic_grad(critic: CriticParams, obs, target: torch.Tensor, index: Optional[torch.Tensor] = None, *, l2_reg: float = 0.0,
@@ -518,46 +445,26 @@ def ppo_critic_grad(critic: CriticParams, obs, target: torch.Tensor, index: Opti
     Returns (grads, stats): grads = {name: float32 tensor} for fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b — `grads` given: overwritten
     in place — and stats float32 [4] = loss, mse, mean error, population variance of the minibatch's targets (explained variance =
     1 - (stats[1] - stats[2] ** 2) / stats[3])."""
+    what = "ppo_critic_grad"
     dev = target.device
     if target.dtype != torch.float32:
-        raise ValueError(f"ppo_critic_grad: target must be float32, got {target.dtype}")
-    rows, stride = target.numel(), _element_stride(target, "target")
+        raise ValueError(f"{what}: target must be float32, got {target.dtype}")
+    rows, stride = target.numel(), ck.element_stride(what, "target", target)
     if critic.device != dev:
-        raise ValueError(f"ppo_critic_grad: the critic's tensors are on {critic.device}, the target on {dev}")
-    obs = list(obs) + [None] * (2 - len(obs))
-    widths = []
-    for k, r in enumerate(obs[:2]):
-        if r is None:
-            widths.append(0)
-            continue
-        if r.dtype != torch.float32 or r.device != dev or not r.is_contiguous() or r.dim() < 2 or r[..., 0].numel() < rows:
-            raise ValueError(f"ppo_critic_grad: observation rows {k} must be contiguous float32 [>= {rows} rows, D] on {dev}")
-        widths.append(r.shape[-1])
-    while widths and widths[-1] == 0:
-        widths.pop()
+        raise ValueError(f"{what}: the critic's tensors are on {critic.device}, the target on {dev}")
+    obs, widths = ck.obs_rows(what, obs, rows, dev, at_least=True)
     q = critic.as_c(widths)
-    if index is not None:
-        if index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous():
-            raise ValueError(f"ppo_critic_grad: index must be a contiguous int64 [B] tensor on {dev}")
-        B = index.numel()
-    else:
-        B = rows
+    B = ck.index(what, index, dev, rows)
     if B and rows < 1:
-        raise ValueError("ppo_critic_grad: an index needs a target with at least one element")
+        raise ValueError(f"{what}: an index needs a target with at least one element")
     shapes = {n: tuple(getattr(critic, n).shape) for n in _lib.PPO_CRITIC_GRAD_NAMES}
-    grads, stats, workspace = _grad_outputs("ppo_critic_grad", shapes, dev, B, grads, stats, workspace,
+    grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
                                             lambda: ppo_critic_workspace_bytes(critic.dims, B, max_workgroups))
     if workspace is None:
         return grads, stats
-    b = _lib.QrCriticBatch()
-    b.obs0, b.obs1 = (_lib.ptr(obs[0]) if q.in0 else None), (_lib.ptr(obs[1]) if q.in1 else None)
-    b.target, b.index = target.data_ptr(), _lib.ptr(index)
-    b.workspace, b.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    b.batch, b.rows, b.target_stride, b.max_workgroups, b.l2_reg = B, rows, stride, int(max_workgroups), float(l2_reg)
-    g = _lib.QrCriticGrad(*[grads[n].data_ptr() for n in _lib.PPO_CRITIC_GRAD_NAMES], stats.data_ptr())
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_ppo_critic_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ppo_critic_grad")
+    b = _lib.critic_batch_args(obs[0] if q.in0 else None, obs[1] if q.in1 else None, target, workspace, index=index, batch=B, rows=rows,
+                               target_stride=stride, max_workgroups=max_workgroups, l2_reg=l2_reg)
+    _lib.launch(dev, "qr_ppo_critic_grad", q, b, _lib.critic_grad_args(grads, stats))
     return grads, stats
 
 
@@ -570,11 +477,7 @@ def critic_loss(module, storage, k: int, index: Optional[torch.Tensor] = None, i
     params = (module.fc1.weight, module.fc1.bias, module.fc2.weight, module.fc2.bias, module.fc3.weight, module.fc3.bias)
     if "grads" in coeffs:
         raise ValueError("critic_loss writes into the module's .grad tensors: it takes no grads")
-    grads = {}
-    for n, p in zip(_lib.PPO_CRITIC_GRAD_NAMES, params):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
+    grads = module_grads(_lib.PPO_CRITIC_GRAD_NAMES, params)
     _, stats = storage.critic_grad(k, CriticParams.from_module(module, inputs), index, grads=grads, **coeffs)
     return stats
 

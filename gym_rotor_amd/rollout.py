@@ -13,11 +13,11 @@ all-reduced over the env shards (RCCL when launched under torchrun; gloo in the 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .td3 import TIME_LIMITS, TimeLimitRule
 
@@ -48,61 +48,49 @@ def gae_rule(reward, done, value, advantage, td_target, *, gamma: float = 0.99, 
     dev = reward.device
     if na not in (1, 2) or T < 1:
         raise ValueError(f"{what}: one or two agents and T >= 1, got reward of shape {tuple(reward.shape)}")
-
-    def need(x, shape, dtypes, name):
-        dtypes = dtypes if isinstance(dtypes, tuple) else (dtypes,)
-        if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or x.device != dev or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous {dtypes[0]} {shape} tensor on {dev}")
-    need(done, (T, N, na), (torch.bool, torch.uint8), "done")
+    f32, flag = torch.float32, (torch.bool, torch.uint8)
+    ck.tensor(what, "done", done, flag, (T, N, na), dev)
     if next_value is None:
-        need(value, (T + 1, N, na), torch.float32, "value")
+        ck.tensor(what, "value", value, f32, (T + 1, N, na), dev)
     else:
         if not isinstance(value, torch.Tensor) or value.dim() != 3 or value.shape[0] not in (T, T + 1):
             raise ValueError(f"{what}: value must be [{T} or {T + 1}, {N}, {na}]")
-        need(value, (value.shape[0], N, na), torch.float32, "value")
-        need(next_value, (T, N, na), torch.float32, "next_value")
-    need(advantage, (T, N, na), torch.float32, "advantage")
-    need(td_target, (T, N, na), torch.float32, "td_target")
+        ck.tensor(what, "value", value, f32, (value.shape[0], N, na), dev)
+        ck.tensor(what, "next_value", next_value, f32, (T, N, na), dev)
+    ck.tensor(what, "advantage", advantage, f32, (T, N, na), dev)
+    ck.tensor(what, "td_target", td_target, f32, (T, N, na), dev)
     if rule is not None:
         rule = TimeLimitRule(*rule).check(what)
         if truncated is None or term_obs is None:
             raise ValueError(f"{what}: the time-limit rule needs truncated and term_obs, the rows that hold obs_next at the time limit")
-        need(truncated, (T, N), (torch.bool, torch.uint8), "truncated")
+        ck.tensor(what, "truncated", truncated, flag, (T, N), dev)
         term_obs = [term_obs] if isinstance(term_obs, torch.Tensor) else list(term_obs)
         if len(term_obs) != na:
             raise ValueError(f"{what}: term_obs is one [T, N, D_k] tensor per agent ({na}), got {len(term_obs)}")
         for k, f in enumerate(term_obs):
             if not isinstance(f, torch.Tensor) or f.dim() != 3 or f.shape[-1] < (3 if k == 0 else 1):
                 raise ValueError(f"{what}: term_obs[{k}] must be [T, N, D] with D >= {3 if k == 0 else 1} (ex is three words, eb1 one)")
-            need(f, (T, N, f.shape[-1]), torch.float32, f"term_obs[{k}]")
+            ck.tensor(what, f"term_obs[{k}]", f, f32, (T, N, f.shape[-1]), dev)
     else:
         truncated = term_obs = None
-    if done_eff is not None:
-        need(done_eff, (T, N, na), (torch.bool, torch.uint8), "done_eff")
+    ck.tensor(what, "done_eff", done_eff, flag, (T, N, na), dev, True)
     if normalized is not None:
-        need(normalized, (T, N, na), torch.float32, "normalized")
+        ck.tensor(what, "normalized", normalized, f32, (T, N, na), dev)
         if stats is None:
             raise ValueError(f"{what}: normalized needs stats")
         if T * N < 2:
             raise ValueError(f"{what}: normalized needs at least two transitions per agent (the unbiased std), got {T} x {N}")
-        if not (float(norm_eps) >= 0.0 and float(norm_eps) < float("inf")):
-            raise ValueError(f"{what}: norm_eps must be finite and >= 0, got {norm_eps}")
+        ck.nonneg(what, ("norm_eps",), norm_eps)
     if stats is not None:
-        need(stats, (na, 3), torch.float64, "stats")
-        numel = gae_rule_workspace_numel(N, na)
-        if workspace is not None and (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or workspace.device != dev or
-                                      workspace.dim() != 1 or not workspace.is_contiguous() or workspace.numel() < numel):
-            raise ValueError(f"{what}: workspace must be a contiguous float64 tensor of at least {numel} elements on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        ck.tensor(what, "stats", stats, torch.float64, (na, 3), dev)
+        ck.workspace(what, workspace, gae_rule_workspace_numel(N, na), dev)
+    ck.require_gpu(dev)
     if stats is not None and workspace is None:
         workspace = torch.empty(gae_rule_workspace_numel(N, na), dtype=torch.float64, device=dev)
     e = _lib.gae_rule_args(reward, done, truncated, term_obs, value, next_value, advantage, td_target, done_eff, stats, normalized,
                            workspace if stats is not None else None, n_steps=T, n_envs=N, n_agents=na, gamma=gamma, lam=lam, rule=rule,
                            norm_eps=norm_eps)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_gae_rule(C.byref(e), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_gae_rule")
+    _lib.launch(dev, "qr_gae_rule", e)
     return advantage, td_target, stats
 
 
@@ -157,7 +145,7 @@ class RolloutStorage:
         self.td_target = torch.zeros(T, N, self.n_agents, **f32)
         self.env_x_lim = getattr(env, "x_lim", None)   # the default x_lim of compute_gae(time_limit="solved")
         self.gae_stats = self._gae_workspace = self.advantage_normalized = self.done_eff = None   # compute_gae's, made at first use
-        self._lib = _lib.load()
+        _lib.load()   # a missing library is reported here, not at the first launch
         self._ppo_workspace = {}   # (agent, B, max_workgroups) -> workspace of actor_grad
         self._critic_workspace = {}   # (agent, B, max_workgroups) -> workspace of critic_grad
 
@@ -334,13 +322,9 @@ class RolloutStorage:
         nv = None if next_value is None else next_value.contiguous()
         if nv is not None and (tuple(nv.shape) != (self.T, self.N, self.n_agents) or nv.dtype != torch.float32 or nv.device != self.device):
             raise ValueError(f"next_value must be float32 [{self.T}, {self.N}, {self.n_agents}] on {self.device}")
-        with torch.cuda.device(self.device):  # launch on the storage's device, whatever the caller's current device is
-            rc = self._lib.qr_gae(self.reward.data_ptr(), self.done.data_ptr(), self.value.data_ptr(),
-                                  None if nv is None else nv.data_ptr(), self.T, M, float(gamma), float(lam),
-                                  self.advantage.data_ptr(), self.td_target.data_ptr(),
-                                  None if partials is None else partials.data_ptr(),
-                                  torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(rc, "qr_gae")
+        # (launched on the storage's device, whatever the caller's current device is)
+        _lib.launch(self.device, "qr_gae", self.reward.data_ptr(), self.done.data_ptr(), self.value.data_ptr(), _lib.ptr(nv), self.T, M, float(gamma),
+                    float(lam), self.advantage.data_ptr(), self.td_target.data_ptr(), _lib.ptr(partials))
         if not want_stats:
             return self.advantage, self.td_target
         if self.n_agents == 1:
@@ -377,8 +361,7 @@ class RolloutStorage:
             raise ValueError(f"next_value must be float32 [{T}, {N}, {na}] on {dev}")
         if normalized and T * N < 2:
             raise ValueError(f"{what}: normalized=True needs at least two transitions per agent, got {T} x {N}")
-        if dev.type != "cuda":
-            raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+        ck.require_gpu(dev)
         stats = want_stats or normalized
         if stats and self.gae_stats is None:
             self.gae_stats = torch.zeros(na, 3, dtype=torch.float64, device=dev)

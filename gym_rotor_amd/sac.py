@@ -21,14 +21,35 @@ from __future__ import annotations
 
 from typing import Optional, Union
 
-import ctypes as C
-
 import torch
 
+from . import _checks as ck
 from . import _lib
-from .policy import ActorParams, QCriticParams, _grad_outputs, _vector
-from .td3 import (ReplayBuffer, _check_actor, _check_index, _critic_update_state, _ctde_actor_launch, _pair_of, _rows, _target, _target_ctde,
-                  twinq_grad, twinq_grad_ctde)
+from .policy import PPO_ACTOR_DIMS, ActorParams, QCriticParams, _grad_outputs, module_grads
+from .td3 import ReplayBuffer, _critic_update_state, _ctde_actor_launch, _ctde_actors_c, _target, _target_ctde, twinq_grad, twinq_grad_ctde
+
+
+_EPS = ("eps", "eps_reg", "eps_next", "eps_pert")   # sac_actor_grad's four [B, A] draws
+
+
+def _entropy_terms(what: str, alpha, target_entropy, alpha_grad, A: int, dev):
+    """(alpha, alpha_dev, target_entropy) of a SAC actor launch, checked, and the check of alpha_grad; target_entropy None: -A."""
+    a, alpha_dev = ck.alpha(what, alpha, dev)
+    te = -float(A) if target_entropy is None else float(target_entropy)
+    if not -float("inf") < te < float("inf"):
+        raise ValueError(f"{what}: target_entropy must be finite, got {target_entropy}")
+    ck.scalar(what, "alpha_grad", alpha_grad, torch.float32, dev)
+    return a, alpha_dev, te
+
+
+def _actor_grads(what: str, m, log_alpha) -> dict:
+    """The live SAC actor's eight .grad tensors by name, and log_alpha's where it is given, made where there is none."""
+    params = [t for l in (m.fc1, m.fc2, m.mean_linear, m.log_std_linear) for t in (l.weight, l.bias)]
+    if log_alpha is not None:
+        if log_alpha.numel() != 1:
+            raise ValueError(f"{what}: log_alpha must have one element")
+        params.append(log_alpha)
+    return module_grads(_lib.SAC_ACTOR_GRAD_NAMES, params)
 
 
 def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffer_or_tensors, k: int = 0,
@@ -49,21 +70,11 @@ def sac_target(actor: Optional[ActorParams], critic_target: QCriticParams, buffe
     what = "sac_target"
 
     def own(B, A, dev):   # what follows _target's check of noise and action_next; the keywords of sac_target_args that are SAC's
-        x = action_out
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
-            raise ValueError(f"{what}: action_out must be a contiguous float32 [{B}, {A}] tensor on {dev}")
-        for name, x in (("logp_next", logp_next), ("logp_out", logp_out)):
-            if x is not None and (x.dtype != torch.float32 or x.device != dev or x.numel() != B or not x.is_contiguous()):
-                raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}] tensor on {dev}")
-        a, alpha_dev = alpha, None
-        if isinstance(a, torch.Tensor):
-            if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
-                raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
-            alpha_dev, a = a, 0.0
-        elif not 0.0 <= float(a) < float("inf"):
-            raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
-        if not 0.0 <= float(discount) < float("inf"):
-            raise ValueError(f"{what}: discount must be finite and >= 0, got {discount}")
+        ck.tensor(what, "action_out", action_out, torch.float32, (B, A), dev, True)
+        ck.flat(what, "logp_next", logp_next, torch.float32, B, dev, True)
+        ck.flat(what, "logp_out", logp_out, torch.float32, B, dev, True)
+        a, alpha_dev = ck.alpha(what, alpha, dev)
+        ck.nonneg(what, ("discount",), discount)
         return dict(logp_next=logp_next, alpha_dev=alpha_dev, action_out=action_out, logp_out=logp_out, discount=discount, alpha=a)
 
     A = critic_target.dims[1]
@@ -112,24 +123,14 @@ def sac_target_ctde(actors, critic_target: QCriticParams, buffer_or_tensors, k: 
     what = "sac_target_ctde"
 
     def own(B, ad, dev, supplied):
-        outs = _pair_of(what, "action_out", action_out, B, ad, dev)
-        x = noise_logp
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, ad[k]) or not x.is_contiguous()):
-            raise ValueError(f"{what}: noise_logp must be a contiguous float32 [{B}, {ad[k]}] tensor on {dev}")
-        for name, x in (("logp_next", logp_next), ("logp_out", logp_out)):
-            if x is not None and (x.dtype != torch.float32 or x.device != dev or x.numel() != B or not x.is_contiguous()):
-                raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}] tensor on {dev}")
+        outs = ck.pair_of(what, "action_out", action_out, B, ad, dev)
+        ck.tensor(what, "noise_logp", noise_logp, torch.float32, (B, ad[k]), dev, True)
+        ck.flat(what, "logp_next", logp_next, torch.float32, B, dev, True)
+        ck.flat(what, "logp_out", logp_out, torch.float32, B, dev, True)
         if supplied and logp_next is None:
             raise ValueError(f"{what}: without actors, logp_next [B] is required")
-        a, alpha_dev = alpha, None
-        if isinstance(a, torch.Tensor):
-            if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
-                raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
-            alpha_dev, a = a, 0.0
-        elif not 0.0 <= float(a) < float("inf"):
-            raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
-        if not 0.0 <= float(discount) < float("inf"):
-            raise ValueError(f"{what}: discount must be finite and >= 0, got {discount}")
+        a, alpha_dev = ck.alpha(what, alpha, dev)
+        ck.nonneg(what, ("discount",), discount)
         return dict(eps_logp=noise_logp, logp_next=logp_next, alpha_dev=alpha_dev, action_out=outs, logp_out=logp_out, discount=discount, alpha=a,
                     agent=k)
 
@@ -160,9 +161,7 @@ def sac_critic_loss_ctde(critic_module, critic_target_module, actor_modules, buf
 
 def sac_actor_workspace_bytes(actor_dims, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `sac_actor_grad` call needs (qr_sac_actor_workspace_bytes); actor_dims = (obs_dim, hidden, action_dim)."""
-    n = _lib.load().qr_sac_actor_workspace_bytes(*(int(d) for d in actor_dims), int(critic_hidden), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_sac_actor_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_sac_actor_workspace_bytes", *actor_dims, critic_hidden, batch, max_workgroups)
 
 
 def sac_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor, obs_next: Optional[torch.Tensor] = None,
@@ -191,36 +190,19 @@ def sac_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
     what = "sac_actor_grad"
     dev = critic.device
     D, A, H = critic.dims
-    shapes = _check_actor(actor, D, A, dev, what, _lib.ACTOR_TANH_SAMPLE, True,
-                          "the actor must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
-    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
-        if not 0.0 <= float(v) < float("inf"):
-            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
-    a, alpha_dev = alpha, None
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
-            raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
-        alpha_dev, a = a, 0.0
-    elif not 0.0 <= float(a) < float("inf"):
-        raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
-    te = -float(A) if target_entropy is None else float(target_entropy)
-    if not -float("inf") < te < float("inf"):
-        raise ValueError(f"{what}: target_entropy must be finite, got {target_entropy}")
-    if alpha_grad is not None and (alpha_grad.dtype != torch.float32 or alpha_grad.device != dev or alpha_grad.numel() != 1):
-        raise ValueError(f"{what}: alpha_grad must be a float32 tensor of one element on {dev}")
-    rows = _rows(obs, D, dev, what, "obs")
-    if lam_T != 0 and _rows(obs_next, D, dev, what, "obs_next") != rows:
+    shapes = ck.actor(what, actor, PPO_ACTOR_DIMS, D, A, dev, _lib.ACTOR_TANH_SAMPLE, True,
+                      "the actor must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
+    ck.nonneg(what, ck.LAMS, lam_T, lam_S, lam_M, max_action)
+    a, alpha_dev, te = _entropy_terms(what, alpha, target_entropy, alpha_grad, A, dev)
+    rows = ck.rows(what, "obs", obs, D, dev)
+    if lam_T != 0 and ck.rows(what, "obs_next", obs_next, D, dev) != rows:
         raise ValueError(f"{what}: obs_next must have obs's {rows} rows")
     if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
         raise ValueError(f"{what}: noise [{D}] is required when lam_S != 0, nominal [{A}] when lam_M != 0")
-    _vector(noise, D, dev, what, "noise")
-    _vector(nominal, A, dev, what, "nominal")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
-    for name, x in (("eps", eps), ("eps_reg", eps_reg), ("eps_next", eps_next), ("eps_pert", eps_pert)):
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
-    shapes = {n: shapes[n] for n in _lib.SAC_ACTOR_GRAD_NAMES}
+    ck.flat(what, "noise", noise, torch.float32, D, dev, True)
+    ck.flat(what, "nominal", nominal, torch.float32, A, dev, True)
+    B = ck.index(what, index, dev, rows)
+    ck.named(what, "{}", dict(eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert), dict.fromkeys(_EPS, (B, A)), dev, optional=True)
     grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
                                             lambda: sac_actor_workspace_bytes(actor.dims, H, B, max_workgroups), size_given=False,
                                             n_stats=_lib.SAC_ACTOR_STATS)
@@ -233,10 +215,7 @@ def sac_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
                                  noise=noise if lam_S != 0 else None, nominal=nominal if lam_M != 0 else None, alpha_dev=alpha_dev,
                                  alpha_grad=alpha_grad, alpha=a, target_entropy=te, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                                  max_action=max_action, max_workgroups=max_workgroups)
-    p, q = actor.as_c(), critic.as_c()
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_sac_actor_grad(C.byref(p), C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_sac_actor_grad")
+    _lib.launch(dev, "qr_sac_actor_grad", actor.as_c(), critic.as_c(), b, g)
     return grads, stats
 
 
@@ -258,27 +237,12 @@ def sac_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
     and `torch.exp(log_alpha, out=alpha)` feeds the next `sac_target` and `sac_actor_loss`."""
     if not isinstance(buffer, ReplayBuffer):
         raise ValueError("sac_actor_loss: buffer must be a ReplayBuffer")
-    m = actor_module
-    params = [t for l in (m.fc1, m.fc2, m.mean_linear, m.log_std_linear) for t in (l.weight, l.bias)]
-    if log_alpha is not None:
-        if log_alpha.numel() != 1:
-            raise ValueError("sac_actor_loss: log_alpha must have one element")
-        params.append(log_alpha)
-    for p in params:
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-    grads = {n: p.grad for n, p in zip(_lib.SAC_ACTOR_GRAD_NAMES, params)}
-    actor = ActorParams.from_sac_module(m)
+    grads = _actor_grads("sac_actor_loss", actor_module, log_alpha)
+    actor = ActorParams.from_sac_module(actor_module)
     critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
-    B = buffer.capacity if index is None else index.numel()
-    key = ("sac_actor", k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = sac_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev),
-                                    torch.empty(_lib.SAC_ACTOR_STATS, dtype=torch.float32, device=dev))
-    workspace, own_stats = hit
+    workspace, own_stats = buffer._actor_scratch("sac_actor", k, index, max_workgroups, critic.device,
+                                                 lambda B: sac_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups),
+                                                 _lib.SAC_ACTOR_STATS)
     _, stats = sac_actor_grad(actor, critic, buffer.obs[k], buffer.obs_next[k], index, alpha=alpha, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                               max_action=max_action, eps=eps, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert, noise=noise,
                               nominal=nominal, alpha_grad=None if log_alpha is None else log_alpha.grad, target_entropy=target_entropy,
@@ -289,9 +253,7 @@ def sac_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
 def sac_actor_workspace_bytes_ctde(k: int, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `sac_actor_grad_ctde` call needs for agent k (qr_ctde_sac_actor_workspace_bytes): `sac_actor_workspace_bytes`'
     figure for td3.CTDE_ACTOR_DIMS[k]."""
-    n = _lib.load().qr_ctde_sac_actor_workspace_bytes(int(k), int(critic_hidden), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_ctde_sac_actor_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_ctde_sac_actor_workspace_bytes", k, critic_hidden, batch, max_workgroups)
 
 
 def sac_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index: Optional[torch.Tensor] = None, *, k: int = 0,
@@ -322,23 +284,10 @@ def sac_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index
     form = (_lib.ACTOR_TANH_SAMPLE, True, "the actors must be of MLP_Actor_SAC's form: the tanh-of-sample rule with a log_std head")
     shapes, B, rows, od, ad, nxt = _ctde_actor_launch(what, actors, critic, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action,
                                                       noise, nominal, form)
-    a, alpha_dev = alpha, None
-    if isinstance(a, torch.Tensor):
-        if a.dtype != torch.float32 or a.device != dev or a.numel() != 1:
-            raise ValueError(f"{what}: alpha must be a Python float or a float32 tensor of one element on {dev}")
-        alpha_dev, a = a, 0.0
-    elif not 0.0 <= float(a) < float("inf"):
-        raise ValueError(f"{what}: alpha must be finite and >= 0, got {a}")
-    te = -float(ad[k]) if target_entropy is None else float(target_entropy)
-    if not -float("inf") < te < float("inf"):
-        raise ValueError(f"{what}: target_entropy must be finite, got {target_entropy}")
-    if alpha_grad is not None and (alpha_grad.dtype != torch.float32 or alpha_grad.device != dev or alpha_grad.numel() != 1):
-        raise ValueError(f"{what}: alpha_grad must be a float32 tensor of one element on {dev}")
-    for name, x, w in (("eps", eps, ad[k]), ("eps_logp", eps_logp, ad[k]), ("eps_other", eps_other, ad[1 - k]), ("eps_reg", eps_reg, ad[k]),
-                       ("eps_next", eps_next, ad[k]), ("eps_pert", eps_pert, ad[k])):
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, w) or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {w}] tensor on {dev}")
-    shapes = {n: shapes[n] for n in _lib.SAC_ACTOR_GRAD_NAMES}
+    a, alpha_dev, te = _entropy_terms(what, alpha, target_entropy, alpha_grad, ad[k], dev)
+    own, other = (B, ad[k]), (B, ad[1 - k])
+    ck.named(what, "{}", dict(eps=eps, eps_logp=eps_logp, eps_other=eps_other, eps_reg=eps_reg, eps_next=eps_next, eps_pert=eps_pert),
+             dict(eps=own, eps_logp=own, eps_other=other, eps_reg=own, eps_next=own, eps_pert=own), dev, optional=True)
     grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
                                             lambda: sac_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups), size_given=False,
                                             n_stats=_lib.SAC_ACTOR_STATS)
@@ -352,12 +301,7 @@ def sac_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index
                                       eps_pert=eps_pert, noise=noise if lam_S != 0 else None, nominal=nominal if lam_M != 0 else None,
                                       alpha_dev=alpha_dev, alpha_grad=alpha_grad, alpha=a, target_entropy=te, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                                       max_action=max_action, max_workgroups=max_workgroups)
-    q = critic.as_c()
-    p = [None if c is None else c.as_c() for c in actors]
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_ctde_sac_actor_grad(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
-                                                torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ctde_sac_actor_grad")
+    _lib.launch(dev, "qr_ctde_sac_actor_grad", *_ctde_actors_c(actors, log_std=True), critic.as_c(), b, g)
     return grads, stats
 
 
@@ -382,27 +326,12 @@ def sac_actor_loss_ctde(actor_modules, critic_module, buffer: ReplayBuffer, k: i
     actor_modules = tuple(actor_modules)
     if len(actor_modules) != 2:
         raise ValueError(f"{what}: actor_modules must be the pair of both agents' actors")
-    m = actor_modules[k]
-    params = [t for l in (m.fc1, m.fc2, m.mean_linear, m.log_std_linear) for t in (l.weight, l.bias)]
-    if log_alpha is not None:
-        if log_alpha.numel() != 1:
-            raise ValueError(f"{what}: log_alpha must have one element")
-        params.append(log_alpha)
-    for p in params:
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-    grads = {n: p.grad for n, p in zip(_lib.SAC_ACTOR_GRAD_NAMES, params)}
+    grads = _actor_grads(what, actor_modules[k], log_alpha)
     actors = [ActorParams.from_sac_module(a) for a in actor_modules]
     critic = QCriticParams.from_module(critic_module, sum(buffer.action_dims))
-    B = buffer.capacity if index is None else index.numel()
-    key = ("sac_actor_ctde", k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = sac_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev),
-                                    torch.empty(_lib.SAC_ACTOR_STATS, dtype=torch.float32, device=dev))
-    workspace, own_stats = hit
+    workspace, own_stats = buffer._actor_scratch("sac_actor_ctde", k, index, max_workgroups, critic.device,
+                                                 lambda B: sac_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups),
+                                                 _lib.SAC_ACTOR_STATS)
     _, stats = sac_actor_grad_ctde(actors, critic, buffer.obs, buffer.obs_next, index, k=k, alpha=alpha, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                                    max_action=max_action, eps=eps, eps_logp=eps_logp, eps_other=eps_other, eps_reg=eps_reg, eps_next=eps_next,
                                    eps_pert=eps_pert, noise=noise, nominal=nominal, alpha_grad=None if log_alpha is None else log_alpha.grad,

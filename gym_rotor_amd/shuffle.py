@@ -9,11 +9,11 @@ launch reads it there, which is what lets a captured graph shuffle afresh at eve
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 
+from . import _checks as ck
 from . import _lib
 from .noise import check_seed
 
@@ -52,14 +52,8 @@ def shuffle(out: torch.Tensor, *, n: int, seed: int, draw: int, stream: int, fir
     if draw_dev is None and not 0 <= draw < 2 ** 63:
         raise ValueError(f"{what}: draw must lie in [0, 2^63), got {draw}")
     dev = out.device
-    if draw_dev is not None and (not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype != torch.int64 or draw_dev.device != dev or
-                                 draw_dev.numel() != 1):
-        raise ValueError(f"{what}: draw_dev must be an int64 tensor of one element on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    s = _lib.shuffle_args(out, n=n, first=first, seed=seed, draw=0 if draw_dev is not None else draw, draw_dev=draw_dev, stream=stream,
-                          max_workgroups=max_workgroups)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_shuffle(C.byref(s), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_shuffle")
+    ck.scalar(what, "draw_dev", draw_dev, torch.int64, dev)
+    ck.require_gpu(dev)
+    _lib.launch(dev, "qr_shuffle", _lib.shuffle_args(out, n=n, first=first, seed=seed, draw=0 if draw_dev is not None else draw, draw_dev=draw_dev,
+                                                     stream=stream, max_workgroups=max_workgroups))
     return out

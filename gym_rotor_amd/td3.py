@@ -27,14 +27,14 @@ stores the reference's done at the episode time limit (main.py:169-173: "solved 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple, Optional, Sequence
 
 import torch
 
+from . import _checks as ck
 from . import _lib
-from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams, _grad_outputs, _vector
+from .policy import ActorParams, PPO_ACTOR_DIMS, QCriticParams, _grad_outputs, module_grads
 
 
 TIME_LIMITS = ("own", "solved")   # what `done` holds on a transition at the episode time limit: the agent's own flag / main.py:169-173
@@ -86,6 +86,19 @@ class ReplayBuffer:
     @property
     def n_agents(self) -> int:
         return len(self.obs_dims)
+
+    def _scratch(self, key: tuple, make):
+        """The tensors a `*_loss` wrapper keeps between calls, from the cache under `key`; made by `make()` at first use."""
+        hit = self._cache.get(key)
+        if hit is None:
+            hit = self._cache[key] = make()
+        return hit
+
+    def _actor_scratch(self, tag: str, k: int, index, max_workgroups: int, dev, workspace_bytes, n_stats: int = 4):
+        """(workspace, stats [n_stats]) of an actor-loss wrapper under (tag, k, B, max_workgroups); workspace_bytes(B): the size query."""
+        B = self.capacity if index is None else index.numel()
+        return self._scratch((tag, k, B, int(max_workgroups)), lambda: (
+            torch.empty(workspace_bytes(B) // 8 if B else 0, dtype=torch.float64, device=dev), torch.empty(n_stats, dtype=torch.float32, device=dev)))
 
     def _check_storage(self, storage, time_limit: str) -> Optional[TimeLimitRule]:
         """add's and append's checks, before anything is written; the rule's numbers for time_limit "solved", None for "own"."""
@@ -236,41 +249,29 @@ def replay_add(tensors, obs, final_obs, action: torch.Tensor, reward: torch.Tens
         raise ValueError(f"{what}: the time-limit rule reads the first three words of agent 0's observation, which has {od[0]}")
     if T < 1 or N < 1 or T * N > capacity:
         raise ValueError(f"{what}: a horizon of {T} x {N} = {T * N} transitions does not fit a buffer of {capacity}")
-    def need(x, shape, dtype, name):
-        if x is None or x.dtype != dtype or x.device != dev or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous {dtype} {shape} tensor on {dev}")
+    f32 = torch.float32
     for k, t in enumerate(tensors):
         for name, shape in (("obs", (capacity, od[k])), ("obs_next", (capacity, od[k])), ("act", (capacity, ad[k])), ("rwd", (capacity,)), ("done", (capacity,))):
-            need(t.get(name), shape, torch.float32, f"agent {k}'s buffer {name}")
-        need(obs[k], (T + 1, N, od[k]), torch.float32, f"obs[{k}]")
+            ck.tensor(what, f"agent {k}'s buffer {name}", t.get(name), f32, shape, dev)
+        ck.tensor(what, f"obs[{k}]", obs[k], f32, (T + 1, N, od[k]), dev)
         if final_obs is not None:
-            need(final_obs[k], (T, N, od[k]), torch.float32, f"final_obs[{k}]")
-    need(action, (T, N, row), torch.float32, "action")
-    need(reward, (T, N, na), torch.float32, "reward")
-    need(done, (T, N, na), torch.bool, "done")
-    if truncated is not None:
-        need(truncated, (T, N), torch.bool, "truncated")
-    _check_state(what, state, dev)
+            ck.tensor(what, f"final_obs[{k}]", final_obs[k], f32, (T, N, od[k]), dev)
+    ck.tensor(what, "action", action, f32, (T, N, row), dev)
+    ck.tensor(what, "reward", reward, f32, (T, N, na), dev)
+    ck.tensor(what, "done", done, torch.bool, (T, N, na), dev)
+    ck.tensor(what, "truncated", truncated, torch.bool, (T, N), dev, True)
+    ck.state(what, state, dev)
     count = int(count)
     if state is None and not 0 <= count < capacity:
         raise ValueError(f"{what}: count must lie in [0, {capacity}), got {count}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    ck.require_gpu(dev)
     r = _lib.replay_add_args(tensors, obs, final_obs, action, reward, done, truncated, state=state, count=count if state is None else 0,
                              capacity=capacity, n_steps=T, n_envs=N, obs_dims=od, action_dims=ad,
                              col_offsets=[sum(ad[:k]) for k in range(na)], action_row=row)
-    with torch.cuda.device(dev):
-        if time_limit_rule is None:
-            rc = _lib.load().qr_replay_add(C.byref(r), torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rr = _lib.replay_add_rule_args(r, **time_limit_rule._asdict())
-            rc = _lib.load().qr_replay_add_rule(C.byref(rr), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_replay_add" if time_limit_rule is None else "qr_replay_add_rule")
-
-
-def _check_state(what: str, state, dev):
-    if state is not None and (state.dtype != torch.int64 or state.device != dev or tuple(state.shape) != (3,) or not state.is_contiguous()):
-        raise ValueError(f"{what}: state must be a contiguous int64 [3] tensor (count, current_size, draw) on {dev}")
+    if time_limit_rule is None:
+        _lib.launch(dev, "qr_replay_add", r)
+    else:
+        _lib.launch(dev, "qr_replay_add_rule", _lib.replay_add_rule_args(r, **time_limit_rule._asdict()))
 
 
 def replay_sample(n: int, batch_size: int, seed: int, draw: int, out: Optional[torch.Tensor] = None, *, device=None,
@@ -292,20 +293,13 @@ def replay_sample(n: int, batch_size: int, seed: int, draw: int, out: Optional[t
     dev = torch.device("cuda" if out is None else out.device) if device is None else torch.device(device)
     if dev.type == "cuda" and dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    if out is not None:
-        if out.dtype != torch.int64 or out.device != dev or tuple(out.shape) != (B,) or not out.is_contiguous():
-            raise ValueError(f"{what}: out must be a contiguous int64 [{B}] tensor on {dev}")
-    _check_state(what, state, dev)
-    if status is not None and (status.dtype != torch.int32 or status.device != dev or status.numel() != 1):
-        raise ValueError(f"{what}: status must be an int32 tensor of one element on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    ck.tensor(what, "out", out, torch.int64, (B,), dev, True)
+    ck.state(what, state, dev)
+    ck.scalar(what, "status", status, torch.int32, dev)
+    ck.require_gpu(dev)
     if out is None:
         out = torch.empty(B, dtype=torch.int64, device=dev)
-    s = _lib.replay_sample_args(out, status, state, n=n, batch=B, seed=seed, draw=draw)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_replay_sample(C.byref(s), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_replay_sample")
+    _lib.launch(dev, "qr_replay_sample", _lib.replay_sample_args(out, status, state, n=n, batch=B, seed=seed, draw=draw))
     return out
 
 
@@ -313,85 +307,38 @@ def _agent_tensors(buffer_or_tensors, k: int) -> dict:
     return buffer_or_tensors.tensors(k) if isinstance(buffer_or_tensors, ReplayBuffer) else dict(buffer_or_tensors)
 
 
-def _check_index(index, dev, what: str):
-    if index is not None and (index.dtype != torch.int64 or index.device != dev or index.dim() != 1 or not index.is_contiguous()):
-        raise ValueError(f"{what}: index must be a contiguous int64 [B] tensor on {dev}")
-
-
-def _rows(t, width: int, dev, what: str, name: str) -> int:
-    if t is None or t.dtype != torch.float32 or t.device != dev or t.dim() != 2 or t.shape[1] != width or not t.is_contiguous():
-        raise ValueError(f"{what}: {name} must be a contiguous float32 [rows, {width}] tensor on {dev}")
-    return t.shape[0]
-
-
-def _column(t, rows: int, dev, what: str, name: str) -> int:
-    """Element stride of a float32 tensor of `rows` elements with one stride ([rows], [rows, 1] or a column of a wider tensor)."""
-    if t is None or t.dtype != torch.float32 or t.device != dev or t.numel() != rows:
-        raise ValueError(f"{what}: {name} must be float32 with {rows} elements on {dev}")
-    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]
-    if len(dims) > 1 or (dims and dims[0][1] < 1):
-        raise ValueError(f"{what}: {name} must have one positive element stride, got shape {tuple(t.shape)} strides {t.stride()}")
-    return dims[0][1] if dims else 1
-
-
-def _check_actor(actor: ActorParams, D: int, A: int, dev, what: str, squash: int, log_std_head: bool, form: str) -> dict:
-    """An actor beside a twin critic that reads D + A: one of the rollout's sizes, of the form the launch takes (`form`: the message
-    otherwise), its tensors of their shapes on `dev`.  Returns {name: shape} of the tensors the launch reads."""
-    if actor.dims not in PPO_ACTOR_DIMS:
-        raise ValueError(f"{what}: actor sizes {actor.dims} are not among {PPO_ACTOR_DIMS} (obs, hidden, action)")
-    if actor.squash != squash or ((actor.log_std_w is None or actor.log_std_b is None) if log_std_head else actor.log_std_w is not None):
-        raise ValueError(f"{what}: {form}")
-    if (actor.dims[0], actor.dims[2]) != (D, A):
-        raise ValueError(f"{what}: the actor maps {actor.dims[0]} -> {actor.dims[2]}, the critic reads {D} + {A}")
-    Da, Ha, Aa = actor.dims
-    shapes = {"fc1_w": (Ha, Da), "fc1_b": (Ha,), "fc2_w": (Ha, Ha), "fc2_b": (Ha,), "mean_w": (Aa, Ha), "mean_b": (Aa,)}
-    if log_std_head:
-        shapes.update(log_std_w=(Aa, Ha), log_std_b=(Aa,))
-    for n, shp in shapes.items():   # (log_std is not read: whatever it holds is not checked)
-        w = getattr(actor, n)
-        if tuple(w.shape) != shp or w.dtype != torch.float32 or w.device != dev or not w.is_contiguous():
-            raise ValueError(f"{what}: actor tensor {n} must be a contiguous float32 {shp} tensor on {dev}")
-    return shapes
-
-
 def _target(what: str, entry: str, make_args, actor: Optional[ActorParams], form: tuple, missing: Optional[str], critic_target: QCriticParams,
             buffer_or_tensors, k: int, index, noise, action_next, out, own) -> torch.Tensor:
-    """What `td3_target` and `sac.sac_target` do alike: the transitions, the actor (`form`: _check_actor's last three arguments) or,
+    """What `td3_target` and `sac.sac_target` do alike: the transitions, the actor (`form`: _checks.actor's last three arguments) or,
     without one, `missing` (the message when a supplied tensor is), noise, action_next, the caller's `own(B, A, dev)` checks —
     which return its own keywords of `make_args` — out, and the launch of `entry`."""
     t = _agent_tensors(buffer_or_tensors, k)
     dev = critic_target.device
     D, A, H = critic_target.dims
-    rows = _rows(t.get("obs_next"), D, dev, what, "obs_next")
-    rs, ds = _column(t.get("rwd"), rows, dev, what, "rwd"), _column(t.get("done"), rows, dev, what, "done")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
+    rows = ck.rows(what, "obs_next", t.get("obs_next"), D, dev)
+    rs, ds = ck.column(what, "rwd", t.get("rwd"), rows, dev), ck.column(what, "done", t.get("done"), rows, dev)
+    B = ck.index(what, index, dev, rows)
     if actor is not None:
-        _check_actor(actor, D, A, dev, what, *form)
+        ck.actor(what, actor, PPO_ACTOR_DIMS, D, A, dev, *form)
     elif missing is not None:
         raise ValueError(f"{what}: {missing}")
-    for name, x in (("noise", noise), ("action_next", action_next)):
-        if x is not None and (x.dtype != torch.float32 or x.device != dev or tuple(x.shape) != (B, A) or not x.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 [{B}, {A}] tensor on {dev}")
+    ck.tensor(what, "noise", noise, torch.float32, (B, A), dev, True)
+    ck.tensor(what, "action_next", action_next, torch.float32, (B, A), dev, True)
     kw = own(B, A, dev)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    else:
+        ck.flat(what, "out", out, torch.float32, B, dev)
+    ck.require_gpu(dev)
     if B == 0:
         return out
     b = _lib.transitions(obs_next=t["obs_next"], reward=t["rwd"], done=t["done"], index=index, batch=B, rows=rows, reward_stride=rs, done_stride=ds)
     g = make_args(eps=noise, action_next=action_next, y=out, **kw)
-    q = critic_target.as_c()
+    p = None
     if actor is not None:
         p = actor.as_c()
         p.log_std = None
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), entry)(C.byref(p) if actor is not None else None, C.byref(q), C.byref(b), C.byref(g),
-                                         torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, entry)
+    _lib.launch(dev, entry, p, critic_target.as_c(), b, g)
     return out
 
 
@@ -418,6 +365,21 @@ def td3_target(actor_target: Optional[ActorParams], critic_target: QCriticParams
 CTDE_ACTOR_DIMS = ((15, 16, 4), (3, 4, 1))   # the Decoupled wrapper's two actors: what the centralized target kernels hold
 
 
+def _ctde_actors_c(actors, log_std: bool = False) -> list:
+    """The pair's QrActor structs for a centralized launch, None where an agent's actor is not given; their log_std, which these
+    launches do not read, is null unless `log_std`."""
+    p = [None if a is None else a.as_c() for a in actors]
+    for c in p:
+        if c is not None and not log_std:
+            c.log_std = None
+    return p
+
+
+def _td3_actor(m) -> ActorParams:
+    """MLP_Actor_TD3's six tensors (fc3 the mean head) as the TD3 launches take them: no log_std, which they do not read."""
+    return ActorParams(*(t.data for l in (m.fc1, m.fc2, m.fc3) for t in (l.weight, l.bias)), None)
+
+
 def _ctde_tensors(what: str, buffer_or_tensors, critic: QCriticParams, k: int):
     """Both agents' tensors of a two-agent `ReplayBuffer` (or a pair of dicts with obs, obs_next, act and, for agent k, rwd and done),
     their observation and action widths — which must add up to the centralized critic's — and the common row count."""
@@ -441,70 +403,46 @@ def _ctde_tensors(what: str, buffer_or_tensors, critic: QCriticParams, k: int):
     D, A, _ = critic.dims
     if sum(od) != D or sum(ad) != A:
         raise ValueError(f"{what}: the buffer's widths {od[0]}+{od[1]} / {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
-    rows = _rows(t[0]["obs_next"], od[0], dev, what, "agent 0's obs_next")
-    if _rows(t[1]["obs_next"], od[1], dev, what, "agent 1's obs_next") != rows:
+    rows = ck.rows(what, "agent 0's obs_next", t[0]["obs_next"], od[0], dev)
+    if ck.rows(what, "agent 1's obs_next", t[1]["obs_next"], od[1], dev) != rows:
         raise ValueError(f"{what}: agent 1's obs_next must have agent 0's {rows} rows")
     return t, od, ad, rows
-
-
-def _pair_of(what: str, name: str, x, B: int, widths, dev):
-    """None, or a pair of None / contiguous float32 [B, widths[m]] tensors."""
-    if x is None:
-        return (None, None)
-    x = tuple(x)
-    if len(x) != 2:
-        raise ValueError(f"{what}: {name} must be a pair, one entry per agent")
-    for m, e in enumerate(x):
-        if e is not None and (e.dtype != torch.float32 or e.device != dev or tuple(e.shape) != (B, widths[m]) or not e.is_contiguous()):
-            raise ValueError(f"{what}: {name}[{m}] must be a contiguous float32 [{B}, {widths[m]}] tensor on {dev}")
-    return x
 
 
 def _target_ctde(what: str, entry: str, make_args, actors, form: tuple, critic_target: QCriticParams, buffer_or_tensors, k: int, index, noise,
                  action_next, out, own) -> torch.Tensor:
     """`_target` for the centralized critic of two agents, shared by `td3_target_ctde` and `sac.sac_target_ctde`: both agents'
-    transitions, both actors (`form`: _check_actor's last three arguments) or neither, the pairs noise and action_next, the caller's
+    transitions, both actors (`form`: _checks.actor's last three arguments) or neither, the pairs noise and action_next, the caller's
     `own(B, widths, dev, supplied)` checks — which return its own keywords of `make_args` — out, and the launch of `entry`."""
     t, od, ad, rows = _ctde_tensors(what, buffer_or_tensors, critic_target, k)
     dev = critic_target.device
-    rs, ds = _column(t[k].get("rwd"), rows, dev, what, "rwd"), _column(t[k].get("done"), rows, dev, what, "done")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
+    rs, ds = ck.column(what, "rwd", t[k].get("rwd"), rows, dev), ck.column(what, "done", t[k].get("done"), rows, dev)
+    B = ck.index(what, index, dev, rows)
     actors = (None, None) if actors is None else tuple(actors)
     if len(actors) != 2 or (actors[0] is None) != (actors[1] is None):
         raise ValueError(f"{what}: actors must be a pair of both agents' actors, or None for both")
     supplied = actors[0] is None
     for m in range(2):
         if not supplied:
-            _check_actor(actors[m], od[m], ad[m], dev, what, *form)
+            ck.actor(what, actors[m], PPO_ACTOR_DIMS, od[m], ad[m], dev, *form)
             if actors[m].dims != CTDE_ACTOR_DIMS[m]:
                 raise ValueError(f"{what}: actor {m} must have the sizes {CTDE_ACTOR_DIMS[m]} (obs, hidden, action), got {actors[m].dims}")
-    noise = _pair_of(what, "noise", noise, B, ad, dev)
-    action_next = _pair_of(what, "action_next", action_next, B, ad, dev)
+    noise = ck.pair_of(what, "noise", noise, B, ad, dev)
+    action_next = ck.pair_of(what, "action_next", action_next, B, ad, dev)
     if supplied and (action_next[0] is None or action_next[1] is None):
         raise ValueError(f"{what}: without actors, action_next ([B, {ad[0]}], [B, {ad[1]}]) is required")
     kw = own(B, ad, dev, supplied)
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or out.device != dev or out.numel() != B or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float32 [{B}] tensor on {dev}")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
+    else:
+        ck.flat(what, "out", out, torch.float32, B, dev)
+    ck.require_gpu(dev)
     if B == 0:
         return out
     b = _lib.ctde_transitions(obs_next=(t[0]["obs_next"], t[1]["obs_next"]), reward=t[k]["rwd"], done=t[k]["done"], index=index, batch=B, rows=rows,
                               obs_dims=od, action_dims=ad, reward_stride=rs, done_stride=ds)
     g = make_args(eps=noise, action_next=action_next, y=out, **kw)
-    q = critic_target.as_c()
-    p = [None, None]
-    if not supplied:
-        p = [a.as_c() for a in actors]
-        for c in p:
-            c.log_std = None
-    with torch.cuda.device(dev):
-        rc = getattr(_lib.load(), entry)(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
-                                         torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, entry)
+    _lib.launch(dev, entry, *_ctde_actors_c(actors), critic_target.as_c(), b, g)
     return out
 
 
@@ -542,39 +480,27 @@ def twinq_grad_ctde(critic: QCriticParams, obs, action, y: torch.Tensor, index: 
     for m in range(2):
         if obs[m] is None or obs[m].dim() != 2 or obs[m].shape[1] < 1:
             raise ValueError(f"{what}: obs[{m}] must be a contiguous float32 [rows, width] tensor on {dev}")
-    rows = _rows(obs[0], obs[0].shape[1], dev, what, "obs[0]")
-    if _rows(obs[1], obs[1].shape[1], dev, what, "obs[1]") != rows:
+    rows = ck.rows(what, "obs[0]", obs[0], obs[0].shape[1], dev)
+    if ck.rows(what, "obs[1]", obs[1], obs[1].shape[1], dev) != rows:
         raise ValueError(f"{what}: obs[1] must have obs[0]'s {rows} rows")
-    for m, a in enumerate(action):
-        if (a is None or a.dtype != torch.float32 or a.device != dev or a.dim() != 2 or a.shape[0] != rows or a.shape[1] < 1
-                or (a.shape[1] > 1 and a.stride(1) != 1) or a.stride(0) < a.shape[1]):
-            raise ValueError(f"{what}: action[{m}] must be float32 [{rows}, width] rows with unit column stride on {dev}")
+    strides = [ck.strided_rows(what, f"action[{m}]", a, rows, 1, dev, wider=True) for m, a in enumerate(action)]
     od, ad = [o.shape[1] for o in obs], [a.shape[1] for a in action]
     if sum(od) != D or sum(ad) != A:
         raise ValueError(f"{what}: the widths of obs {od[0]}+{od[1]} / action {ad[0]}+{ad[1]} do not add up to the critic's {D} / {A}")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
-    if y is None or y.dtype != torch.float32 or y.device != dev or y.numel() != B or not y.is_contiguous():
-        raise ValueError(f"{what}: y must be a contiguous float32 [{B}] tensor on {dev}")
+    B = ck.index(what, index, dev, rows)
+    ck.flat(what, "y", y, torch.float32, B, dev)
     grads, stats, workspace = _grad_outputs(what, critic.shapes, dev, B, grads, stats, workspace,
                                             lambda: twinq_workspace_bytes(critic.dims, B, max_workgroups))
     if workspace is None:
         return grads, stats
-    b = _lib.ctde_transitions(obs=obs, action=action, index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad,
-                              row_strides=[a.stride(0) if rows > 1 else a.shape[1] for a in action])
-    g = _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups)
-    q = critic.as_c()
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_ctde_twinq_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ctde_twinq_grad")
+    b = _lib.ctde_transitions(obs=obs, action=action, index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad, row_strides=strides)
+    _lib.launch(dev, "qr_ctde_twinq_grad", critic.as_c(), b, _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups))
     return grads, stats
 
 
 def twinq_workspace_bytes(dims, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `twinq_grad` call needs (qr_twinq_workspace_bytes); dims = (obs_dim, action_dim, hidden width)."""
-    n = _lib.load().qr_twinq_workspace_bytes(int(dims[0]) + int(dims[1]), int(dims[2]), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_twinq_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_twinq_workspace_bytes", int(dims[0]) + int(dims[1]), dims[2], batch, max_workgroups)
 
 
 def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y: torch.Tensor, index: Optional[torch.Tensor] = None, *,
@@ -590,24 +516,16 @@ def twinq_grad(critic: QCriticParams, obs: torch.Tensor, action: torch.Tensor, y
     what = "twinq_grad"
     dev = critic.device
     D, A, H = critic.dims
-    rows = _rows(obs, D, dev, what, "obs")
-    if (action is None or action.dtype != torch.float32 or action.device != dev or action.dim() != 2 or action.shape[0] != rows or action.shape[1] < A
-            or (action.shape[1] > 1 and action.stride(1) != 1) or action.stride(0) < action.shape[1]):
-        raise ValueError(f"{what}: action must be float32 [{rows}, >= {A}] rows with unit column stride on {dev}")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
-    if y is None or y.dtype != torch.float32 or y.device != dev or y.numel() != B or not y.is_contiguous():
-        raise ValueError(f"{what}: y must be a contiguous float32 [{B}] tensor on {dev}")
+    rows = ck.rows(what, "obs", obs, D, dev)
+    row_stride = ck.strided_rows(what, "action", action, rows, A, dev, wider=True)
+    B = ck.index(what, index, dev, rows)
+    ck.flat(what, "y", y, torch.float32, B, dev)
     grads, stats, workspace = _grad_outputs(what, critic.shapes, dev, B, grads, stats, workspace,
                                             lambda: twinq_workspace_bytes(critic.dims, B, max_workgroups))
     if workspace is None:
         return grads, stats
-    b = _lib.transitions(obs=obs, action=action, index=index, batch=B, rows=rows, row_stride=action.stride(0) if rows > 1 else max(action.shape[1], 1))
-    g = _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups)
-    q = critic.as_c()
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_twinq_grad(C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_twinq_grad")
+    b = _lib.transitions(obs=obs, action=action, index=index, batch=B, rows=rows, row_stride=row_stride)
+    _lib.launch(dev, "qr_twinq_grad", critic.as_c(), b, _lib.twinq_grad_args(grads, stats, y, workspace, max_workgroups))
     return grads, stats
 
 
@@ -616,21 +534,16 @@ def _critic_update_state(critic_module, buffer: ReplayBuffer, k: int, index, max
     where there is none), its `QCriticParams` (action_dim: agent k's, or what the centralized form gives), and (y, workspace, stats)
     from the buffer's cache under tag + (k, B, max_workgroups)."""
     layers = [getattr(critic_module, f"fc{j}") for j in range(1, 7)]
-    grads = {}
-    for n, p in zip(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias))):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
+    grads = module_grads(_lib.TWINQ_GRAD_NAMES, (t for l in layers for t in (l.weight, l.bias)))
     critic = QCriticParams.from_module(critic_module, buffer.action_dims[k] if action_dim is None else action_dim)
     B = buffer.capacity if index is None else index.numel()
-    key = tag + (k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
+    dev = critic.device
+
+    def make():
         need = twinq_workspace_bytes(critic.dims, B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
-                                    torch.empty(4, dtype=torch.float32, device=dev))
-    return grads, critic, hit
+        return (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(need, dtype=torch.float64, device=dev),
+                torch.empty(4, dtype=torch.float32, device=dev))
+    return grads, critic, buffer._scratch(tag + (k, B, int(max_workgroups)), make)
 
 
 def td3_critic_loss(critic_module, critic_target_module, actor_target_module, buffer: ReplayBuffer, k: int = 0,
@@ -646,9 +559,7 @@ def td3_critic_loss(critic_module, critic_target_module, actor_target_module, bu
     one `optim.PolyakAdamW` group of all twelve tensors, or torch's."""
     A = buffer.action_dims[k]
     grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups)
-    m = actor_target_module
-    actor = ActorParams(m.fc1.weight.data, m.fc1.bias.data, m.fc2.weight.data, m.fc2.bias.data, m.fc3.weight.data, m.fc3.bias.data, None)
-    td3_target(actor, QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
+    td3_target(_td3_actor(actor_target_module), QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
                noise_clip=noise_clip, max_action=max_action, noise=noise, out=y)
     _, stats = twinq_grad(critic, buffer.obs[k], buffer.act[k], y, index, grads=grads, stats=own_stats if stats is None else stats,
                           workspace=workspace, max_workgroups=max_workgroups)
@@ -667,9 +578,7 @@ def td3_critic_loss_ctde(critic_module, critic_target_module, actor_target_modul
         raise ValueError("td3_critic_loss_ctde: buffer must be a ReplayBuffer")
     A = sum(buffer.action_dims)
     grads, critic, (y, workspace, own_stats) = _critic_update_state(critic_module, buffer, k, index, max_workgroups, ("td3_ctde",), action_dim=A)
-    actors = [ActorParams(m.fc1.weight.data, m.fc1.bias.data, m.fc2.weight.data, m.fc2.bias.data, m.fc3.weight.data, m.fc3.bias.data, None)
-              for m in actor_target_modules]
-    td3_target_ctde(actors, QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
+    td3_target_ctde([_td3_actor(m) for m in actor_target_modules], QCriticParams.from_module(critic_target_module, A), buffer, k, index, discount=discount, target_noise=target_noise,
                     noise_clip=noise_clip, max_action=max_action, noise=noise, out=y)
     _, stats = twinq_grad_ctde(critic, buffer.obs, buffer.act, y, index, grads=grads, stats=own_stats if stats is None else stats,
                                workspace=workspace, max_workgroups=max_workgroups)
@@ -678,9 +587,7 @@ def td3_critic_loss_ctde(critic_module, critic_target_module, actor_target_modul
 
 def dpg_actor_workspace_bytes(actor_dims, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `dpg_actor_grad` call needs (qr_dpg_actor_workspace_bytes); actor_dims = (obs_dim, hidden, action_dim)."""
-    n = _lib.load().qr_dpg_actor_workspace_bytes(*(int(d) for d in actor_dims), int(critic_hidden), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_dpg_actor_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_dpg_actor_workspace_bytes", *actor_dims, critic_hidden, batch, max_workgroups)
 
 
 def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor, obs_next: Optional[torch.Tensor] = None,
@@ -701,19 +608,16 @@ def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
     what = "dpg_actor_grad"
     dev = critic.device
     D, A, H = critic.dims
-    shapes = _check_actor(actor, D, A, dev, what, _lib.ACTOR_TANH_MEAN, False, "the actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
-    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
-        if not 0.0 <= float(v) < float("inf"):
-            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
-    rows = _rows(obs, D, dev, what, "obs")
-    if lam_T != 0 and _rows(obs_next, D, dev, what, "obs_next") != rows:
+    shapes = ck.actor(what, actor, PPO_ACTOR_DIMS, D, A, dev, _lib.ACTOR_TANH_MEAN, False, "the actor must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
+    ck.nonneg(what, ck.LAMS, lam_T, lam_S, lam_M, max_action)
+    rows = ck.rows(what, "obs", obs, D, dev)
+    if lam_T != 0 and ck.rows(what, "obs_next", obs_next, D, dev) != rows:
         raise ValueError(f"{what}: obs_next must have obs's {rows} rows")
     if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
         raise ValueError(f"{what}: noise [{D}] is required when lam_S != 0, nominal [{A}] when lam_M != 0")
-    _vector(noise, D, dev, what, "noise")
-    _vector(nominal, A, dev, what, "nominal")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
+    ck.flat(what, "noise", noise, torch.float32, D, dev, True)
+    ck.flat(what, "nominal", nominal, torch.float32, A, dev, True)
+    B = ck.index(what, index, dev, rows)
     grads, stats, workspace = _grad_outputs(what, shapes, dev, B, grads, stats, workspace,
                                             lambda: dpg_actor_workspace_bytes(actor.dims, H, B, max_workgroups), size_given=False)
     if workspace is None:
@@ -721,11 +625,9 @@ def dpg_actor_grad(actor: ActorParams, critic: QCriticParams, obs: torch.Tensor,
     b = _lib.transitions(obs=obs, obs_next=obs_next if lam_T != 0 else None, index=index, batch=B, rows=rows)
     g = _lib.dpg_grad_args(grads, stats, noise if lam_S != 0 else None, nominal if lam_M != 0 else None, workspace, lam_T=lam_T, lam_S=lam_S,
                            lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
-    p, q = actor.as_c(), critic.as_c()
+    p = actor.as_c()
     p.log_std = None
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_dpg_actor_grad(C.byref(p), C.byref(q), C.byref(b), C.byref(g), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_dpg_actor_grad")
+    _lib.launch(dev, "qr_dpg_actor_grad", p, critic.as_c(), b, g)
     return grads, stats
 
 
@@ -739,18 +641,11 @@ def td3_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
     Returns stats (stats[0] = the loss).  From the second call on with an unchanged B nothing is allocated: the workspace and stats
     are cached on the buffer.  The optimiser step follows on these .grad tensors (`optim.DeviceAdamW`, or torch's), then
     `soft_update`."""
-    layers = [actor_module.fc1, actor_module.fc2, actor_module.fc3]
     grads = _actor_grads(actor_module)
-    actor = ActorParams(*(t.data for l in layers for t in (l.weight, l.bias)), None)
+    actor = _td3_actor(actor_module)
     critic = QCriticParams.from_module(critic_module, buffer.action_dims[k])
-    B = buffer.capacity if index is None else index.numel()
-    key = ("actor", k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = dpg_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.float32, device=dev))
-    workspace, own_stats = hit
+    workspace, own_stats = buffer._actor_scratch("actor", k, index, max_workgroups, critic.device,
+                                                 lambda B: dpg_actor_workspace_bytes(actor.dims, critic.dims[2], B, max_workgroups))
     _, stats = dpg_actor_grad(actor, critic, buffer.obs[k], buffer.obs_next[k], index, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
                               max_action=max_action, noise=noise, nominal=nominal, grads=grads, stats=own_stats if stats is None else stats,
                               workspace=workspace, max_workgroups=max_workgroups)
@@ -760,9 +655,7 @@ def td3_actor_loss(actor_module, critic_module, buffer: ReplayBuffer, k: int = 0
 def dpg_actor_workspace_bytes_ctde(k: int, critic_hidden: int, batch: int, max_workgroups: int = 0) -> int:
     """Bytes of workspace one `dpg_actor_grad_ctde` call needs for agent k (qr_ctde_dpg_actor_workspace_bytes): `dpg_actor_workspace_bytes`'
     figure for CTDE_ACTOR_DIMS[k]."""
-    n = _lib.load().qr_ctde_dpg_actor_workspace_bytes(int(k), int(critic_hidden), int(batch), int(max_workgroups))
-    _lib.check(n if n < 0 else 0, "qr_ctde_dpg_actor_workspace_bytes")
-    return int(n)
+    return _lib.workspace_bytes("qr_ctde_dpg_actor_workspace_bytes", k, critic_hidden, batch, max_workgroups)
 
 
 _TD3_FORM = (_lib.ACTOR_TANH_MEAN, False, "the actors must be of MLP_Actor_TD3's form: the tanh-of-mean rule, no log_std head")
@@ -770,7 +663,7 @@ _TD3_FORM = (_lib.ACTOR_TANH_MEAN, False, "the actors must be of MLP_Actor_TD3's
 
 def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, index, k, action_other, lam_T, lam_S, lam_M, max_action, noise, nominal,
                        form=_TD3_FORM):
-    """`dpg_actor_grad_ctde`'s and `sac.sac_actor_grad_ctde`'s checks up to the outputs (form: what `_check_actor` asks of both actors):
+    """`dpg_actor_grad_ctde`'s and `sac.sac_actor_grad_ctde`'s checks up to the outputs (form: what `_checks.actor` asks of both actors):
     returns (shapes of agent k's tensors, B, rows, the four widths, obs_next[k])."""
     dev = critic.device
     D, A, H = critic.dims
@@ -789,17 +682,16 @@ def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, 
         if obs[m] is None or obs[m].dim() != 2 or obs[m].shape[1] < 1:
             raise ValueError(f"{what}: obs[{m}] must be a contiguous float32 [rows, width] tensor on {dev}")
     od = [x.shape[1] for x in obs]
-    rows = _rows(obs[0], od[0], dev, what, "obs[0]")
-    if _rows(obs[1], od[1], dev, what, "obs[1]") != rows:
+    rows = ck.rows(what, "obs[0]", obs[0], od[0], dev)
+    if ck.rows(what, "obs[1]", obs[1], od[1], dev) != rows:
         raise ValueError(f"{what}: obs[1] must have obs[0]'s {rows} rows")
-    _check_index(index, dev, what)
-    B = rows if index is None else index.numel()
+    B = ck.index(what, index, dev, rows)
     ad = [0, 0]
     ad[k] = actors[k].dims[2]
     if action_other is not None:
-        if action_other.dtype != torch.float32 or action_other.device != dev or action_other.dim() != 2 or action_other.shape[0] != B \
-                or action_other.shape[1] < 1 or not action_other.is_contiguous():
-            raise ValueError(f"{what}: action_other must be a contiguous float32 [{B}, width] tensor on {dev}")
+        ck.tensor(what, "action_other", action_other, torch.float32, (B, "width"), dev)
+        if action_other.shape[1] < 1:
+            raise ValueError(f"{what}: action_other must hold at least one column")
         ad[o] = action_other.shape[1]
     else:
         ad[o] = actors[o].dims[2]
@@ -809,24 +701,22 @@ def _ctde_actor_launch(what: str, actors, critic: QCriticParams, obs, obs_next, 
     for m in (k, o):
         if actors[m] is None:
             continue
-        s = _check_actor(actors[m], od[m], ad[m], dev, what, *form)
+        s = ck.actor(what, actors[m], PPO_ACTOR_DIMS, od[m], ad[m], dev, *form)
         if actors[m].dims != CTDE_ACTOR_DIMS[m]:
             raise ValueError(f"{what}: actor {m} must have the sizes {CTDE_ACTOR_DIMS[m]} (obs, hidden, action), got {actors[m].dims}")
         shapes = s if m == k else shapes
-    for name, v in (("lam_T", lam_T), ("lam_S", lam_S), ("lam_M", lam_M), ("max_action", max_action)):
-        if not 0.0 <= float(v) < float("inf"):
-            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v}")
+    ck.nonneg(what, ck.LAMS, lam_T, lam_S, lam_M, max_action)
     nxt = None
     if lam_T != 0:
         nxt = tuple(obs_next)[k] if obs_next is not None and len(tuple(obs_next)) == 2 else None
         if nxt is None:
             raise ValueError(f"{what}: obs_next must be a pair whose entry {k} is given when lam_T != 0")
-        if _rows(nxt, od[k], dev, what, f"obs_next[{k}]") != rows:
+        if ck.rows(what, f"obs_next[{k}]", nxt, od[k], dev) != rows:
             raise ValueError(f"{what}: obs_next[{k}] must have obs's {rows} rows")
     if (lam_S != 0 and noise is None) or (lam_M != 0 and nominal is None):
         raise ValueError(f"{what}: noise [{od[k]}] is required when lam_S != 0, nominal [{ad[k]}] when lam_M != 0")
-    _vector(noise, od[k], dev, what, "noise")
-    _vector(nominal, ad[k], dev, what, "nominal")
+    ck.flat(what, "noise", noise, torch.float32, od[k], dev, True)
+    ck.flat(what, "nominal", nominal, torch.float32, ad[k], dev, True)
     return shapes, B, rows, od, ad, nxt
 
 
@@ -856,26 +746,13 @@ def dpg_actor_grad_ctde(actors, critic: QCriticParams, obs, obs_next=None, index
     b = _lib.ctde_transitions(obs=obs, obs_next=(nxt, None) if k == 0 else (None, nxt), index=index, batch=B, rows=rows, obs_dims=od, action_dims=ad)
     g = _lib.ctde_dpg_grad_args(grads, stats, noise if lam_S != 0 else None, nominal if lam_M != 0 else None, workspace, agent=k,
                                 action_other=action_other, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M, max_action=max_action, max_workgroups=max_workgroups)
-    q = critic.as_c()
-    p = [None if a is None else a.as_c() for a in actors]
-    for c in p:
-        if c is not None:
-            c.log_std = None
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_ctde_dpg_actor_grad(*(None if c is None else C.byref(c) for c in p), C.byref(q), C.byref(b), C.byref(g),
-                                                torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_ctde_dpg_actor_grad")
+    _lib.launch(dev, "qr_ctde_dpg_actor_grad", *_ctde_actors_c(actors), critic.as_c(), b, g)
     return grads, stats
 
 
 def _actor_grads(actor_module) -> dict:
     """The live actor's six .grad tensors by name, made where there is none."""
-    grads = {}
-    for n, p in zip(_lib.DPG_GRAD_NAMES, (t for l in (actor_module.fc1, actor_module.fc2, actor_module.fc3) for t in (l.weight, l.bias))):
-        if p.grad is None or not p.grad.is_contiguous():
-            p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        grads[n] = p.grad
-    return grads
+    return module_grads(_lib.DPG_GRAD_NAMES, (t for l in (actor_module.fc1, actor_module.fc2, actor_module.fc3) for t in (l.weight, l.bias)))
 
 
 def td3_actor_loss_ctde(actor_modules, critic_module, buffer: ReplayBuffer, k: int = 0, index: Optional[torch.Tensor] = None, *,
@@ -896,19 +773,12 @@ def td3_actor_loss_ctde(actor_modules, critic_module, buffer: ReplayBuffer, k: i
     if len(actor_modules) != 2:
         raise ValueError(f"{what}: actor_modules must be the pair of both agents' actors")
     grads = _actor_grads(actor_modules[k])
-    actors = [ActorParams(*(t.data for l in (m.fc1, m.fc2, m.fc3) for t in (l.weight, l.bias)), None) for m in actor_modules]
     critic = QCriticParams.from_module(critic_module, sum(buffer.action_dims))
-    B = buffer.capacity if index is None else index.numel()
-    key = ("actor_ctde", k, B, int(max_workgroups))
-    hit = buffer._cache.get(key)
-    if hit is None:
-        dev = critic.device
-        need = dpg_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups) // 8 if B else 0
-        hit = buffer._cache[key] = (torch.empty(need, dtype=torch.float64, device=dev), torch.empty(4, dtype=torch.float32, device=dev))
-    workspace, own_stats = hit
-    _, stats = dpg_actor_grad_ctde(actors, critic, buffer.obs, buffer.obs_next, index, k=k, lam_T=lam_T, lam_S=lam_S, lam_M=lam_M,
-                                   max_action=max_action, noise=noise, nominal=nominal, grads=grads, stats=own_stats if stats is None else stats,
-                                   workspace=workspace, max_workgroups=max_workgroups)
+    workspace, own_stats = buffer._actor_scratch("actor_ctde", k, index, max_workgroups, critic.device,
+                                                 lambda B: dpg_actor_workspace_bytes_ctde(k, critic.dims[2], B, max_workgroups))
+    _, stats = dpg_actor_grad_ctde([_td3_actor(m) for m in actor_modules], critic, buffer.obs, buffer.obs_next, index, k=k, lam_T=lam_T, lam_S=lam_S,
+                                   lam_M=lam_M, max_action=max_action, noise=noise, nominal=nominal, grads=grads,
+                                   stats=own_stats if stats is None else stats, workspace=workspace, max_workgroups=max_workgroups)
     return stats
 
 
@@ -943,9 +813,5 @@ def soft_update(params, targets, tau: float = 0.005) -> None:
             raise ValueError(f"{what}: pair {k} has {p.numel()} and {t.numel()} elements")
         if p.data_ptr() == t.data_ptr():
             raise ValueError(f"{what}: pair {k}: the target is its own param")
-    if dev.type != "cuda":
-        raise RuntimeError("gym_rotor_amd ops run on the GPU only (no CPU kernel exists)")
-    u = _lib.soft_update_args(ps, ts, tau)
-    with torch.cuda.device(dev):
-        rc = _lib.load().qr_soft_update(C.byref(u), torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "qr_soft_update")
+    ck.require_gpu(dev)
+    _lib.launch(dev, "qr_soft_update", _lib.soft_update_args(ps, ts, tau))
